@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — E-step datapoint-component evaluations per second (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|c1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|c1] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no RANK / WORLD_SIZE in the environment launches the N ranks itself (fresh child
@@ -24,6 +24,10 @@ The JSON line also carries
   cpu_baseline : the NumPy restatement of the reference algorithm (oracle/, verified equal to the
                  reference on golden vectors) timed on this box's host cores on a bounded row sample
   sustained    : the same step repeated for >= 3 s after the timed steps (median / min ms per step).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (the statistic block of the data pass and,
+for the mean-field configs, the ELBO) as DIR/<name>.npy in float64; the inputs depend on the arguments only, so two builds
+can be compared output for output.
 """
 import argparse
 import json
@@ -210,6 +214,23 @@ def cpu_baseline(cfg, X_host):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, S, elbo):
+    """The arrays one timed step hands its caller: the statistics S' (global over the ranks) and the bound (None for Gibbs)."""
+    arrays = {"stats_" + name: getattr(S, name, None) for name in ("n", "sx", "sxx", "sxx_total", "n_rows")}
+    arrays["elbo"] = elbo
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def _rank_ordered(engine):
     """Which association the sum over the ranks has: the torch route follows ShardedEngine (MIMO_SHARDED_RANK_ORDER), the native
     route the library's own switch (mimo_comm.cpp: MIMO_COMM_RANK_ORDER, default on)."""
@@ -258,9 +279,13 @@ def main(argv=None, engine_factory=None, launcher=None):
     ap.add_argument("--no-sustained", action="store_true")
     ap.add_argument("--no-sample", action="store_true",
                     help="drop the reference's per-iteration likelihood.params = posterior.rvs() (sample_likelihood=False)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--sustained-seconds", type=float, default=10.0,
                     help="length of the sustained leg after the timed steps (>= 10 s: a 5-second utilisation sampler must see it)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and world_env is None and "RANK" not in os.environ:
@@ -287,6 +312,7 @@ def main(argv=None, engine_factory=None, launcher=None):
         else:
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device(device))
 
+    from mimo_amd.engine import SuffStats
     from mimo_amd.sharded import ShardedEngine
 
     cfg = CONFIGS[args.config]
@@ -350,6 +376,9 @@ def main(argv=None, engine_factory=None, launcher=None):
         vlb.append(v)
     barrier()
     elapsed = time.perf_counter() - t0
+    # the last timed step's outputs, copied before the sustained leg runs more steps
+    last_outputs = (SuffStats(*(None if getattr(S, k, None) is None else np.array(getattr(S, k)) for k in SuffStats.__slots__)),
+                    None if v is None else float(v))
     kernel_ms, launches, kinfo = prof(True)
     kinfo = {k: {"ms_per_launch": v["ms"] / max(v["launches"], 1), "launches_per_step": v["launches"] / max(args.steps, 1)}
              for k, v in kinfo.items()}
@@ -449,6 +478,8 @@ def main(argv=None, engine_factory=None, launcher=None):
             out["elbo_first_last"] = [float(vlb[0]), float(vlb[-1])]
         if sustained:
             out["sustained"] = sustained
+        if args.dump_outputs:
+            out["dumped_outputs"] = dump_outputs(args.dump_outputs, *last_outputs)
         if world == 1 and not args.no_cpu_baseline and not dry:
             out["cpu_baseline"] = cpu_baseline(cfg, X[:600_000].cpu().numpy())
         else:

@@ -1,10 +1,9 @@
-"""Generate golden vectors by importing the REFERENCE (hanyas/mimo) in the build container.
+"""Generate golden vectors by importing the REFERENCE (hanyas/mimo) from a checkout of it.
 
-    PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg python tests/golden/make_golden.py
+    MIMO_REFERENCE=<checkout of hanyas/mimo> PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg python tests/golden/make_golden.py
 
 Writes tests/golden/*.npz (inputs and the reference's outputs only — no reference code).  The
-reference lives at /root/reference, is read-only, and never travels to the GPU box; the committed
-.npz files do.  Seeds are fixed, so the files are reproducible bit-for-bit on this image
+reference is only read, and the tests never need it: they read the committed .npz files.  Seeds are fixed, so the files are reproducible bit-for-bit on this image
 (numpy 2.2.6 / scipy 1.15.3 / OpenBLAS 0.3.29).
 """
 import copy
@@ -15,7 +14,9 @@ os.environ.setdefault("MPLBACKEND", "Agg")
 sys.dont_write_bytecode = True
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, "/root/reference")
+if not os.environ.get("MIMO_REFERENCE"):
+    raise SystemExit("set MIMO_REFERENCE to a checkout of the reference (hanyas/mimo)")
+sys.path.insert(0, os.environ["MIMO_REFERENCE"])
 sys.path.insert(0, ROOT)
 
 import numpy as np

@@ -56,3 +56,32 @@ def test_bench_py_carries_no_test_hook():
 def test_world_size_mismatch_is_an_error():
     p = _run(["--gpus", "2", "--rows", "1000"], {"RANK": "0", "WORLD_SIZE": "1", "REAL_BENCH": "1"})
     assert p.returncode != 0 and "WORLD_SIZE" in (p.stderr + p.stdout)
+
+
+@pytest.mark.parametrize("config", ["c2", "c3"])
+def test_bench_dumps_the_last_step_outputs(config, tmp_path):
+    """--dump-outputs DIR: what the last timed step returned, float64 .npy files, the same from run to run; --steps sets the
+    number of timed steps."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        p = _run(["--rows", "2000", "--steps", "3", "--warmup", "1", "--config", config, "--no-cpu-baseline",
+                  "--dump-outputs", str(out)], {"BENCH_DRY_RUN_DOUBLE": "oracle_engine:OracleEngine"})
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        K, D = d["config"]["K"], d["config"]["Dz"]
+        files = {f.stem: np.load(f) for f in out.glob("*.npy")}
+        assert set(files) == set(d["dumped_outputs"]) and {"stats_n", "stats_sx", "stats_sxx"} <= set(files)
+        assert ("elbo" in files) == (config != "c3")
+        assert files["stats_n"].shape == (K,) and files["stats_sxx"].shape == (K, D, D)
+        assert all(a.dtype == np.float64 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert abs(files["stats_n"].sum() - 2000) < 1e-6
+        runs.append(files)
+    assert all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
+
+
+def test_bench_rejects_zero_steps():
+    p = _run(["--rows", "1000", "--steps", "0"], {"BENCH_DRY_RUN_DOUBLE": "oracle_engine:OracleEngine"})
+    assert p.returncode != 0 and "--steps" in p.stderr

@@ -4,7 +4,8 @@ times, (i) the (row, component) pairs whose l - max < -707 (their exponential is
 that are dead for ALL 16 rows of a wave step — in the kernel's component layout and in contiguous layouts.  Result (profiles/r04_c3_exp_skip_potential.txt):
 55 - 77 % of the exponentials are dead, 0.0 % of the chunks: rows of one step belong to different clusters.  VERDICT round 3, item 5."""
 import sys, os
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np, torch
 import bench
 from oracle_engine import OracleEngine

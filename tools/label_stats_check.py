@@ -1,6 +1,6 @@
 """Diagnostic: mimo_label_stats of a caller's label vector at Dz > 16 (one-pass kernel over the ranked tiles), small and large K, against the oracle."""
-import sys, numpy as np
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mimo_amd.engine import HipEngine
 from oracle import mimo_oracle as O
 eng = HipEngine(0)

@@ -476,6 +476,9 @@ int mimo_data_checksum(mimo_ctx* ctx, uint64_t out[2]);
 /* Test / tuning hook: overrides a launch-geometry value for later calls.  Keys:
  *   "num_cu"       (per context) the compute-unit count every persistent grid is sized from; 0 restores the device's own.
  *                  A small value makes every workgroup of every kernel family walk many tiles / steps / ranges at test sizes.
+ *   "resp_skip_log2" (per context, default 60) the mean-field pass on the fused kernel at Dz >= 14 leaves out of the statistics of a
+ *                  16-component row block every datum whose 16 responsibilities there are all below tau = 2^-value; each
+ *                  statistic moves by at most tau * sum_n |phi_nf|, the ELBO scalars not at all.  0: every weight enters.
  *   "sorted_range" (process-wide) cap on the 256-row tiles per range of label_stats_sorted_kernel (default and maximum 80;
  *                  0 restores it): with a low cap a workgroup takes several ranges ("first range writes, later ranges add").
  *   "mid_min_d", "mid_narrow_k" (process-wide) 0 / 0: the mid kernels (mimo_mid.hip) run where they measured fastest.  Otherwise
@@ -484,7 +487,7 @@ int mimo_data_checksum(mimo_ctx* ctx, uint64_t out[2]);
  *   "mid_labels_min_d" (process-wide) smallest Dz whose label pass (K <= 48) runs on the mid kernel's label mode; 0: where it measured ahead.
  *   "narrow_big_vi" (process-wide) largest K (129 .. 256) whose softmax pass over at most two contraction steps runs on the narrow
  *                  kernels of mimo_narrow_big.hip; 0: where they measured ahead (256 for one step, 192 for two).
- * Results do not depend on either value beyond the documented summation order of the partial blocks.  MIMO_E_INVALID for
+ * Results do not depend on the geometry keys beyond the documented summation order of the partial blocks.  MIMO_E_INVALID for
  * an unknown key or a value out of range.  The reference has no counterpart (launch geometry is ours). */
 int mimo_tune(mimo_ctx* ctx, const char* key, int64_t value);
 

@@ -30,6 +30,7 @@ struct mimo_ctx {
   int device = 0;
   int num_cu = 256;       // what the grids are sized from (mimo_tune "num_cu" overrides it for tests)
   int hw_num_cu = 256;
+  int resp_skip_log2 = 60;  // fused softmax pass: statistics skip the row blocks whose weights are all < 2^-60 (0: dense)
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   char err[512] = {0};   // fixed buffer: reporting an error never allocates
@@ -262,6 +263,7 @@ static void fill_args(mimo_ctx* ctx, int K, KernelArgs* a) {
   a->diag = ctx->structure != 0;
   a->ntiles = (ctx->N + kTile - 1) / kTile;
   a->aux = ctx->ls_aux;
+  a->resp_skip = ctx->resp_skip_log2;
 }
 
 // (c, b, W) -> Theta[k][f] -> MFMA A-operand image [K16][F16/4][64] on the device.
@@ -1653,6 +1655,11 @@ int mimo_tune(mimo_ctx* ctx, const char* key, int64_t value) {
     if (!strcmp(key, "num_cu")) {
       if (value < 0 || value > 4096) return fail(ctx, MIMO_E_INVALID, "mimo_tune: num_cu = %lld outside [0, 4096]", (long long)value);
       ctx->num_cu = value == 0 ? ctx->hw_num_cu : (int)value;
+      return MIMO_OK;
+    }
+    if (!strcmp(key, "resp_skip_log2")) {
+      if (value < 0 || value > 1000) return fail(ctx, MIMO_E_INVALID, "mimo_tune: resp_skip_log2 = %lld outside [0, 1000]", (long long)value);
+      ctx->resp_skip_log2 = (int)value;
       return MIMO_OK;
     }
     if (!strcmp(key, "sorted_range")) {

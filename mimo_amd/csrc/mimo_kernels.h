@@ -55,6 +55,8 @@ struct KernelArgs {
   int presort;            // the statistics launch reads sort_list / sort_start instead of ranking the tile's labels itself
   int k0;                 // label_stats_wide_kernel: first component of the launch's window (components k0 .. k0 + 127 of K > 128)
   int fuse_hist;          // gibbs_rowwave_kernel counts the labels it draws into aux[0 .. 255] (no label_hist_kernel behind it)
+  int resp_skip;          // fused softmax pass: rows whose 16 weights of a row block are all < 2^-resp_skip skip that block's
+                          // statistics (0: dense; mimo_tune "resp_skip_log2")
 };
 
 // feature count helpers (z~ = [z,1]; features = upper-triangular pairs of z~)

@@ -83,10 +83,13 @@ double philox_uniform_host(uint64_t seed, uint64_t row, uint64_t sweep) {
 #ifndef MIMO_RBW4_ESTEP_WGS
 #define MIMO_RBW4_ESTEP_WGS 2   // workgroups per CU the RBW = 4 E-step kernels with NCB <= 3 are compiled for
 #endif
-template <int NCB, int RBW, int MODE, int DS = 0, int SPLIT = 0>
+// SKIP (fast VI, one row block per wave, not split, Dz >= 14; launched when KernelArgs::resp_skip > 0): the statistics of a
+// row block contract only the rows with a weight >= 2^-resp_skip in it (step 5).
+template <int NCB, int RBW, int MODE, int DS = 0, int SPLIT = 0, bool SKIP = false>
 __global__ __launch_bounds__(kWG, (RBW == 1 ? 2 : (MODE <= kGeneric && RBW == 2) ? 2 : (MODE <= kGeneric && NCB <= 3) ? MIMO_RBW4_ESTEP_WGS
                                    : (MODE > kGeneric && RBW * NCB <= 12) ? 2 : 1))
 void fused_kernel(const KernelArgs a) {
+  static_assert(!SKIP || (MODE == kFastVI && RBW == 1 && SPLIT == 0), "responsibility skip: fast VI, RBW = 1, not split");
   constexpr int SRC = MODE == kModeWeights ? kSrcWeights : MODE == kModeLabels ? kSrcLabels : kSrcEstep;
   // flags fold to constants in the two fast modes
   const bool gibbs = MODE == kFastVI ? false : MODE == kFastGibbs ? true : a.gibbs != 0;
@@ -109,6 +112,8 @@ void fused_kernel(const KernelArgs a) {
   constexpr bool E2K = DS >= 14 && RBW == 1 && MODE <= kGeneric;
   uint8_t* fe = reinterpret_cast<uint8_t*>(etab + (E2K ? kExpTab : 64));  // [F16][2]
   int* labs = reinterpret_cast<int*>(red);       // [32] labels of the tile's rows (red is idle until the epilogue)
+  uint32_t* live = reinterpret_cast<uint32_t*>(red);   // SKIP: [K16] member masks of the row blocks (rows of the tile)
+  const double lnt = SKIP ? -0.6931471805599453 * a.resp_skip : 0.0;   // ln tau, tau = 2^-resp_skip
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: wave-uniform branches and SGPR bases
@@ -397,8 +402,9 @@ void fused_kernel(const KernelArgs a) {
       // ---- 4. normalise over k: 8 lanes per datum, 2*K16 consecutive components per lane ----------
       __builtin_amdgcn_s_setprio(2);
       if constexpr (RBW == 1)
-        normalise_tile<RBW, MODE, E2K>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp, out_lse,
-                                  sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T);
+        normalise_tile<RBW, MODE, E2K, SKIP>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
+                                             out_lse, sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T, lnt,
+                                             live);
       else
         normalise_tile_chunked<RBW, MODE>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
                                           out_lse, sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T);
@@ -550,8 +556,47 @@ void fused_kernel(const KernelArgs a) {
         if (K16 >= 2) stats_sparse();
         else stats_nact(std::true_type{});
       };
+      // Soft responsibilities (SKIP): the rows of this wave's row block with a weight >= tau there (mask of the
+      // normalise phase, wave-uniform: SGPRs) are contracted 4 at a time in ascending row order; lane (kk = q) takes
+      // member q of the group, an empty slot repeats the group's first row with A = 0.  The rows left out hold weights
+      // < tau only; a tile with every row live costs the dense body's 8 steps.  Neither a dense fallback for full masks
+      // nor operands of the next group read ahead fit: both pushed this instantiation from 208 VGPRs into scratch
+      // (C2 shape: 4 and 23 - 138 spilled registers), so each group's LDS latency is left to the co-resident workgroup.
+      auto stats_skip = [&](uint32_t mrow) {
+        const double* ltc = Lt + (16 * wave + j);
+        const double* phc = Ph + j;
+        double avq, bvq[NCB];
+        auto fetch = [&]() {
+          const int cnt = __builtin_popcount(mrow);   // (scalar) members left: the group takes min(cnt, 4)
+          const uint32_t d0 = __builtin_ctz(mrow);
+          mrow &= mrow - 1;
+          const uint32_t d1 = mrow ? __builtin_ctz(mrow) : d0;
+          mrow &= mrow - 1;
+          const uint32_t d2 = mrow ? __builtin_ctz(mrow) : d0;
+          mrow &= mrow - 1;
+          const uint32_t d3 = mrow ? __builtin_ctz(mrow) : d0;
+          mrow &= mrow - 1;
+          const uint32_t packed = d0 | (d1 << 8) | (d2 << 16) | (d3 << 24);
+          const int row = (int)((packed >> (8 * q)) & 0xFFu);
+          const double v = ltc[row * LS];
+          avq = q < cnt ? v : 0.0;
+          const double* pb = phc + row * RS;
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb) bvq[cb] = pb[16 * cb];
+        };
+        auto issue = [&]() {
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb)
+            sacc[0][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(avq, bvq[cb], sacc[0][cb], 0, 0, 0);
+        };
+        while (mrow) {
+          fetch();
+          issue();
+        }
+      };
       if constexpr (MODE == kFastGibbs || MODE == kModeLabels) stats_labels();
       else if constexpr (MODE == kGeneric) { if (gibbs) stats_labels(); else stats_nact(std::false_type{}); }
+      else if constexpr (SKIP) stats_skip(__builtin_amdgcn_readfirstlane(live[wave]));
       else stats_nact(std::false_type{});
     }
 
@@ -1110,9 +1155,14 @@ constexpr int ncb_of(int D) { return ((D + 1) * (D + 2) / 2 + 15) / 16; }
 
 // E-step modes: one instantiation per Dz (compile-time feature map)
 template <int D, int RBW>
-static fused_fn pick_estep_mode(int mode) {
+static fused_fn pick_estep_mode(int mode, bool skip) {
   switch (mode) {
-    case kFastVI: return fused_kernel<ncb_of(D), RBW, kFastVI, D>;
+    case kFastVI:
+      // SKIP only where it costs no occupancy: at Dz >= 14 the LDS (feature tile + 2048-entry exp table) holds the
+      // kernel at two workgroups per CU whatever its registers.  Below, the skip's extra VGPRs cost a workgroup per CU
+      // (Dz = 12: 3 -> 2, Dz = 6 .. 8: 4 -> 3), which a pass with dense responsibilities would pay in full.
+      if constexpr (RBW == 1 && D >= 14) if (skip) return fused_kernel<ncb_of(D), 1, kFastVI, D, 0, true>;
+      return fused_kernel<ncb_of(D), RBW, kFastVI, D>;
     case kFastGibbs: return fused_kernel<ncb_of(D), RBW, kFastGibbs, D>;
     case kGeneric: return fused_kernel<ncb_of(D), RBW, kGeneric, D>;
   }
@@ -1120,28 +1170,28 @@ static fused_fn pick_estep_mode(int mode) {
 }
 
 template <int RBW>
-static fused_fn pick_estep(int D, int mode) {
+static fused_fn pick_estep(int D, int mode, bool skip = false) {
   switch (D) {
-    case 1: return pick_estep_mode<1, RBW>(mode);
-    case 2: return pick_estep_mode<2, RBW>(mode);
-    case 3: return pick_estep_mode<3, RBW>(mode);
-    case 4: return pick_estep_mode<4, RBW>(mode);
-    case 5: return pick_estep_mode<5, RBW>(mode);
-    case 6: return pick_estep_mode<6, RBW>(mode);
-    case 7: return pick_estep_mode<7, RBW>(mode);
-    case 8: return pick_estep_mode<8, RBW>(mode);
-    case 9: return pick_estep_mode<9, RBW>(mode);
+    case 1: return pick_estep_mode<1, RBW>(mode, skip);
+    case 2: return pick_estep_mode<2, RBW>(mode, skip);
+    case 3: return pick_estep_mode<3, RBW>(mode, skip);
+    case 4: return pick_estep_mode<4, RBW>(mode, skip);
+    case 5: return pick_estep_mode<5, RBW>(mode, skip);
+    case 6: return pick_estep_mode<6, RBW>(mode, skip);
+    case 7: return pick_estep_mode<7, RBW>(mode, skip);
+    case 8: return pick_estep_mode<8, RBW>(mode, skip);
+    case 9: return pick_estep_mode<9, RBW>(mode, skip);
     default: break;
   }
   if constexpr (RBW == 1) {
     switch (D) {
-      case 10: return pick_estep_mode<10, 1>(mode);
-      case 11: return pick_estep_mode<11, 1>(mode);
-      case 12: return pick_estep_mode<12, 1>(mode);
-      case 13: return pick_estep_mode<13, 1>(mode);
-      case 14: return pick_estep_mode<14, 1>(mode);
-      case 15: return pick_estep_mode<15, 1>(mode);
-      case 16: return pick_estep_mode<16, 1>(mode);
+      case 10: return pick_estep_mode<10, 1>(mode, skip);
+      case 11: return pick_estep_mode<11, 1>(mode, skip);
+      case 12: return pick_estep_mode<12, 1>(mode, skip);
+      case 13: return pick_estep_mode<13, 1>(mode, skip);
+      case 14: return pick_estep_mode<14, 1>(mode, skip);
+      case 15: return pick_estep_mode<15, 1>(mode, skip);
+      case 16: return pick_estep_mode<16, 1>(mode, skip);
     }
   }
   return nullptr;
@@ -1230,7 +1280,7 @@ static fused_fn resolve_fused(const KernelArgs& a, int src) {
     static const bool rbw2 = [] { const char* e = getenv("MIMO_ESTEP_RBW2"); return !e || atoi(e) != 0; }();   // tuning knob
     if (rbw2 && a.K16 > 4 && a.K16 <= 8) if (fused_fn f = pick_estep<2>(a.D, mode)) return f;
     if (rbw2 && a.K16 > 8 && a.K16 <= 12) if (fused_fn f = pick_estep<3>(a.D, mode)) return f;     // 128 < K <= 192: three
-    return rbw_for(a.K16) == 1 ? pick_estep<1>(a.D, mode) : pick_estep<4>(a.D, mode);
+    return rbw_for(a.K16) == 1 ? pick_estep<1>(a.D, mode, a.resp_skip > 0) : pick_estep<4>(a.D, mode);
   }
   if (a.K16 <= 2 && ncb >= 3) {   // K <= 32: split distribution of the statistics column blocks (see fused_kernel, SPLIT)
     static const bool on = [] { const char* e = getenv("MIMO_SPLIT_STATS"); return !e || atoi(e) != 0; }();   // tuning knob

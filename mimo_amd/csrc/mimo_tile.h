@@ -90,16 +90,22 @@ __device__ __forceinline__ void build_features_static(const double (&z)[D + 2], 
 // Per-datum normalisation over k of one 32-row tile held in LDS as Lt[row][component]:
 // 8 lanes per datum, 2*K16 consecutive components per lane (<= 8 here: RBW = 1), fully unrolled.
 // Softmax -> r written back in place, or inverse-CDF categorical draw -> label (LDS + HBM).
+// SKIP (softmax of the fast VI mode): also the member masks of the responsibility skip.  Row pt is live in row block b
+// when one of its 16 components there has l - m >= lnt = ln tau, i.e. e >= tau; r = e / sum e <= e, so every weight
+// of a row left out of block b is below tau.  live[b] (32 bits, LDS) gets bit pt for each live row of the tile: wave w
+// writes byte w of every word (its rows 8w .. 8w+7), so the words need no clearing between tiles.
 // ------------------------------------------------------------------------------------------
-template <int RBW, int MODE, bool E2K = false>
+template <int RBW, int MODE, bool E2K = false, bool SKIP = false>
 __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __restrict__ Lt, const int LS,
                                                const double* __restrict__ etab, const int K, const int K16,
                                                const int64_t N, const int64_t n0, const int wave, const int lane,
                                                const bool gibbs, double* const out_logp, double* const out_resp,
                                                double* const out_lse, double& sc_lse, double& sc_rl, double& sc_prod,
                                                int* __restrict__ labs, PhiloxBatch& pb,
-                                               const int64_t tstride) {
+                                               const int64_t tstride, const double lnt = 0.0,
+                                               uint32_t* __restrict__ live = nullptr) {
         static_assert(RBW == 1, "register variant: at most 8 components per lane");
+        static_assert(!SKIP || MODE == kFastVI, "responsibility skip: softmax of the fast VI mode only");
         const int pt = 8 * wave + (lane & 7), part = lane >> 3;
         const int CPP = 2 * K16, k0 = part * CPP;
         const int64_t n = n0 + pt;
@@ -125,6 +131,29 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
         m = fmax(m, __shfl_xor(m, 8));
         m = fmax(m, __shfl_xor(m, 16));
         m = fmax(m, __shfl_xor(m, 32));
+
+        if constexpr (SKIP) {
+          // bit b of lb: one of this lane's slots in row block b is live (masked slots hold -inf: never live).
+          // FULL: the lane's 8 slots lie in one row block (part >> 1); else 2*K16 < 8 slots may straddle two.
+          uint32_t lb = 0;
+#pragma unroll
+          for (int c = 0; c < 8; ++c)
+            if (ok(c) && x[c] - m >= lnt) lb |= FULL ? 1u << (part >> 1) : 1u << ((k0 + c) >> 4);
+          if (!valid) lb = 0;
+          // per row block: ballot over the wave (bit 8 part + i: row 8 wave + i), OR over the 8 parts -> one byte
+          uint32_t bytes = 0;
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            if (b < K16) {
+              const uint64_t bal = __ballot((lb >> b) & 1u);
+              uint32_t v = (uint32_t)bal | (uint32_t)(bal >> 32);
+              v |= v >> 16;
+              v |= v >> 8;
+              bytes |= (v & 0xFFu) << (8 * b);
+            }
+          }
+          if (lane < K16) reinterpret_cast<uint8_t*>(live)[4 * lane + wave] = (uint8_t)(bytes >> (8 * lane));
+        }
 
 #pragma unroll
         for (int c = 0; c < 8; ++c) {

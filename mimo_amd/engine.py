@@ -245,7 +245,8 @@ class HipEngine(BoundDataGuard):
         return sc
 
     def tune(self, key, value):
-        """Launch-geometry override for tests and experiments (mimo_tune): 'num_cu' (0: the device's own), 'sorted_range'."""
+        """Launch-geometry override for tests and experiments (mimo_tune): 'num_cu' (0: the device's own), 'sorted_range',
+        'resp_skip_log2' (statistics skip weights below 2^-value, default 60; 0: dense)."""
         self._check(self._lib.mimo_tune(self._ctx, key.encode(), int(value)))
 
     def profile(self, enable=True):

@@ -1,0 +1,65 @@
+"""24 mixtures of linear-Gaussian experts fitted at once (the flow of the reference's examples/ilr/evaluate_sinc_parallel.py,
+which runs the 24 fits with joblib.Parallel): a noisy sinc, 24 random 80 % train splits, one ILR model per split
+(stick-breaking gating over 100 experts, dx = dy = 1, affine experts, inputs and outputs standardised per model), all fitted
+by meanfield_coordinate_descent_batched — one batched softmax pass per iteration for all 24 models."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from mimo_amd.distributions import (TruncatedStickBreaking, CategoricalWithStickBreaking, StackedNormalWisharts,
+                                    StackedGaussiansWithNormalWisharts, StackedMatrixNormalWisharts,
+                                    StackedLinearGaussiansWithMatrixNormalWisharts)
+from mimo_amd.engine import HipEngine
+from mimo_amd.mixtures import BayesianMixtureOfLinearGaussians
+from mimo_amd.mixtures.batched import meanfield_coordinate_descent_batched
+
+
+def make_model(K, engine):
+    dx = dy = 1
+    gating = CategoricalWithStickBreaking(K, TruncatedStickBreaking(K, np.ones(K), 10. * np.ones(K)))
+    basis_prior = StackedNormalWisharts(K, dx, np.zeros((K, dx)), 1e-2 * np.ones(K), np.stack(K * [np.eye(dx)]),
+                                        (dx + 1.) * np.ones(K) + 1e-8)
+    models_prior = StackedMatrixNormalWisharts(K, dx + 1, dy, np.zeros((K, dy, dx + 1)), np.stack(K * [1e-2 * np.eye(dx + 1)]),
+                                               np.stack(K * [np.eye(dy)]), (dy + 1.) * np.ones(K) + 1e-8)
+    return BayesianMixtureOfLinearGaussians(K, dx, dy, gating,
+                                            StackedGaussiansWithNormalWisharts(K, dx, basis_prior, engine=engine),
+                                            StackedLinearGaussiansWithMatrixNormalWisharts(K, dx + 1, dy, models_prior,
+                                                                                           engine=engine),
+                                            scale=True, engine=engine)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=2000)
+    ap.add_argument("--fits", type=int, default=24)
+    ap.add_argument("--experts", type=int, default=100)
+    ap.add_argument("--iters", type=int, default=250)
+    args = ap.parse_args()
+    rng = np.random.default_rng(1337)
+    x = rng.uniform(-10., 10., size=(args.rows, 1))
+    y = np.sinc(x / np.pi) + 0.1 * rng.standard_normal((args.rows, 1))
+    ntrain = int(0.8 * args.rows)
+    engine = HipEngine(0)
+    models, data = [], []
+    for _ in range(args.fits):
+        idx = rng.permutation(args.rows)[:ntrain]
+        m = make_model(args.experts, engine)
+        m.init_transform(x[idx], y[idx])
+        models.append(m)
+        data.append((x[idx], y[idx]))
+    t0 = time.perf_counter()
+    vlbs = meanfield_coordinate_descent_batched(models, data, randomize=True, init_rng='philox', seeds=range(args.fits),
+                                                maxiter=args.iters, tol=1e-6)
+    wall = time.perf_counter() - t0
+    final = np.array([v[-1] for v in vlbs])
+    print(f"{args.fits} fits of {ntrain} rows, K = {args.experts}: best ELBO {final.max():.2f}, median {np.median(final):.2f}, "
+          f"iterations {min(map(len, vlbs))} - {max(map(len, vlbs))}, wall time {wall:.2f} s")
+
+
+if __name__ == "__main__":
+    main()

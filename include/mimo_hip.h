@@ -278,6 +278,34 @@ int mimo_comm_unique_id(char* id128);
 int mimo_comm_init(mimo_ctx* ctx, const char* id128, int rank, int world);
 int mimo_comm_destroy(mimo_ctx* ctx);
 
+/* ---- batched E-step: many independent mixtures in one launch ---------------------------
+ * B problems that share Dz and K, each with its own rows and its own (c, b, W).
+ * Replaces: B separate runs of the reference's drivers, e.g. the joblib.Parallel loop of
+ *   examples/ilr/evaluate_sinc_parallel.py (one ILR fit per train split) or random restarts of one model.
+ *
+ * Copy the rows of all B problems, concatenated, to the device: Z (N_total, Dz) row-major with problem b owning the
+ * rows [row_off[b], row_off[b+1]) (row_off: B + 1 entries, row_off[0] = 0, non-decreasing; empty problems allowed).
+ * Every element must be finite (MIMO_E_INVALID otherwise: batched mode has no NaN-row semantics).  Dz <= 16
+ * (MIMO_E_UNSUPPORTED otherwise).  The context is in batched mode until the next mimo_upload / mimo_attach: the
+ * single-problem entry points (mimo_estep, mimo_gibbs_labels, mimo_weighted_stats, mimo_predict, ...) return
+ * MIMO_E_INVALID on it. */
+int mimo_upload_batched(mimo_ctx* ctx, const double* Z_host, const int64_t* row_off, int B, int Dz);
+
+/* One softmax pass over all B problems of a batched context: per problem b what mimo_estep returns for its rows and
+ * its parameters (c + b K, b + b K Dz, W + b K Dz Dz).
+ * Replaces: per problem, the calls of mimo_estep (expected_log_likelihood + softmax + weighted_statistics + the data /
+ *   label ELBO terms, see there) that B reference driver runs (the joblib.Parallel workers of
+ *   examples/ilr/evaluate_sinc_parallel.py) make one after another.
+ * c (B,K), b (B,K,Dz), W (B,K,Dz,Dz); S (B, K(1+Dz+Dz²)) or NULL with MIMO_F_NO_STATS; scalars (B,3), the layout of
+ * mimo_estep's scalars per problem.  flags: MIMO_F_NO_STATS, MIMO_F_ENTROPY_SPLIT, MIMO_F_KEEP_LSE (mimo_get_lse then
+ * returns the N_total concatenated rows).  c[k] = -inf allowed, NaN / +inf in c, b, W is MIMO_E_INVALID.
+ * Covered: the full structure, Dz <= 16, K <= 128 and ceil(K/16) * ceil((Dz+1)(Dz+2)/32) <= 40 (K <= 64 at every Dz,
+ * K <= 128 up to Dz = 11); anything else is MIMO_E_UNSUPPORTED.  A context without a batch: MIMO_E_INVALID.
+ * A problem's results do not depend on the other problems of the batch (bit for bit).  The batched pass is not
+ * reduced over ranks: on a context with a communicator (mimo_comm_init) it returns MIMO_E_UNSUPPORTED. */
+int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, int flags,
+                       double* S, double* scalars);
+
 /* ---- copy-outs of device-resident tables ----------------------------------------------- */
 int mimo_get_resp(mimo_ctx* ctx, double* resp_host /* K×N */);
 /* The columns `cols[0 .. ncols)` (row indices of the data) of the resident responsibility table: out (K, ncols) row-major.  What a

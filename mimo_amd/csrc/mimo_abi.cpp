@@ -5,6 +5,7 @@
 #include "../../include/mimo_hip.h"
 #include "mimo_kernels.h"
 #include "mimo_extra.h"
+#include "mimo_batched.h"
 
 #include <algorithm>
 #include <cmath>
@@ -84,6 +85,15 @@ struct mimo_ctx {
   uint16_t* sort_start = nullptr; size_t sort_start_cap = 0;
   double* table_tmp = nullptr;  size_t table_tmp_cap = 0;
   int bad_counts_K = 0;         // > 0: cnt_d[1..K] holds the label counts of the NaN rows of the last label pass
+
+  // batched mode (mimo_upload_batched): Z holds the rows of B problems back to back; the single-problem entry points refuse
+  bool batched = false;
+  int batch_B = 0;
+  int batch_G = 0;                                         // workgroups of the work table
+  std::vector<int64_t> batch_rows;                         // host copy of row_off [B + 1]
+  int64_t* batch_row_off_d = nullptr;                      // [B + 1]
+  BatchedWork* batch_work_d = nullptr;                     // [G]
+  int32_t* batch_wg_off_d = nullptr;                       // [B + 1]: problem b owns the workgroups [wg_off[b], wg_off[b + 1])
 
   void* comm = nullptr;         // RCCL communicator (mimo_comm_init): every pass then returns statistics summed over the ranks
   int comm_world = 1;
@@ -238,7 +248,16 @@ static int prepare_features(mimo_ctx* ctx, int D) {
   return MIMO_OK;
 }
 
+// The single-problem entry points on a context that holds a batch (mimo_upload_batched)
+static int single_only(mimo_ctx* ctx) {
+  if (ctx->batched)
+    return fail(ctx, MIMO_E_INVALID, "the context holds a batch of problems (mimo_upload_batched): single-problem calls need "
+                "mimo_upload or mimo_attach first");
+  return MIMO_OK;
+}
+
 static int check_shapes(mimo_ctx* ctx, int K) {
+  if (single_only(ctx)) return MIMO_E_INVALID;
   if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
   if (!ctx->Z) return fail(ctx, MIMO_E_NODATA, "no data uploaded or attached");
   if (K < 1) return fail(ctx, MIMO_E_INVALID, "K must be >= 1 (got %d)", K);
@@ -985,7 +1004,8 @@ int mimo_destroy(mimo_ctx* ctx) {
   drain_profile(ctx);
   if (ctx->comm) { (void)mimo_comm::destroy(ctx->comm); ctx->comm = nullptr; }
   void* bufs[] = {ctx->sort_list, ctx->sort_start, ctx->ls_aux, ctx->Z_owned, ctx->feat_d, ctx->feat_full_d, ctx->row_mask, ctx->cnt_d, ctx->labels_tmp, ctx->table_tmp, ctx->theta_d, ctx->partials, ctx->reduced, ctx->S_d, ctx->resp,
-                  ctx->logp, ctx->lse, ctx->labels, ctx->u_d, ctx->win, ctx->lin};
+                  ctx->logp, ctx->lse, ctx->labels, ctx->u_d, ctx->win, ctx->lin,
+                  ctx->batch_row_off_d, ctx->batch_work_d, ctx->batch_wg_off_d};
   for (void* p : bufs) if (p) (void)hipFree(p);
   if (ctx->theta_h) (void)hipHostFree(ctx->theta_h);
   if (ctx->S_h) (void)hipHostFree(ctx->S_h);
@@ -1011,6 +1031,7 @@ static int set_data(mimo_ctx* ctx, int64_t N, int Dz) {
   if (Dz < 1 || Dz > kMaxD)
     return fail(ctx, MIMO_E_UNSUPPORTED, "Dz = %d outside [1, %d]", Dz, kMaxD);
   ctx->N = N; ctx->D = Dz;
+  ctx->batched = false;
   ctx->resp_valid = ctx->logp_valid = ctx->lse_valid = ctx->labels_valid = false;
   ctx->weights_resident = false;
   return prepare_features(ctx, Dz);
@@ -1442,6 +1463,7 @@ int mimo_predict_flags(mimo_ctx* ctx, const double* c, const double* b, const do
   const size_t ncov = diag ? 2 * (size_t)dy : (size_t)dy * dy;        // doubles of the second output per row
   int rc = bind(ctx); if (rc) return rc;
   if (!ctx->Z) return fail(ctx, MIMO_E_NODATA, "mimo_predict: no data resident (call mimo_upload)");
+  if ((rc = single_only(ctx))) return rc;
   if (!c || !b || !W || !M || !Q || !Cc || !mu || !covar || K < 1 || (mode != 0 && mode != 1))
     return fail(ctx, MIMO_E_INVALID, "mimo_predict: bad arguments");
   const bool want_nlpd = nlpd != nullptr;
@@ -1812,6 +1834,7 @@ int mimo_plan(mimo_ctx* ctx, int K, int gibbs, int64_t* out8) {
   int rc = bind(ctx); if (rc) return rc;
   if (!out8) return fail(ctx, MIMO_E_INVALID, "mimo_plan: out is NULL");
   if (!ctx->Z) return fail(ctx, MIMO_E_NODATA, "no data uploaded or attached");
+  if ((rc = single_only(ctx))) return rc;
   if (K < 1 || K > 256) return fail(ctx, MIMO_E_UNSUPPORTED, "K = %d outside [1, 256]", K);
   KernelArgs a;
   fill_args(ctx, K, &a);
@@ -1850,6 +1873,146 @@ int mimo_plan_shape(int Dz, int K, int structure, int64_t N, int gibbs, int64_t*
   a.gibbs = gibbs ? 1 : 0;
   if (desc && desc_len > 0) desc[0] = 0;
   plan_route(&ctx, a, K, gibbs, out8, desc, desc && desc_len > 0 ? (size_t)desc_len : 0);
+  return MIMO_OK;
+  });
+}
+
+// ------------------------------------------------------------------------------------------
+// Batched softmax pass (mimo_batched.hip)
+// ------------------------------------------------------------------------------------------
+int mimo_upload_batched(mimo_ctx* ctx, const double* Z_host, const int64_t* row_off, int B, int Dz) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
+  if (B < 1 || B > 65535 || !row_off) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: B = %d outside [1, 65535] or row_off is NULL", B);
+  if (Dz < 1 || Dz > kBatchedMaxD)
+    return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_upload_batched: Dz = %d outside [1, %d] (batched pass)", Dz, kBatchedMaxD);
+  if (row_off[0] != 0) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: row_off[0] = %lld, must be 0", (long long)row_off[0]);
+  for (int b = 0; b < B; ++b)
+    if (row_off[b + 1] < row_off[b])
+      return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: row_off decreases at problem %d", b);
+  const int64_t N = row_off[B];
+  if (!Z_host && N > 0) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: Z is NULL");
+  // batched mode has no NaN-row semantics: every element must be finite
+  for (int64_t i = 0; i < N * Dz; ++i)
+    if (!std::isfinite(Z_host[i]))
+      return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: row %lld holds a NaN or an infinity", (long long)(i / Dz));
+  // work table: problem b's tiles in runs of batched_tiles_per_wg(N_b), a function of N_b alone
+  std::vector<BatchedWork> work;
+  std::vector<int32_t> wg_off((size_t)B + 1, 0);
+  for (int b = 0; b < B; ++b) {
+    const int64_t nb = row_off[b + 1] - row_off[b];
+    const int64_t tiles = (nb + kTile - 1) / kTile;
+    const int tpw = batched_tiles_per_wg(nb);
+    for (int64_t t = 0; t < tiles; t += tpw)
+      work.push_back(BatchedWork{b, (int32_t)t, (int32_t)std::min<int64_t>(tpw, tiles - t), 0});
+    if (work.size() > (size_t)INT32_MAX) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: too many rows");
+    wg_off[(size_t)b + 1] = (int32_t)work.size();
+  }
+  if ((rc = set_data(ctx, N, Dz))) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->Z_owned) { HIP_TRY(ctx, hipFree(ctx->Z_owned)); ctx->Z_owned = nullptr; }
+  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->Z_owned), (size_t)(N > 0 ? N : 1) * Dz * sizeof(double)));
+  if (N > 0) HIP_TRY(ctx, hipMemcpy(ctx->Z_owned, Z_host, (size_t)N * Dz * sizeof(double), hipMemcpyHostToDevice));
+  ctx->Z = ctx->Z_owned;
+  ctx->n_bad = 0; ctx->bad_counts_K = 0; ctx->data_sum_valid = false;
+  void* olds[] = {ctx->batch_row_off_d, ctx->batch_work_d, ctx->batch_wg_off_d};
+  for (void* o : olds) if (o) HIP_TRY(ctx, hipFree(o));
+  ctx->batch_row_off_d = nullptr; ctx->batch_work_d = nullptr; ctx->batch_wg_off_d = nullptr;
+  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->batch_row_off_d), ((size_t)B + 1) * sizeof(int64_t)));
+  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->batch_work_d), std::max<size_t>(work.size(), 1) * sizeof(BatchedWork)));
+  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->batch_wg_off_d), ((size_t)B + 1) * sizeof(int32_t)));
+  HIP_TRY(ctx, hipMemcpy(ctx->batch_row_off_d, row_off, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  if (!work.empty()) HIP_TRY(ctx, hipMemcpy(ctx->batch_work_d, work.data(), work.size() * sizeof(BatchedWork), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->batch_wg_off_d, wg_off.data(), ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  ctx->batch_rows.assign(row_off, row_off + B + 1);
+  ctx->batch_B = B;
+  ctx->batch_G = (int)work.size();
+  ctx->batched = true;
+  return MIMO_OK;
+  });
+}
+
+int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, int flags, double* S,
+                       double* scalars) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if (!ctx->batched) return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: the context holds no batch (call mimo_upload_batched)");
+  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
+  if (ctx->comm)
+    return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_estep_batched: a communicator is attached (mimo_comm_init); the batched pass "
+                "has no reduction over ranks");
+  if (flags & ~(MIMO_F_NO_STATS | MIMO_F_ENTROPY_SPLIT | MIMO_F_KEEP_LSE))
+    return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: flags 0x%x: only MIMO_F_NO_STATS, MIMO_F_ENTROPY_SPLIT, MIMO_F_KEEP_LSE", flags);
+  const bool no_stats = (flags & MIMO_F_NO_STATS) != 0;
+  if (!c || !b || !W || !scalars || (!no_stats && !S))
+    return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: c, b, W, scalars (and S without MIMO_F_NO_STATS) must be non-NULL");
+  if (K < 1) return fail(ctx, MIMO_E_INVALID, "K must be >= 1 (got %d)", K);
+  const int D = ctx->D, B = ctx->batch_B;
+  if (ctx->structure != MIMO_STRUCT_FULL)
+    return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_estep_batched: only the full structure (symmetric W) is covered");
+  if (!batched_covers(K, D))
+    return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_estep_batched: K = %d, Dz = %d outside the batched kernels (K <= %d, Dz <= %d, "
+                "ceil(K/16) * ceil(F/16) <= %d with F = (Dz+1)(Dz+2)/2)", K, D, kBatchedMaxK, kBatchedMaxD, kBatchedMaxPairs);
+  const int F = ctx->F, F16 = ctx->F16, K16 = (K + 15) / 16, NS = F16 / 4;
+  // stacked operand image [B][K16][NS][64]: problem p's slice is the single-problem image of its (c, b, W)
+  const size_t per = (size_t)K16 * NS * 64, count = per * B;
+  if ((rc = ensure_dev(ctx, &ctx->theta_d, &ctx->theta_cap, count))) return rc;
+  if ((rc = ensure_pinned(ctx, &ctx->theta_h, &ctx->theta_hcap, count))) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // the staging buffer may still be in flight
+  double* img = ctx->theta_h;
+  memset(img, 0, count * sizeof(double));
+  bool finite = true;
+  for (int p = 0; p < B; ++p) {
+    double* ip = img + per * p;
+    for (int k = 0; k < 16 * K16; ++k) {
+      const int rb = k / 16, i = k % 16;
+      auto put = [&](int f, double v) {
+        finite = finite && std::fabs(v) <= 1.7976931348623157e308;
+        ip[((size_t)rb * NS + f / 4) * 64 + (f % 4) * 16 + i] = v;
+      };
+      if (k >= K) { ip[((size_t)rb * NS + feat_index(D, D, D) / 4) * 64 + (feat_index(D, D, D) % 4) * 16 + i] = kPadLogDensity; continue; }
+      const double ck = c[(size_t)p * K + k];
+      const double* bk = b + ((size_t)p * K + k) * D;
+      const double* Wk = W + ((size_t)p * K + k) * D * D;
+      if (ck != ck || ck > 1.7976931348623157e308)
+        return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: c[%d][%d] is NaN or +inf", p, k);
+      put(feat_index(D, D, D), ck < kPadLogDensity ? kPadLogDensity : ck);   // c_k = -inf: a switched-off component
+      for (int a = 0; a < D; ++a) put(feat_index(D, a, D), bk[a]);
+      for (int a = 0; a < D; ++a) {
+        put(feat_index(D, a, a), -0.5 * Wk[a * D + a]);
+        for (int bb = a + 1; bb < D; ++bb) put(feat_index(D, a, bb), -0.5 * (Wk[a * D + bb] + Wk[bb * D + a]));
+      }
+    }
+    if (!finite) return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: b or W of problem %d holds a NaN or an infinity", p);
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+
+  const int G = ctx->batch_G;
+  const size_t pstride = (size_t)16 * K16 * F16 + 4;
+  if ((rc = ensure_dev(ctx, &ctx->partials, &ctx->partials_cap, pstride * (size_t)std::max(G, 1)))) return rc;
+  const bool keep_lse = (flags & MIMO_F_KEEP_LSE) != 0;
+  if (keep_lse && (rc = ensure_dev(ctx, &ctx->lse, &ctx->lse_cap, (size_t)(ctx->N > 0 ? ctx->N : 1)))) return rc;
+  ctx->lse_valid = keep_lse;
+  ctx->resp_valid = ctx->logp_valid = ctx->labels_valid = false;
+  BatchedArgs a;
+  a.Z = ctx->Z; a.row_off = ctx->batch_row_off_d; a.work = ctx->batch_work_d; a.theta = ctx->theta_d; a.feat = ctx->feat_d;
+  a.partials = ctx->partials; a.lse = keep_lse ? ctx->lse : nullptr;
+  a.D = D; a.K = K; a.K16 = K16; a.F16 = F16;
+  a.ZS = (D + 2) | 1;
+  a.do_stats = no_stats ? 0 : 1;
+  HIP_TRY(ctx, launch_batched(a, G, ctx->stream));
+  const size_t slen = (size_t)K * (1 + D + (size_t)D * D), out = (no_stats ? 0 : slen * B) + 3 * (size_t)B;
+  if ((rc = ensure_dev(ctx, &ctx->S_d, &ctx->S_cap, out))) return rc;
+  if ((rc = ensure_pinned(ctx, &ctx->S_h, &ctx->S_hcap, out))) return rc;
+  double* sc_d = ctx->S_d + (no_stats ? 0 : slen * B);
+  const int split = (flags & (MIMO_F_ENTROPY_SPLIT | MIMO_F_KEEP_LSE)) ? 1 : 0;
+  HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, D, F, F16, split,
+                                     no_stats ? nullptr : ctx->S_d, sc_d, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->S_h, ctx->S_d, out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (!no_stats) memcpy(S, ctx->S_h, slen * B * sizeof(double));
+  memcpy(scalars, ctx->S_h + (no_stats ? 0 : slen * B), 3 * (size_t)B * sizeof(double));
   return MIMO_OK;
   });
 }

@@ -1,0 +1,52 @@
+// Internal interface of the batched softmax pass (mimo_batched.hip): B independent problems that share Dz and K, each with
+// its own rows and its own (c, b, W), in one launch.  Not installed; the public surface is include/mimo_hip.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace mimo {
+
+constexpr int kBatchedMaxD = 16;        // single-pass feature tile (F = 153 features at Dz = 16)
+constexpr int kBatchedMaxK = 128;       // normalise phase: at most 16 components per lane (8 lanes per row)
+constexpr int kBatchedMaxPairs = 40;    // K16 * NCB statistics accumulators (16 x 16 blocks) of one workgroup: 10 per wave
+
+// LDS row strides (doubles) of the feature tile and the weight tile: compile-time constants of each instantiation
+__host__ __device__ constexpr int batched_rs(int ncb) { return 16 * ncb + 1; }
+__host__ __device__ constexpr int batched_ls(int ncb, int rbw) {
+  return 16 * ((rbw == 1 ? 4 : 8) < kBatchedMaxPairs / ncb ? (rbw == 1 ? 4 : 8) : kBatchedMaxPairs / ncb) + 2;
+}
+
+// One workgroup's share of the work: `ntiles` consecutive 32-row tiles of problem `prob`, starting at its local tile `tile0`.
+struct BatchedWork {
+  int32_t prob;
+  int32_t tile0;
+  int32_t ntiles;
+  int32_t pad;
+};
+
+struct BatchedArgs {
+  const double* Z;            // (N_total, D) row-major, the problems' rows concatenated
+  const int64_t* row_off;     // [B + 1]: problem b owns rows [row_off[b], row_off[b + 1])
+  const BatchedWork* work;    // [G]
+  const double* theta;        // [B][K16][F16 / 4][64]: the single-problem operand image, one per problem
+  const uint8_t* feat;        // [F16][2] index pairs (a, b) into z~ = [z, 1, 0]
+  double* partials;           // [G][K16 * 16 * F16 + 4]
+  double* lse;                // (N_total,) or null
+  int D, K, K16, F16;
+  int ZS;                     // LDS row stride (doubles) of the z~ tile
+  int do_stats;
+};
+
+// Tiles per workgroup for a problem of `nrows` rows: a function of the row count alone (the determinism rule: a problem's
+// result does not depend on what else is in the batch).
+int batched_tiles_per_wg(int64_t nrows);
+bool batched_covers(int K, int D);
+size_t batched_lds_bytes(const BatchedArgs& a);
+hipError_t launch_batched(const BatchedArgs& a, int grid, hipStream_t stream);
+// Per problem: the fixed-order sum of its workgroups' partial blocks [wg_off[b], wg_off[b + 1]), unpacked into
+// S[b] = K x (1 + Dz + Dz^2) (or nothing when S is null) and scalars[b] = {sum lse, sum r l, sum lse - sum r l}
+// (the last two NaN unless `split`).
+hipError_t launch_batched_reduce(const double* partials, const int32_t* wg_off, int B, const uint8_t* feat, int K, int D,
+                                 int F, int F16, int split, double* S, double* scalars, hipStream_t stream);
+
+}  // namespace mimo

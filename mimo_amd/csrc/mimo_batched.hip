@@ -1,0 +1,366 @@
+// Batched softmax pass (gfx950): B independent problems that share Dz and K, each with its own rows and its own (c, b, W),
+// in ONE launch.  The rows of all problems are concatenated into one (N_total, Dz) matrix; problem b owns the rows
+// [row_off[b], row_off[b + 1]).  A host-built work table gives every workgroup a run of 32-row tiles of ONE problem; how a
+// problem's tiles are split depends on its row count alone (batched_tiles_per_wg), so a problem's partial blocks — and,
+// through the fixed-order second stage, its results — are bit-identical whatever else is in the batch.
+//
+// Per tile, on the matrix instruction of the fused tile kernel (v_mfma_f64_16x16x4_f64):
+//   1. z~ tile of the problem's rows into LDS (rows past the problem's end are zero, with a zero in the constant slot:
+//      their features, weights, statistics and lse terms are all zero)
+//   2. feature tile Phi (32 x F16) from the feature table
+//   3. L = Theta_b Phi': wave w owns the component row blocks w, w + 4; Theta_b's MFMA A-operand slices come from the
+//      problem's slice of the stacked operand image (the single-problem image, one per problem)
+//   4. softmax over k (normalise_tile / normalise_tile_chunked of mimo_tile.h, generic mode: sum lse and sum r l per row)
+//   5. S += R Phi: the K16 x NCB 16 x 16 output blocks are dealt to the four waves in row-block-major runs (at most 10 per
+//      wave: the K16 NCB <= 40 coverage bound is this register budget)
+// and one partial block per workgroup at the end.  batched_reduce_kernel sums each problem's blocks in a fixed order and
+// unpacks them into the packed per-problem statistics and scalars.
+#include "mimo_batched.h"
+#include "mimo_tile.h"
+
+#include <math.h>
+
+namespace mimo {
+
+int batched_tiles_per_wg(int64_t nrows) {
+  const int64_t tiles = (nrows + kTile - 1) / kTile;
+  const int64_t t = (tiles + 127) / 128;      // at most 128 workgroups per problem: bounds the partial blocks of large problems
+  return (int)(t > 4 ? t : 4);
+}
+
+static int batched_ncb(int D) { return (feat_count(D) + 15) / 16; }
+
+bool batched_covers(int K, int D) {
+  if (D < 1 || D > kBatchedMaxD || K < 1 || K > kBatchedMaxK) return false;
+  return ((K + 15) / 16) * batched_ncb(D) <= kBatchedMaxPairs;
+}
+
+size_t batched_lds_bytes(const BatchedArgs& a) {
+  const int ncb = a.F16 / 16, rbw = a.K16 <= 4 ? 1 : 2;
+  return sizeof(double) * ((size_t)kTile * (a.ZS + batched_rs(ncb) + batched_ls(ncb, rbw)) + 16 + 64) + (size_t)a.F16 * 2;
+}
+
+// NCB: 16-wide feature column blocks; RBW: component row blocks per wave (1: K <= 64, 2: K <= 128)
+template <int NCB, int RBW>
+__global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
+  constexpr int T = kTile;
+  constexpr int NSI = 4 * NCB;                                       // contraction steps of the L product (4 features each)
+  constexpr int K16MAX = (RBW == 1 ? 4 : 8) < kBatchedMaxPairs / NCB ? (RBW == 1 ? 4 : 8) : kBatchedMaxPairs / NCB;
+  constexpr int SP = (K16MAX * NCB + 3) / 4;                         // statistics blocks per wave at most (<= 10)
+  // compile-time row strides: every LDS operand of the two products is a base register + an immediate offset
+  constexpr int RS = batched_rs(NCB), LS = batched_ls(NCB, RBW);
+
+  extern __shared__ __align__(16) unsigned char smem[];
+  double* Zs = reinterpret_cast<double*>(smem);   // [T][ZS]  z~ rows (z, 1, 0)
+  double* Ph = Zs + T * a.ZS;                     // [T][RS]  feature tile
+  double* Lt = Ph + T * RS;                       // [T][LS]  l -> r per (row, component)
+  double* red = Lt + T * LS;                      // [16]     scalar reduction scratch
+  double* etab = red + 16;                        // [64]     2^(j/64) for exp_nonpos
+  uint8_t* fe = reinterpret_cast<uint8_t*>(etab + 64);   // [F16][2]
+  int* labs = reinterpret_cast<int*>(red);        // (label scratch of the normalise helpers: unused by the softmax)
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j = lane & 15, q = lane >> 4;
+  const int D = a.D, K = a.K, K16 = a.K16, F16 = a.F16;
+  const int ZS = a.ZS;
+  const int Kpad = 16 * K16;
+
+  const BatchedWork wk = a.work[blockIdx.x];
+  const int prob = __builtin_amdgcn_readfirstlane(wk.prob);
+  const int tile0 = __builtin_amdgcn_readfirstlane(wk.tile0), ntl = __builtin_amdgcn_readfirstlane(wk.ntiles);
+  const int64_t rbeg = a.row_off[prob], Nb = a.row_off[prob + 1] - rbeg;
+  const double* Zb = a.Z + rbeg * D;
+  double* const out_lse = a.lse ? a.lse + rbeg : nullptr;
+  const gptr_t th = (gptr_t)(a.theta + (size_t)prob * K16 * NSI * 64);
+
+  for (int e = tid; e < F16 * 2; e += kWG) fe[e] = a.feat[e];
+  if (tid < 64) etab[tid] = exp2((double)tid * (1.0 / 64.0));
+
+  // the normalise helpers read the row weights / uniforms / labels of a KernelArgs: none here (softmax, unit weights)
+  KernelArgs ka;
+  ka.u = nullptr;
+  ka.labels = nullptr;
+  ka.seed = 0; ka.sweep = 0; ka.row0 = 0;
+
+  // Z tile staging: thread element e = tid + 256 i (T * D <= 512) of the tile; the next tile is read into registers
+  // while the current one is processed
+  int zoff[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int e = tid + kWG * i;
+    const int pt = e / D;
+    zoff[i] = e < T * D ? pt * ZS + (e - pt * D) : -1;
+  }
+  double zr[2];
+  auto load_z = [&](int t) {
+    const int64_t base = (int64_t)t * T * D, total = Nb * D;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int64_t g = base + tid + kWG * i;
+      zr[i] = (zoff[i] >= 0 && g < total) ? Zb[g] : 0.0;
+    }
+  };
+  auto store_z = [&](int t) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      if (zoff[i] >= 0) Zs[zoff[i]] = zr[i];
+    if (tid < T) {
+      Zs[tid * ZS + D] = ((int64_t)t * T + tid) < Nb ? 1.0 : 0.0;   // rows past the problem's end contribute nothing
+      Zs[tid * ZS + D + 1] = 0.0;                                   // padded features read this slot
+    }
+  };
+  load_z(tile0);
+  store_z(tile0);
+  load_z(tile0 + 1);
+
+  const int frow = tid & (T - 1), fgrp = tid >> 5;
+  wg_sync();   // feature and exp tables are in LDS
+  uint32_t w[NCB];
+#pragma unroll
+  for (int jj = 0; jj < NCB; ++jj) w[jj] = reinterpret_cast<const uint32_t*>(fe)[fgrp * NCB + jj];
+
+  // statistics blocks of this wave: pairs p = wave P + i (row block p / NCB, column block p % NCB), i < npw
+  const int npair = K16 * NCB, P = (npair + 3) / 4;
+  const int npw = __builtin_amdgcn_readfirstlane(min(max(npair - wave * P, 0), P));
+  // per block: the base of its A operands (row 8 q, component 16 rb + j) and B operands (row 8 q, feature 16 cb + j)
+  int lo[SP], po[SP];
+#pragma unroll
+  for (int i = 0; i < SP; ++i) {
+    const int p = i < npw ? wave * P + i : 0;
+    const int rb = p / NCB, cb = p - rb * NCB;
+    lo[i] = 8 * q * LS + 16 * rb + j;
+    po[i] = 8 * q * RS + 16 * cb + j;
+  }
+  d4 sacc[SP];
+#pragma unroll
+  for (int i = 0; i < SP; ++i) sacc[i] = d4{0.0, 0.0, 0.0, 0.0};
+
+  double sc_lse = 0.0, sc_rl = 0.0, sc_prod = 1.0;
+  PhiloxBatch pbatch;
+
+  for (int t = tile0; t < tile0 + ntl; ++t) {
+    const int64_t n0 = (int64_t)t * T;
+    wg_sync();   // z~ tile of this step is in LDS; the previous tile's readers are done
+
+    // ---- feature tile: thread (row frow, group fgrp) writes features [2 NCB fgrp, 2 NCB (fgrp + 1)) ----
+    {
+      const double* zrow = Zs + frow * ZS;
+      double* prow = Ph + frow * RS + fgrp * (2 * NCB);
+#pragma unroll
+      for (int jj = 0; jj < NCB; ++jj) {
+        uint32_t wj = w[jj];
+        asm volatile("" : "+v"(wj));
+        const double za0 = zrow[wj & 255u], zb0 = zrow[(wj >> 8) & 255u];
+        const double za1 = zrow[(wj >> 16) & 255u], zb1 = zrow[wj >> 24];
+        prow[2 * jj] = za0 * zb0;
+        prow[2 * jj + 1] = za1 * zb1;
+      }
+    }
+    wg_sync();
+
+    // ---- L tile = Theta_b Phi': row block rb = wave + 4 h, both 16-row column groups -------------------
+    // A lane (i = j, kk = q) = Theta[16 rb + j][4 s + q]; B lane (kk = q, col = j) = Phi[16 g + j][4 s + q];
+    // C/D: reg r of lane (q, j) = component 16 rb + q + 4 r, row 16 g + j
+#pragma unroll
+    for (int h = 0; h < RBW; ++h) {
+      const int rb = wave + 4 * h;
+      if (rb < K16) {
+        // Theta slices stream from L2 through an 8-deep register ring, B operands are read two steps ahead of their
+        // MFMAs; sched_barriers keep hipcc from hoisting every read of the unrolled loop (register pressure)
+        constexpr int PD = NSI < 8 ? NSI : 8;
+        gptr_t thb = th + (size_t)rb * NSI * 64;
+        asm volatile("" : "+s"(thb));   // opaque per tile: slice addresses = scalar base + immediates, not hoisted VGPR pairs
+        const gptr_t thr = thb + lane;
+        double tr[PD], bq0[3], bq1[3];
+#pragma unroll
+        for (int e = 0; e < PD; ++e) tr[e] = thr[e * 64];
+        const double* p0 = Ph + j * RS + q;
+        const double* p1 = Ph + (16 + j) * RS + q;
+        bq0[0] = p0[0]; bq1[0] = p1[0];
+        if (NSI > 1) { bq0[1] = p0[4]; bq1[1] = p1[4]; }
+        d4 acc0 = d4{0.0, 0.0, 0.0, 0.0}, acc1 = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < NSI; ++s) {
+          if (s + 2 < NSI) { bq0[(s + 2) % 3] = p0[4 * (s + 2)]; bq1[(s + 2) % 3] = p1[4 * (s + 2)]; }
+          __builtin_amdgcn_sched_barrier(0);
+          const double av = tr[s % PD];
+          if (s + PD < NSI) tr[s % PD] = thr[(s + PD) * 64];
+          acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bq0[s % 3], acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bq1[s % 3], acc1, 0, 0, 0);
+        }
+        double* lw0 = Lt + j * LS + 16 * rb + q;
+        double* lw1 = lw0 + 16 * LS;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          lw0[4 * r] = acc0[r];
+          lw1[4 * r] = acc1[r];
+        }
+      }
+    }
+    wg_sync();
+
+    // ---- softmax over k (8 lanes per row); rows past the problem's end get zero weights and no lse -------------
+    if constexpr (RBW == 1)
+      normalise_tile<1, kGeneric>(ka, Lt, LS, etab, K, K16, Nb, n0, wave, lane, false, nullptr, nullptr, out_lse, sc_lse,
+                                  sc_rl, sc_prod, labs, pbatch, 0);
+    else
+      normalise_tile_chunked<RBW, kGeneric>(ka, Lt, LS, etab, K, K16, Nb, n0, wave, lane, false, nullptr, nullptr, out_lse,
+                                            sc_lse, sc_rl, sc_prod, labs, pbatch, 0);
+    wg_sync();
+
+    // ---- S += R Phi: step s contracts rows {s, s + 8, s + 16, s + 24}; A lane (i = j, kk = q) = R[8 q + s][16 rb + j],
+    // B lane (kk = q, col = j) = Phi[8 q + s][16 cb + j] ----------------------------------------------------------
+    if (a.do_stats) {
+      // operands of step s + 1 are read before the MFMAs of step s are issued
+      // opaque offsets per tile (not pointers: those would lose the LDS address space): every read below is
+      // one of these registers + an immediate, instead of 16 SP loop-invariant addresses pinned in (and spilled from) VGPRs
+      int lot[SP], pot[SP];
+#pragma unroll
+      for (int i = 0; i < SP; ++i) {
+        lot[i] = lo[i];
+        pot[i] = po[i];
+        asm volatile("" : "+v"(lot[i]), "+v"(pot[i]));
+      }
+      double avq[2][SP], bvq[2][SP];
+      auto fetch = [&](int s, int slot) {
+#pragma unroll
+        for (int i = 0; i < SP; ++i) {
+          if (i < npw) {
+            avq[slot][i] = Lt[lot[i] + s * LS];
+            bvq[slot][i] = Ph[pot[i] + s * RS];
+          }
+        }
+      };
+      fetch(0, 0);
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        if (s + 1 < 8) fetch(s + 1, (s + 1) & 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < SP; ++i)
+          if (i < npw) sacc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(avq[s & 1][i], bvq[s & 1][i], sacc[i], 0, 0, 0);
+      }
+    }
+
+    // ---- stage the next tile's z~ rows (Zs was last read before the barrier after the feature build) ----------
+    if (t + 1 < tile0 + ntl) {
+      store_z(t + 1);
+      load_z(t + 2);
+    }
+  }
+
+  // ---- partial block of this workgroup ---------------------------------------------------------------------
+  const size_t pstride = (size_t)Kpad * F16 + 4;
+  double* Pb = a.partials + (size_t)blockIdx.x * pstride;
+  if (a.do_stats) {
+#pragma unroll
+    for (int i = 0; i < SP; ++i) {
+      if (i < npw) {
+        const int p = wave * P + i;
+        const int rb = p / NCB, cb = p - rb * NCB;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Pb[(size_t)(16 * rb + q + 4 * r) * F16 + 16 * cb + j] = sacc[i][r];
+      }
+    }
+  }
+  sc_lse = wave_sum(sc_lse);
+  sc_rl = wave_sum(sc_rl);
+  wg_sync();
+  if (lane == 0) { red[2 * wave] = sc_lse; red[2 * wave + 1] = sc_rl; }
+  wg_sync();
+  if (tid == 0) {
+    double* Ps = Pb + (size_t)Kpad * F16;
+    Ps[0] = (red[0] + red[2]) + (red[4] + red[6]);
+    Ps[1] = (red[1] + red[3]) + (red[5] + red[7]);
+    Ps[2] = 0.0;
+    Ps[3] = 0.0;
+  }
+}
+
+// One thread per (component, feature) entry of a problem (blockIdx.y), plus one for the two scalar sums: the problem's
+// partial blocks in ascending order, four interleaved chains combined in a fixed order.
+__global__ __launch_bounds__(256) void batched_reduce_kernel(const double* __restrict__ partials, const int32_t* __restrict__ wg_off,
+                                                              const uint8_t* __restrict__ feat, int K, int D, int F, int F16, int split,
+                                                              double* __restrict__ S, double* __restrict__ scalars) {
+  const int b = blockIdx.y;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int Kpad = (K + 15) / 16 * 16;
+  const int64_t pstride = (int64_t)Kpad * F16 + 4, nsx = (int64_t)K * F;
+  const int g0 = wg_off[b], g1 = wg_off[b + 1];
+  auto sum = [&](int64_t off) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    int g = g0;
+    for (; g + 3 < g1; g += 4) {
+      s0 += partials[(int64_t)g * pstride + off];
+      s1 += partials[(int64_t)(g + 1) * pstride + off];
+      s2 += partials[(int64_t)(g + 2) * pstride + off];
+      s3 += partials[(int64_t)(g + 3) * pstride + off];
+    }
+    for (; g < g1; ++g) s0 += partials[(int64_t)g * pstride + off];
+    return (s0 + s1) + (s2 + s3);
+  };
+  if (S && e < nsx) {
+    const int k = (int)(e / F), f = (int)(e - (int64_t)k * F);
+    const int aa = feat[2 * f], bb = feat[2 * f + 1];
+    const double v = sum((int64_t)k * F16 + f);
+    double* Sk = S + ((int64_t)b * K + k) * (1 + D + D * D);
+    if (aa == D) Sk[0] = v;                // (D, D): n_k
+    else if (bb == D) Sk[1 + aa] = v;      // (a, D): sum r z_a
+    else { Sk[1 + D + aa * D + bb] = v; Sk[1 + D + bb * D + aa] = v; }
+  }
+  if (e == nsx) {
+    const double slse = sum((int64_t)Kpad * F16), srl = sum((int64_t)Kpad * F16 + 1);
+    // (integer selects: built with -fno-honor-nans, see unpack_stats)
+    const long long nan_bits = 0x7ff8000000000000LL;
+    scalars[3 * b] = slse;
+    scalars[3 * b + 1] = __longlong_as_double(split ? __double_as_longlong(srl) : nan_bits);
+    scalars[3 * b + 2] = __longlong_as_double(split ? __double_as_longlong(slse - srl) : nan_bits);
+  }
+}
+
+typedef void (*batched_fn)(const BatchedArgs);
+
+template <int RBW>
+static batched_fn pick_batched(int ncb) {
+  switch (ncb) {
+    case 1: return batched_kernel<1, RBW>;
+    case 2: return batched_kernel<2, RBW>;
+    case 3: return batched_kernel<3, RBW>;
+    case 4: return batched_kernel<4, RBW>;
+    case 5: return batched_kernel<5, RBW>;
+    case 6: return batched_kernel<6, RBW>;
+    case 7: return batched_kernel<7, RBW>;
+    case 8: return batched_kernel<8, RBW>;
+    default: break;
+  }
+  if constexpr (RBW == 1) {
+    if (ncb == 9) return batched_kernel<9, 1>;
+    if (ncb == 10) return batched_kernel<10, 1>;
+  }
+  return nullptr;
+}
+
+hipError_t launch_batched(const BatchedArgs& a, int grid, hipStream_t stream) {
+  if (!batched_covers(a.K, a.D)) return hipErrorInvalidValue;
+  const int ncb = a.F16 / 16;
+  batched_fn fn = a.K16 <= 4 ? pick_batched<1>(ncb) : pick_batched<2>(ncb);
+  if (!fn) return hipErrorInvalidValue;
+  if (grid <= 0) return hipSuccess;
+  const size_t lds = batched_lds_bytes(a);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kWG), lds, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_batched_reduce(const double* partials, const int32_t* wg_off, int B, const uint8_t* feat, int K, int D,
+                                 int F, int F16, int split, double* S, double* scalars, hipStream_t stream) {
+  if (B <= 0) return hipSuccess;
+  const int64_t n = (int64_t)K * F + 1;
+  hipLaunchKernelGGL(batched_reduce_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, stream, partials, wg_off,
+                     feat, K, D, F, F16, split, S, scalars);
+  return hipGetLastError();
+}
+
+}  // namespace mimo

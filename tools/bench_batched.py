@@ -1,0 +1,183 @@
+"""One batched softmax pass (BatchedHipEngine.estep) against the B solo passes it replaces (one HipEngine per problem, its
+data resident), on the same inputs, after warm-up; wall time per pass (each call returns synchronised host results) and the
+largest relative difference of the outputs.  Writes <out>/bench_batched.json.
+
+    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3]
+
+Also times one iteration of meanfield_coordinate_descent_batched against B solo meanfield_iteration calls at shape 1
+(24 ILR models, K = 100, dx = dy = 1), split into host time and pass time.
+
+Shapes: 1. B = 24, N_b = 1600, Dz = 2, K = 100 (the reference's parallel ILR example); 2. B = 64, N_b = 1e4, Dz = 2, K = 4
+(restarts of the toy GMM); 3. B = 8, N_b = 2.5e5, Dz = 12, K = 64 (C4 per model)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from mimo_amd.batched import BatchedHipEngine  # noqa: E402
+from mimo_amd.engine import HipEngine  # noqa: E402
+
+SHAPES = {1: (24, 1600, 2, 100), 2: (64, 10000, 2, 4), 3: (8, 250000, 12, 64)}
+
+
+def inputs(B, N, D, K, seed=0):
+    rng = np.random.default_rng(seed)
+    Zs = [rng.standard_normal((N, D)) * 1.5 + rng.standard_normal(D) for _ in range(B)]
+    A = rng.standard_normal((B, K, D, D))
+    W = A @ A.transpose(0, 1, 3, 2) / D + 0.3 * np.eye(D)
+    return Zs, rng.standard_normal((B, K)), rng.standard_normal((B, K, D)), W
+
+
+def timed(fn, reps):
+    fn()
+    fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append(time.perf_counter() - t0)
+    return float(np.median(t)) * 1e3
+
+
+def run_shape(sid, reps):
+    B, N, D, K = SHAPES[sid]
+    Zs, c, b, W = inputs(B, N, D, K, seed=sid)
+    beng = BatchedHipEngine(0)
+    beng.upload(Zs)
+    solos = []
+    for Z in Zs:
+        e = HipEngine(0)
+        e.upload(Z)
+        solos.append(e)
+    out = {}
+
+    def batched():
+        out["b"] = beng.estep(c, b, W)
+
+    def solo():
+        out["s"] = [e.estep(c[i], b[i], W[i]) for i, e in enumerate(solos)]
+
+    tb = timed(batched, reps)
+    ts = timed(solo, reps)
+    Sb, scb = out["b"]
+    err = 0.
+    for i, (S1, sc1) in enumerate(out["s"]):
+        for x, y in ((Sb[i].n, S1.n), (Sb[i].sx, S1.sx), (Sb[i].sxx, S1.sxx), (scb[i, :1], sc1[:1])):
+            err = max(err, float(np.abs(x - y).max() / max(np.abs(y).max(), 1.)))
+    # the solo passes' kernel time (the engine's event profiler)
+    solos[0].profile(True)
+    solos[0].profile_read(reset=True)
+    for _ in range(reps):
+        solos[0].estep(c[0], b[0], W[0])
+    prof = solos[0].profile_read(reset=True)
+    solos[0].profile(False)
+    for e in solos:
+        e.close()
+    beng.close()
+    return {"shape": sid, "B": B, "N_b": N, "Dz": D, "K": K, "batched_ms": tb, "solo_sum_ms": ts, "speedup": ts / tb,
+            "max_rel_diff": err, "solo_profile": prof, "reps": reps}
+
+
+class _TimedEngine:
+    """BatchedHipEngine that records the wall time of every pass (each call returns synchronised host results)."""
+
+    def __init__(self, eng):
+        self.eng, self.upload_s, self.pass_s = eng, 0., []
+
+    def upload(self, arrays):
+        t0 = time.perf_counter()
+        self.eng.upload(arrays)
+        self.upload_s += time.perf_counter() - t0
+
+    def estep(self, *a, **k):
+        t0 = time.perf_counter()
+        out = self.eng.estep(*a, **k)
+        self.pass_s.append(time.perf_counter() - t0)
+        return out
+
+
+def ilr_models(B, N, K, engines, seed=0):
+    from mimo_amd.distributions import (TruncatedStickBreaking, CategoricalWithStickBreaking, StackedNormalWisharts,
+                                        StackedGaussiansWithNormalWisharts, StackedMatrixNormalWisharts,
+                                        StackedLinearGaussiansWithMatrixNormalWisharts)
+    from mimo_amd.mixtures import BayesianMixtureOfLinearGaussians
+    rng = np.random.default_rng(seed)
+    models, data = [], []
+    for engine in engines:
+        x = rng.uniform(-10., 10., size=(N, 1))
+        y = np.sinc(x / np.pi) + 0.1 * rng.standard_normal((N, 1))
+        gating = CategoricalWithStickBreaking(K, TruncatedStickBreaking(K, np.ones(K), 10. * np.ones(K)))
+        bp = StackedNormalWisharts(K, 1, np.zeros((K, 1)), 1e-2 * np.ones(K), np.stack(K * [np.eye(1)]), 2. * np.ones(K) + 1e-8)
+        mp = StackedMatrixNormalWisharts(K, 2, 1, np.zeros((K, 1, 2)), np.stack(K * [1e-2 * np.eye(2)]), np.stack(K * [np.eye(1)]),
+                                         2. * np.ones(K) + 1e-8)
+        m = BayesianMixtureOfLinearGaussians(K, 1, 1, gating, StackedGaussiansWithNormalWisharts(K, 1, bp, engine=engine),
+                                             StackedLinearGaussiansWithMatrixNormalWisharts(K, 2, 1, mp, engine=engine),
+                                             scale=True, engine=engine)
+        m.init_transform(x, y)
+        models.append(m)
+        data.append((x, y))
+    return models, data
+
+
+def driver_iteration(reps):
+    """One batched driver iteration against B solo meanfield_iteration calls, shape 1."""
+    from mimo_amd.mixtures.batched import meanfield_coordinate_descent_batched
+    B, N, _, K = SHAPES[1]
+    engines = [HipEngine(0) for _ in range(B)]          # solo: every model on its own engine, its data resident
+    models, data = ilr_models(B, N, K, engines)
+    teng = _TimedEngine(BatchedHipEngine(0))
+    seeds = list(range(B))
+    meanfield_coordinate_descent_batched(models, data, init_rng='philox', seeds=seeds, maxiter=3, tol=0., engine=teng)
+    teng.upload_s, teng.pass_s = 0., []
+    t0 = time.perf_counter()
+    meanfield_coordinate_descent_batched(models, data, randomize=False, maxiter=reps, tol=0., sample_likelihood=True, engine=teng)
+    total = time.perf_counter() - t0 - teng.upload_s - teng.pass_s[0]      # (the start pass of randomize=False is not an iteration)
+    pass_ms = float(np.sum(teng.pass_s[1:])) / reps * 1e3
+    batched = {"iteration_ms": total / reps * 1e3, "pass_ms": pass_ms, "host_ms": total / reps * 1e3 - pass_ms}
+    # solo: the same models, one meanfield_iteration each on the model's own (single-problem) engine
+    states = []
+    for m, (x, y) in zip(models, data):
+        eng = m._bind(*m._scaled(x, y))
+        states.append((eng, eng.estep(*m.canonical_expected())[0]))
+    for e in engines:
+        e.profile(True)
+        e.profile_read(reset=True)
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        for i, m in enumerate(models):
+            x, y = data[i]
+            eng = m._bind(*m._scaled(x, y))
+            S, _ = m.meanfield_iteration(eng, states[i][1])
+            states[i] = (eng, S)
+    wall = (time.perf_counter() - t0) / reps * 1e3
+    kms = sum(e.profile_read(reset=True)[0] for e in engines)
+    for e in engines:
+        e.profile(False)
+    solo = {"iteration_ms": wall, "kernel_ms": kms / reps, "host_ms": wall - kms / reps}
+    return {"driver_shape": 1, "B": B, "batched": batched, "solo": solo, "reps": reps}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--shapes", default="1,2,3")
+    ap.add_argument("--no-driver", action="store_true", help="skip the driver-iteration timing")
+    args = ap.parse_args()
+    os.makedirs(args.out, exist_ok=True)
+    res = [run_shape(int(s), args.reps) for s in args.shapes.split(",")]
+    if not args.no_driver:
+        res.append(driver_iteration(min(args.reps, 10)))
+    for r in res:
+        print(json.dumps(r))
+    with open(os.path.join(args.out, "bench_batched.json"), "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — E-step datapoint-component evaluations per second (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|c1] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|c1] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no RANK / WORLD_SIZE in the environment launches the N ranks itself (fresh child
@@ -21,9 +21,12 @@ The JSON line also carries
   roofline     : the dominant kernel against the float64 matrix-core peak (HIP events around every launch
                  on the launch stream, averaged over the timed steps; algorithmic flops of SURVEY.md §8(d)),
                  or against the HBM roof for the small-shape kernel (config c1)
+and, with `--full` only (a plain run sets up, warms up, times the steps, dumps and prints; cpu_baseline is then null):
   cpu_baseline : the NumPy restatement of the reference algorithm (oracle/, verified equal to the
-                 reference on golden vectors) timed on this box's host cores on a bounded row sample
-  sustained    : the same step repeated for >= 3 s after the timed steps (median / min ms per step).
+                 reference on golden vectors) timed on the host's cores on a bounded row sample (~25 s)
+  sustained    : the same step repeated for --sustained-seconds (default 10 s) after the timed steps (median / min ms
+                 per step, shader clock under the load).
+`--no-cpu-baseline` / `--no-sustained` drop one of the two from a `--full` run.
 
 `--dump-outputs DIR` writes what the last timed step returned to its caller (the statistic block of the data pass and,
 for the mean-field configs, the ELBO) as DIR/<name>.npy in float64; the inputs depend on the arguments only, so two builds
@@ -275,14 +278,17 @@ def main(argv=None, engine_factory=None, launcher=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--rows", type=int, default=0, help="override rows per GPU (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sustained", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the sustained leg and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-sustained", action="store_true", help="with --full: skip the sustained leg")
     ap.add_argument("--no-sample", action="store_true",
                     help="drop the reference's per-iteration likelihood.params = posterior.rvs() (sample_likelihood=False)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--sustained-seconds", type=float, default=10.0,
-                    help="length of the sustained leg after the timed steps (>= 10 s: a 5-second utilisation sampler must see it)")
+                    help="with --full: length of the sustained leg after the timed steps (>= 10 s: a 5-second utilisation sampler "
+                         "must see it)")
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -392,7 +398,7 @@ def main(argv=None, engine_factory=None, launcher=None):
         elapsed = float(t.max().item())
 
     sustained = None
-    if not args.no_sustained and not dry and dist is None:
+    if args.full and not args.no_sustained and not dry and dist is None:
         # the same step for >= 10 s after the timed steps: a 20-launch burst says nothing about sustained FP64 clocks, and an
         # independent 5-second utilisation sampler has to see the load at least once
         ts, t_end, it = [], time.perf_counter() + max(args.sustained_seconds, 0.0), args.warmup + args.steps
@@ -480,7 +486,7 @@ def main(argv=None, engine_factory=None, launcher=None):
             out["sustained"] = sustained
         if args.dump_outputs:
             out["dumped_outputs"] = dump_outputs(args.dump_outputs, *last_outputs)
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             out["cpu_baseline"] = cpu_baseline(cfg, X[:600_000].cpu().numpy())
         else:
             out["cpu_baseline"] = None

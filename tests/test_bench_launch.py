@@ -85,3 +85,34 @@ def test_bench_dumps_the_last_step_outputs(config, tmp_path):
 def test_bench_rejects_zero_steps():
     p = _run(["--rows", "1000", "--steps", "0"], {"BENCH_DRY_RUN_DOUBLE": "oracle_engine:OracleEngine"})
     assert p.returncode != 0 and "--steps" in p.stderr
+
+
+def test_full_is_an_option_of_the_dry_run():
+    """--full is accepted; a plain run's line carries the headline fields and leaves the extras out."""
+    for extra in ([], ["--full"]):
+        p = _run(["--rows", "2000", "--steps", "2", "--warmup", "1", "--config", "c2"] + extra,
+                 {"BENCH_DRY_RUN_DOUBLE": "oracle_engine:OracleEngine"})
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])
+        assert d["metric"] == "E-step datapoint-component evals/sec" and d["unit"] == "evals/s" and d["dtype"] == "f64"
+        assert d["higher_is_better"] is True and d["ms_per_step"] > 0 and d["steps"] == 2 and d["warmup"] == 1
+        assert d["cpu_baseline"] is None and "sustained" not in d
+
+
+@pytest.mark.gpu
+def test_plain_run_leaves_the_extras_to_full():
+    """A plain run times its steps and prints; --full adds the sustained leg and the CPU baseline (on a small row count both
+    stay short: the baseline's sample is bounded by the rows)."""
+    base = ["--rows", "20000", "--steps", "2", "--warmup", "1", "--config", "c2"]
+    lines = []
+    for extra in ([], ["--full", "--sustained-seconds", "0"]):
+        p = _run(base + extra, {"REAL_BENCH": "1"})
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines.append(json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1]))
+    plain, full = lines
+    for d in lines:
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "evals/s" and d["dtype"] == "f64"
+        assert d["roofline"]["kernel_ms"] > 0
+    assert plain["cpu_baseline"] is None and "sustained" not in plain
+    assert full["sustained"]["steps"] >= 5 and full["sustained"]["ms_per_step_median"] > 0
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["unit"] == "evals/s"

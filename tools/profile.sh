@@ -18,9 +18,9 @@ rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 ARGS="--config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-sustained $*"
-# the kernel-trace pass runs bench.py with its DEFAULT step / warm-up counts (what the driver runs), so that the
-# average duration in kernel_stats.csv is the average bench.py itself reports (only the CPU baseline leg is skipped)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $REPO/bench.py --config $CFG --no-cpu-baseline $* > $OUT/trace_bench.json 2> $OUT/trace.log
+# the kernel-trace pass runs bench.py with its DEFAULT step / warm-up counts and --full, sustained leg included (only the
+# CPU baseline leg is skipped), so that kernel_stats.csv averages over the timed steps and the sustained leg
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $REPO/bench.py --config $CFG --full --no-cpu-baseline $* > $OUT/trace_bench.json 2> $OUT/trace.log
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $REPO/bench.py $ARGS > /dev/null 2> $OUT/pmc_fetch.log
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 $REPO/bench.py $ARGS > /dev/null 2> $OUT/pmc_write.log
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA --output-format csv -d $OUT/pmc_sq -- python3 $REPO/bench.py $ARGS > /dev/null 2> $OUT/pmc_sq.log

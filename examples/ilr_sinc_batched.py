@@ -1,7 +1,11 @@
 """24 mixtures of linear-Gaussian experts fitted at once (the flow of the reference's examples/ilr/evaluate_sinc_parallel.py,
 which runs the 24 fits with joblib.Parallel): a noisy sinc, 24 random 80 % train splits, one ILR model per split
 (stick-breaking gating over 100 experts, dx = dy = 1, affine experts, inputs and outputs standardised per model), all fitted
-by meanfield_coordinate_descent_batched — one batched softmax pass per iteration for all 24 models."""
+by meanfield_coordinate_descent_batched — one batched softmax pass per iteration for all 24 models.
+
+--gibbs-iters G > 0 runs the reference job's full flow: a Gibbs warm-up of G sweeps from random labels, each model on its
+own numpy stream seeded like its joblib worker (resample_batched, numpy_seeds = 0 .. fits - 1; one batched label pass per
+sweep), then mean-field VI from the sampled parameters (randomize=False)."""
 import argparse
 import os
 import sys
@@ -16,7 +20,7 @@ from mimo_amd.distributions import (TruncatedStickBreaking, CategoricalWithStick
                                     StackedLinearGaussiansWithMatrixNormalWisharts)
 from mimo_amd.engine import HipEngine
 from mimo_amd.mixtures import BayesianMixtureOfLinearGaussians
-from mimo_amd.mixtures.batched import meanfield_coordinate_descent_batched
+from mimo_amd.mixtures.batched import meanfield_coordinate_descent_batched, resample_batched
 
 
 def make_model(K, engine):
@@ -39,6 +43,7 @@ def main():
     ap.add_argument("--fits", type=int, default=24)
     ap.add_argument("--experts", type=int, default=100)
     ap.add_argument("--iters", type=int, default=250)
+    ap.add_argument("--gibbs-iters", type=int, default=0, help="Gibbs warm-up sweeps before VI (0: random VI start)")
     args = ap.parse_args()
     rng = np.random.default_rng(1337)
     x = rng.uniform(-10., 10., size=(args.rows, 1))
@@ -53,8 +58,14 @@ def main():
         models.append(m)
         data.append((x[idx], y[idx]))
     t0 = time.perf_counter()
-    vlbs = meanfield_coordinate_descent_batched(models, data, randomize=True, init_rng='philox', seeds=range(args.fits),
-                                                maxiter=args.iters, tol=1e-6)
+    if args.gibbs_iters > 0:
+        resample_batched(models, data, init_labels='random', maxiter=args.gibbs_iters, numpy_seeds=range(args.fits))
+        gibbs = time.perf_counter() - t0
+        print(f"Gibbs warm-up: {args.gibbs_iters} sweeps of {args.fits} models in {gibbs:.2f} s")
+        vlbs = meanfield_coordinate_descent_batched(models, data, randomize=False, maxiter=args.iters, tol=1e-6)
+    else:
+        vlbs = meanfield_coordinate_descent_batched(models, data, randomize=True, init_rng='philox', seeds=range(args.fits),
+                                                    maxiter=args.iters, tol=1e-6)
     wall = time.perf_counter() - t0
     final = np.array([v[-1] for v in vlbs])
     print(f"{args.fits} fits of {ntrain} rows, K = {args.experts}: best ELBO {final.max():.2f}, median {np.median(final):.2f}, "

@@ -306,6 +306,31 @@ int mimo_upload_batched(mimo_ctx* ctx, const double* Z_host, const int64_t* row_
 int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, int flags,
                        double* S, double* scalars);
 
+/* One Gibbs label pass over all B problems of a batched context: per problem b what mimo_gibbs_labels returns for its
+ * rows alone under its parameters (c + b K, b + b K Dz, W + b K Dz Dz) — the inverse-CDF draw and the statistics of
+ * the labels drawn.
+ * Replaces: per problem, resample_labels (mimo/mixtures/gmm.py:227-230, ilr.py:161-164) + the one_hot /
+ *   weighted_statistics of the next sweep, in the seeded Gibbs warm-up that B reference jobs run one after another
+ *   (the joblib.Parallel workers of examples/ilr/evaluate_sinc_parallel.py: ilr.resample(..., init_labels='random')).
+ * Uniforms: u = N_total uniforms, the problems' uniforms concatenated (problem b's numpy.random.random((1, N_b))), or
+ *   NULL for the in-kernel Philox stream: problem b keyed by seeds[b] with counter (local row, sweep) — the labels of
+ *   mimo_gibbs_labels(seed = seeds[b], sweep) on its rows alone.  u and seeds both NULL: MIMO_E_INVALID.
+ * flags: MIMO_F_NO_STATS only.  S (B, K(1+Dz+Dz²)) or NULL with MIMO_F_NO_STATS; labels_out N_total int32 or NULL (the
+ * labels stay on the device as well: mimo_get_labels returns the N_total concatenated labels, mimo_label_stats_batched
+ * with labels = NULL their statistics).  c[k] = -inf allowed (that component never draws a label), NaN / +inf in c, b,
+ * W is MIMO_E_INVALID.  Coverage, the batch, the communicator and the determinism rule: those of mimo_estep_batched. */
+int mimo_gibbs_labels_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K,
+                              const uint64_t* seeds, uint64_t sweep, const double* u, int flags,
+                              int32_t* labels_out, double* S);
+
+/* Statistics of hard labels of all B problems of a batched context (no one-hot table): S (B, K(1+Dz+Dz²)).
+ * Replaces: per problem, one_hot + weighted_statistics + Categorical.statistics (gmm.py:235-237, data.py:160-169,
+ *   categorical.py:35-37) of a chain's initial labels (init_labels = 'random' | 'prior' | 'posterior').
+ * labels: N_total int32 in [0, K) on the host, the problems' labels concatenated (MIMO_E_INVALID outside), or NULL for
+ * the labels the last mimo_gibbs_labels_batched left on the device (MIMO_E_STATE if there are none).  flags: 0.
+ * Coverage, the batch, the communicator and the determinism rule: those of mimo_estep_batched. */
+int mimo_label_stats_batched(mimo_ctx* ctx, const int32_t* labels, int K, int flags, double* S);
+
 /* ---- copy-outs of device-resident tables ----------------------------------------------- */
 int mimo_get_resp(mimo_ctx* ctx, double* resp_host /* K×N */);
 /* The columns `cols[0 .. ncols)` (row indices of the data) of the resident responsibility table: out (K, ncols) row-major.  What a

@@ -1,4 +1,5 @@
-"""BatchedHipEngine — one softmax pass over B independent problems (mimo_upload_batched / mimo_estep_batched).
+"""BatchedHipEngine — one softmax pass or one Gibbs label pass over B independent problems (mimo_upload_batched /
+mimo_estep_batched / mimo_gibbs_labels_batched / mimo_label_stats_batched).
 
 B problems share Dz and K; each has its own rows and its own (c, b, W).  Where the reference fits many models with
 joblib (examples/ilr/evaluate_sinc_parallel.py: one ILR fit per train split) or random restarts, every pass of every
@@ -86,6 +87,70 @@ class BatchedHipEngine:
         self._check(self._lib.mimo_estep_batched(self._ctx, _ptr(c), _ptr(b), _ptr(W), K, flags,
                                                  _ptr(S) if stats else None, _ptr(sc)))
         return ([SuffStats.from_packed(S[i], K, D) for i in range(self.B)] if stats else None), sc
+
+    def _split(self, a):
+        return [a[self.row_off[i]:self.row_off[i + 1]].copy() for i in range(self.B)]
+
+    def gibbs_labels(self, c, b, W, seeds=None, sweep=0, u=None, stats=True, return_labels=True):
+        """One label pass over all problems: per problem what HipEngine.gibbs_labels returns for its rows alone.
+        seeds: B Philox keys (problem i draws with seed seeds[i], counter (local row, sweep)), or None with u; u: B arrays
+        of uniforms, (N_b,) or (1, N_b) each.  Returns (list of B int32 arrays | None, list of B SuffStats | None)."""
+        c, b, W, K = self._params(c, b, W)
+        if u is not None:
+            u = list(u)
+            if len(u) != self.B:
+                raise ValueError(f"uniforms for {len(u)} problems, {self.B} uploaded")
+            u = [_f64(ui).reshape(-1) for ui in u]
+            for i, ui in enumerate(u):
+                if ui.shape[0] != self.row_off[i + 1] - self.row_off[i]:
+                    raise ValueError("u must hold one uniform per datum")
+            u = np.ascontiguousarray(np.concatenate(u)) if self.row_off[-1] > 0 else np.zeros(1)
+            sd = None
+        else:
+            if seeds is None:
+                raise ValueError("gibbs_labels needs the uniforms u or one Philox seed per problem")
+            sd = np.ascontiguousarray(np.asarray(seeds).reshape(-1).astype(np.uint64))
+            if sd.shape[0] != self.B:
+                raise ValueError(f"{sd.shape[0]} seeds for {self.B} problems")
+        D = self.D
+        S = np.empty((self.B, K, 1 + D + D * D)) if stats else None
+        labels = np.empty(max(int(self.row_off[-1]), 1), dtype=np.int32) if return_labels else None
+        self._check(self._lib.mimo_gibbs_labels_batched(
+            self._ctx, _ptr(c), _ptr(b), _ptr(W), K, _ptr(sd) if sd is not None else None, int(sweep),
+            _ptr(u) if u is not None else None, 0 if stats else _lib.F_NO_STATS,
+            _ptr(labels) if return_labels else None, _ptr(S) if stats else None))
+        return ((self._split(labels) if return_labels else None),
+                ([SuffStats.from_packed(S[i], K, D) for i in range(self.B)] if stats else None))
+
+    def label_stats(self, labels, K):
+        """Statistics of hard labels: a list of B int32 arrays (N_b,), or None for the labels of the last gibbs_labels.
+        Returns a list of B SuffStats."""
+        K = int(K)
+        if labels is None:
+            p = None
+        else:
+            labels = list(labels)
+            if len(labels) != self.B:
+                raise ValueError(f"labels for {len(labels)} problems, {self.B} uploaded")
+            labels = [np.asarray(z).reshape(-1) for z in labels]
+            for i, z in enumerate(labels):
+                if z.shape[0] != self.row_off[i + 1] - self.row_off[i]:
+                    raise ValueError("labels must hold one entry per datum")
+                if z.size and (z.min() < 0 or z.max() >= K):
+                    raise ValueError("labels out of range")  # mirrors the assert in one_hot (data.py:162)
+            labels = (np.ascontiguousarray(np.concatenate(labels), dtype=np.int32) if self.row_off[-1] > 0
+                      else np.zeros(1, dtype=np.int32))
+            p = _ptr(labels)
+        D = self.D
+        S = np.empty((self.B, K, 1 + D + D * D))
+        self._check(self._lib.mimo_label_stats_batched(self._ctx, p, K, 0, _ptr(S)))
+        return [SuffStats.from_packed(S[i], K, D) for i in range(self.B)]
+
+    def get_labels(self):
+        """The labels of the last gibbs_labels, resident on the device: a list of B int32 arrays (N_b,)."""
+        out = np.empty(max(int(self.row_off[-1]), 1), dtype=np.int32)
+        self._check(self._lib.mimo_get_labels(self._ctx, _ptr(out)))
+        return self._split(out)
 
     def get_lse(self):
         """Per-problem log-normalisers of the last pass with keep_lse: a list of B arrays (N_b,)."""

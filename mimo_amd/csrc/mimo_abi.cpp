@@ -1933,32 +1933,33 @@ int mimo_upload_batched(mimo_ctx* ctx, const double* Z_host, const int64_t* row_
   });
 }
 
-int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, int flags, double* S,
-                       double* scalars) {
-  return guarded(ctx, [&]() -> int {
-  int rc = bind(ctx); if (rc) return rc;
-  if (!ctx->batched) return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: the context holds no batch (call mimo_upload_batched)");
+// The checks every batched pass shares (a batch, no pending call, no communicator, the full structure, a covered shape)
+static int batched_ready(mimo_ctx* ctx, int K, const char* what) {
+  if (!ctx->batched) return fail(ctx, MIMO_E_INVALID, "%s: the context holds no batch (call mimo_upload_batched)", what);
   if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
   if (ctx->comm)
-    return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_estep_batched: a communicator is attached (mimo_comm_init); the batched pass "
-                "has no reduction over ranks");
-  if (flags & ~(MIMO_F_NO_STATS | MIMO_F_ENTROPY_SPLIT | MIMO_F_KEEP_LSE))
-    return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: flags 0x%x: only MIMO_F_NO_STATS, MIMO_F_ENTROPY_SPLIT, MIMO_F_KEEP_LSE", flags);
-  const bool no_stats = (flags & MIMO_F_NO_STATS) != 0;
-  if (!c || !b || !W || !scalars || (!no_stats && !S))
-    return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: c, b, W, scalars (and S without MIMO_F_NO_STATS) must be non-NULL");
+    return fail(ctx, MIMO_E_UNSUPPORTED, "%s: a communicator is attached (mimo_comm_init); the batched pass "
+                "has no reduction over ranks", what);
   if (K < 1) return fail(ctx, MIMO_E_INVALID, "K must be >= 1 (got %d)", K);
-  const int D = ctx->D, B = ctx->batch_B;
+  const int D = ctx->D;
   if (ctx->structure != MIMO_STRUCT_FULL)
-    return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_estep_batched: only the full structure (symmetric W) is covered");
+    return fail(ctx, MIMO_E_UNSUPPORTED, "%s: only the full structure (symmetric W) is covered", what);
   if (!batched_covers(K, D))
-    return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_estep_batched: K = %d, Dz = %d outside the batched kernels (K <= %d, Dz <= %d, "
-                "ceil(K/16) * ceil(F/16) <= %d with F = (Dz+1)(Dz+2)/2)", K, D, kBatchedMaxK, kBatchedMaxD, kBatchedMaxPairs);
-  const int F = ctx->F, F16 = ctx->F16, K16 = (K + 15) / 16, NS = F16 / 4;
-  // stacked operand image [B][K16][NS][64]: problem p's slice is the single-problem image of its (c, b, W)
+    return fail(ctx, MIMO_E_UNSUPPORTED, "%s: K = %d, Dz = %d outside the batched kernels (K <= %d, Dz <= %d, "
+                "ceil(K/16) * ceil(F/16) <= %d with F = (Dz+1)(Dz+2)/2)", what, K, D, kBatchedMaxK, kBatchedMaxD, kBatchedMaxPairs);
+  return MIMO_OK;
+}
+
+// Stacked operand image [B][K16][NS][64] of the B problems' (c, b, W) (problem p's slice is the single-problem image),
+// followed by `extra` uint64 words (copied in the same transfer); on the device at ctx->theta_d.
+static int batched_theta(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, const uint64_t* extra,
+                         size_t nextra, const char* what) {
+  const int D = ctx->D, B = ctx->batch_B;
+  const int F16 = ctx->F16, K16 = (K + 15) / 16, NS = F16 / 4;
   const size_t per = (size_t)K16 * NS * 64, count = per * B;
-  if ((rc = ensure_dev(ctx, &ctx->theta_d, &ctx->theta_cap, count))) return rc;
-  if ((rc = ensure_pinned(ctx, &ctx->theta_h, &ctx->theta_hcap, count))) return rc;
+  int rc;
+  if ((rc = ensure_dev(ctx, &ctx->theta_d, &ctx->theta_cap, count + nextra))) return rc;
+  if ((rc = ensure_pinned(ctx, &ctx->theta_h, &ctx->theta_hcap, count + nextra))) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // the staging buffer may still be in flight
   double* img = ctx->theta_h;
   memset(img, 0, count * sizeof(double));
@@ -1976,7 +1977,7 @@ int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const do
       const double* bk = b + ((size_t)p * K + k) * D;
       const double* Wk = W + ((size_t)p * K + k) * D * D;
       if (ck != ck || ck > 1.7976931348623157e308)
-        return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: c[%d][%d] is NaN or +inf", p, k);
+        return fail(ctx, MIMO_E_INVALID, "%s: c[%d][%d] is NaN or +inf", what, p, k);
       put(feat_index(D, D, D), ck < kPadLogDensity ? kPadLogDensity : ck);   // c_k = -inf: a switched-off component
       for (int a = 0; a < D; ++a) put(feat_index(D, a, D), bk[a]);
       for (int a = 0; a < D; ++a) {
@@ -1984,9 +1985,37 @@ int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const do
         for (int bb = a + 1; bb < D; ++bb) put(feat_index(D, a, bb), -0.5 * (Wk[a * D + bb] + Wk[bb * D + a]));
       }
     }
-    if (!finite) return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: b or W of problem %d holds a NaN or an infinity", p);
+    if (!finite) return fail(ctx, MIMO_E_INVALID, "%s: b or W of problem %d holds a NaN or an infinity", what, p);
   }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (nextra) memcpy(img + count, extra, nextra * sizeof(uint64_t));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, (count + nextra) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  return MIMO_OK;
+}
+
+static BatchedArgs batched_args(mimo_ctx* ctx, int K) {
+  BatchedArgs a;
+  a.Z = ctx->Z; a.row_off = ctx->batch_row_off_d; a.work = ctx->batch_work_d; a.theta = ctx->theta_d; a.feat = ctx->feat_d;
+  a.partials = ctx->partials; a.lse = nullptr;
+  a.D = ctx->D; a.K = K; a.K16 = (K + 15) / 16; a.F16 = ctx->F16;
+  a.ZS = (ctx->D + 2) | 1;
+  a.do_stats = 1;
+  a.u = nullptr; a.seeds = nullptr; a.labels = nullptr; a.sweep = 0;
+  return a;
+}
+
+int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, int flags, double* S,
+                       double* scalars) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, "mimo_estep_batched"))) return rc;
+  if (flags & ~(MIMO_F_NO_STATS | MIMO_F_ENTROPY_SPLIT | MIMO_F_KEEP_LSE))
+    return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: flags 0x%x: only MIMO_F_NO_STATS, MIMO_F_ENTROPY_SPLIT, MIMO_F_KEEP_LSE", flags);
+  const bool no_stats = (flags & MIMO_F_NO_STATS) != 0;
+  if (!c || !b || !W || !scalars || (!no_stats && !S))
+    return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: c, b, W, scalars (and S without MIMO_F_NO_STATS) must be non-NULL");
+  const int D = ctx->D, B = ctx->batch_B;
+  const int F = ctx->F, F16 = ctx->F16, K16 = (K + 15) / 16;
+  if ((rc = batched_theta(ctx, c, b, W, K, nullptr, 0, "mimo_estep_batched"))) return rc;
 
   const int G = ctx->batch_G;
   const size_t pstride = (size_t)16 * K16 * F16 + 4;
@@ -1995,11 +2024,8 @@ int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const do
   if (keep_lse && (rc = ensure_dev(ctx, &ctx->lse, &ctx->lse_cap, (size_t)(ctx->N > 0 ? ctx->N : 1)))) return rc;
   ctx->lse_valid = keep_lse;
   ctx->resp_valid = ctx->logp_valid = ctx->labels_valid = false;
-  BatchedArgs a;
-  a.Z = ctx->Z; a.row_off = ctx->batch_row_off_d; a.work = ctx->batch_work_d; a.theta = ctx->theta_d; a.feat = ctx->feat_d;
-  a.partials = ctx->partials; a.lse = keep_lse ? ctx->lse : nullptr;
-  a.D = D; a.K = K; a.K16 = K16; a.F16 = F16;
-  a.ZS = (D + 2) | 1;
+  BatchedArgs a = batched_args(ctx, K);
+  a.lse = keep_lse ? ctx->lse : nullptr;
   a.do_stats = no_stats ? 0 : 1;
   HIP_TRY(ctx, launch_batched(a, G, ctx->stream));
   const size_t slen = (size_t)K * (1 + D + (size_t)D * D), out = (no_stats ? 0 : slen * B) + 3 * (size_t)B;
@@ -2014,6 +2040,101 @@ int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const do
   if (!no_stats) memcpy(S, ctx->S_h, slen * B * sizeof(double));
   memcpy(scalars, ctx->S_h + (no_stats ? 0 : slen * B), 3 * (size_t)B * sizeof(double));
   return MIMO_OK;
+  });
+}
+
+// The label pass of the batched Gibbs sweep (launch_batched_labels) and its statistics: the partial blocks of the launch
+// just queued are reduced per problem into S (B x K(1+Dz+Dz^2)); the scalars the reduction also writes are not returned.
+static int batched_label_stats_out(mimo_ctx* ctx, int K, double* S) {
+  const int D = ctx->D, B = ctx->batch_B;
+  const size_t slen = (size_t)K * (1 + D + (size_t)D * D), out = slen * B + 3 * (size_t)B;
+  int rc;
+  if ((rc = ensure_dev(ctx, &ctx->S_d, &ctx->S_cap, out))) return rc;
+  if ((rc = ensure_pinned(ctx, &ctx->S_h, &ctx->S_hcap, out))) return rc;
+  HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, D, ctx->F, ctx->F16, 0,
+                                     ctx->S_d, ctx->S_d + slen * B, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->S_h, ctx->S_d, slen * B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(S, ctx->S_h, slen * B * sizeof(double));
+  return MIMO_OK;
+}
+
+int mimo_gibbs_labels_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K,
+                              const uint64_t* seeds, uint64_t sweep, const double* u, int flags, int32_t* labels_out,
+                              double* S) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, "mimo_gibbs_labels_batched"))) return rc;
+  if (flags & ~MIMO_F_NO_STATS)
+    return fail(ctx, MIMO_E_INVALID, "mimo_gibbs_labels_batched: flags 0x%x: only MIMO_F_NO_STATS", flags);
+  const bool no_stats = (flags & MIMO_F_NO_STATS) != 0;
+  if (!c || !b || !W || (!no_stats && !S))
+    return fail(ctx, MIMO_E_INVALID, "mimo_gibbs_labels_batched: c, b, W (and S without MIMO_F_NO_STATS) must be non-NULL");
+  if (!u && !seeds)
+    return fail(ctx, MIMO_E_INVALID, "mimo_gibbs_labels_batched: u and seeds are both NULL (give the uniforms or one Philox "
+                "seed per problem)");
+  const int B = ctx->batch_B, G = ctx->batch_G;
+  const int64_t N = ctx->N;
+  const size_t n1 = (size_t)(N > 0 ? N : 1);
+  // the seeds travel behind the operand image, in its transfer
+  if ((rc = batched_theta(ctx, c, b, W, K, u ? nullptr : seeds, u ? 0 : (size_t)B, "mimo_gibbs_labels_batched"))) return rc;
+  const size_t count = (size_t)((K + 15) / 16) * (ctx->F16 / 4) * 64 * B;
+  if ((rc = ensure_dev(ctx, &ctx->labels, &ctx->labels_cap, n1))) return rc;
+  if (u) {
+    if ((rc = ensure_dev(ctx, &ctx->u_d, &ctx->u_cap, n1))) return rc;
+    if (N > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->u_d, u, (size_t)N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // u is pageable host memory
+    ctx->weights_resident = false;
+  }
+  const size_t pstride = (size_t)16 * ((K + 15) / 16) * ctx->F16 + 4;
+  if ((rc = ensure_dev(ctx, &ctx->partials, &ctx->partials_cap, pstride * (size_t)std::max(G, 1)))) return rc;
+  ctx->resp_valid = ctx->logp_valid = ctx->lse_valid = false;
+  BatchedArgs a = batched_args(ctx, K);
+  a.do_stats = no_stats ? 0 : 1;
+  a.u = u ? ctx->u_d : nullptr;
+  a.seeds = u ? nullptr : reinterpret_cast<const uint64_t*>(ctx->theta_d + count);
+  a.labels = ctx->labels;
+  a.sweep = sweep;
+  HIP_TRY(ctx, launch_batched_labels(a, kBatchedDraw, G, ctx->stream));
+  ctx->labels_valid = true;
+  if (!no_stats && (rc = batched_label_stats_out(ctx, K, S))) return rc;
+  if (labels_out && N > 0) {
+    HIP_TRY(ctx, hipMemcpyAsync(labels_out, ctx->labels, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return MIMO_OK;
+  });
+}
+
+int mimo_label_stats_batched(mimo_ctx* ctx, const int32_t* labels, int K, int flags, double* S) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, "mimo_label_stats_batched"))) return rc;
+  if (flags != 0) return fail(ctx, MIMO_E_INVALID, "mimo_label_stats_batched: flags 0x%x: none are defined", flags);
+  if (!S) return fail(ctx, MIMO_E_INVALID, "mimo_label_stats_batched: S is NULL");
+  const int64_t N = ctx->N;
+  const int G = ctx->batch_G;
+  const int32_t* lab = ctx->labels;
+  if (!labels) {
+    if (!ctx->labels_valid || !ctx->labels)
+      return fail(ctx, MIMO_E_STATE, "mimo_label_stats_batched: labels is NULL and no batched draw is resident");
+  } else {
+    for (int64_t n = 0; n < N; ++n)
+      if (labels[n] < 0 || labels[n] >= K)
+        return fail(ctx, MIMO_E_INVALID, "mimo_label_stats_batched: label %d of row %lld outside [0, %d)", labels[n],
+                    (long long)n, K);
+    const size_t n1 = (size_t)(N > 0 ? N : 1);
+    if ((rc = ensure_dev(ctx, &ctx->lin, &ctx->lin_cap, n1))) return rc;
+    if (N > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->lin, labels, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // labels is pageable host memory
+    lab = ctx->lin;
+  }
+  const size_t pstride = (size_t)16 * ((K + 15) / 16) * ctx->F16 + 4;
+  if ((rc = ensure_dev(ctx, &ctx->partials, &ctx->partials_cap, pstride * (size_t)std::max(G, 1)))) return rc;
+  BatchedArgs a = batched_args(ctx, K);
+  a.labels = const_cast<int32_t*>(lab);
+  HIP_TRY(ctx, launch_batched_labels(a, kBatchedGiven, G, ctx->stream));
+  return batched_label_stats_out(ctx, K, S);
   });
 }
 

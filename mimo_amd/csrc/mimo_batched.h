@@ -1,4 +1,4 @@
-// Internal interface of the batched softmax pass (mimo_batched.hip): B independent problems that share Dz and K, each with
+// Internal interface of the batched softmax and Gibbs label passes (mimo_batched.hip): B independent problems that share Dz and K, each with
 // its own rows and its own (c, b, W), in one launch.  Not installed; the public surface is include/mimo_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,7 +35,16 @@ struct BatchedArgs {
   int D, K, K16, F16;
   int ZS;                     // LDS row stride (doubles) of the z~ tile
   int do_stats;
+  // label modes (launch_batched_labels) only; the softmax pass reads none of these
+  const double* u;            // (N_total,) uniforms of the draw, or null: Philox keyed by seeds[b], counter (local row, sweep)
+  const uint64_t* seeds;      // [B] (Philox draw)
+  int32_t* labels;            // (N_total,): the labels drawn (kBatchedDraw) or given (kBatchedGiven)
+  uint64_t sweep;
 };
+
+// Label modes of the batched kernel family: the inverse-CDF draw of a Gibbs sweep (with the statistics of the labels
+// drawn), or the statistics of labels given on the device (no L product, no draw).
+enum BatchedLabelMode : int { kBatchedSoftmax = 0, kBatchedDraw = 1, kBatchedGiven = 2 };
 
 // Tiles per workgroup for a problem of `nrows` rows: a function of the row count alone (the determinism rule: a problem's
 // result does not depend on what else is in the batch).
@@ -43,6 +52,9 @@ int batched_tiles_per_wg(int64_t nrows);
 bool batched_covers(int K, int D);
 size_t batched_lds_bytes(const BatchedArgs& a);
 hipError_t launch_batched(const BatchedArgs& a, int grid, hipStream_t stream);
+// The label modes (kBatchedDraw / kBatchedGiven) on the same work table; the partial blocks hold the statistics of the labels
+// (one-hot operand, exact counts) and zero scalars.
+hipError_t launch_batched_labels(const BatchedArgs& a, int mode, int grid, hipStream_t stream);
 // Per problem: the fixed-order sum of its workgroups' partial blocks [wg_off[b], wg_off[b + 1]), unpacked into
 // S[b] = K x (1 + Dz + Dz^2) (or nothing when S is null) and scalars[b] = {sum lse, sum r l, sum lse - sum r l}
 // (the last two NaN unless `split`).

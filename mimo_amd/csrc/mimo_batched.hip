@@ -15,6 +15,14 @@
 //      wave: the K16 NCB <= 40 coverage bound is this register budget)
 // and one partial block per workgroup at the end.  batched_reduce_kernel sums each problem's blocks in a fixed order and
 // unpacks them into the packed per-problem statistics and scalars.
+//
+// Label modes (LM, the batched Gibbs sweep), on the same work table and the same reduction:
+//   kBatchedDraw:  phases 1-3 as above; phase 4 is the inverse-CDF draw of the normalise helpers (gibbs = true) with the
+//                  problem's own uniforms (u + row_off[b]) or its own Philox key (seeds[b], counter (local row, sweep)), so a
+//                  problem's labels are those of a solo draw over its rows alone; phase 5 is S += one-hot(labels) Phi, its
+//                  A operand built from the LDS label array (exact integer counts).
+//   kBatchedGiven: labels read from the device (the initial labels of a chain): no L product, no draw, phase 5 as above.
+// No scalars are returned in the label modes (their partial blocks carry zeros there).
 #include "mimo_batched.h"
 #include "mimo_tile.h"
 
@@ -40,8 +48,8 @@ size_t batched_lds_bytes(const BatchedArgs& a) {
   return sizeof(double) * ((size_t)kTile * (a.ZS + batched_rs(ncb) + batched_ls(ncb, rbw)) + 16 + 64) + (size_t)a.F16 * 2;
 }
 
-// NCB: 16-wide feature column blocks; RBW: component row blocks per wave (1: K <= 64, 2: K <= 128)
-template <int NCB, int RBW>
+// NCB: 16-wide feature column blocks; RBW: component row blocks per wave (1: K <= 64, 2: K <= 128); LM: BatchedLabelMode
+template <int NCB, int RBW, int LM = kBatchedSoftmax>
 __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
   constexpr int T = kTile;
   constexpr int NSI = 4 * NCB;                                       // contraction steps of the L product (4 features each)
@@ -57,7 +65,7 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
   double* red = Lt + T * LS;                      // [16]     scalar reduction scratch
   double* etab = red + 16;                        // [64]     2^(j/64) for exp_nonpos
   uint8_t* fe = reinterpret_cast<uint8_t*>(etab + 64);   // [F16][2]
-  int* labs = reinterpret_cast<int*>(red);        // (label scratch of the normalise helpers: unused by the softmax)
+  int* labs = reinterpret_cast<int*>(red);        // [T] labels of the tile (label modes; unused by the softmax)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -77,11 +85,18 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
   for (int e = tid; e < F16 * 2; e += kWG) fe[e] = a.feat[e];
   if (tid < 64) etab[tid] = exp2((double)tid * (1.0 / 64.0));
 
-  // the normalise helpers read the row weights / uniforms / labels of a KernelArgs: none here (softmax, unit weights)
+  // the normalise helpers read the row weights / uniforms / labels of a KernelArgs: none for the softmax (unit weights);
+  // the draw reads the problem's slices of the uniforms and labels, or its Philox key, with local rows (row0 = 0)
   KernelArgs ka;
   ka.u = nullptr;
   ka.labels = nullptr;
   ka.seed = 0; ka.sweep = 0; ka.row0 = 0;
+  if constexpr (LM == kBatchedDraw) {
+    ka.u = a.u ? a.u + rbeg : nullptr;
+    ka.labels = a.labels + rbeg;
+    ka.seed = a.u ? 0 : a.seeds[prob];
+    ka.sweep = a.sweep;
+  }
 
   // Z tile staging: thread element e = tid + 256 i (T * D <= 512) of the tile; the next tile is read into registers
   // while the current one is processed
@@ -124,13 +139,15 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
   const int npair = K16 * NCB, P = (npair + 3) / 4;
   const int npw = __builtin_amdgcn_readfirstlane(min(max(npair - wave * P, 0), P));
   // per block: the base of its A operands (row 8 q, component 16 rb + j) and B operands (row 8 q, feature 16 cb + j)
-  int lo[SP], po[SP];
+  // (label modes: lk = the component of the A operand's lane, 16 rb + j, that the one-hot entry tests for)
+  int lo[SP], po[SP], lk[SP];
 #pragma unroll
   for (int i = 0; i < SP; ++i) {
     const int p = i < npw ? wave * P + i : 0;
     const int rb = p / NCB, cb = p - rb * NCB;
     lo[i] = 8 * q * LS + 16 * rb + j;
     po[i] = 8 * q * RS + 16 * cb + j;
+    lk[i] = 16 * rb + j;
   }
   d4 sacc[SP];
 #pragma unroll
@@ -157,8 +174,12 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
         prow[2 * jj + 1] = za1 * zb1;
       }
     }
+    if constexpr (LM == kBatchedGiven) {   // rows past the problem's end get no label: their one-hot row is zero
+      if (tid < T) labs[tid] = (n0 + tid) < Nb ? a.labels[rbeg + n0 + tid] : -1;
+    }
     wg_sync();
 
+    if constexpr (LM != kBatchedGiven) {
     // ---- L tile = Theta_b Phi': row block rb = wave + 4 h, both 16-row column groups -------------------
     // A lane (i = j, kk = q) = Theta[16 rb + j][4 s + q]; B lane (kk = q, col = j) = Phi[16 g + j][4 s + q];
     // C/D: reg r of lane (q, j) = component 16 rb + q + 4 r, row 16 g + j
@@ -201,16 +222,21 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
     wg_sync();
 
     // ---- softmax over k (8 lanes per row); rows past the problem's end get zero weights and no lse -------------
+    // draw: the label of each row into labs (-1 past the problem's end) and the problem's label slice; the Philox batch
+    // walks this workgroup's consecutive tiles (stride T rows)
+    constexpr bool DRAW = LM == kBatchedDraw;
+    constexpr int NM = DRAW ? kFastGibbs : kGeneric;
     if constexpr (RBW == 1)
-      normalise_tile<1, kGeneric>(ka, Lt, LS, etab, K, K16, Nb, n0, wave, lane, false, nullptr, nullptr, out_lse, sc_lse,
-                                  sc_rl, sc_prod, labs, pbatch, 0);
+      normalise_tile<1, NM>(ka, Lt, LS, etab, K, K16, Nb, n0, wave, lane, DRAW, nullptr, nullptr, DRAW ? nullptr : out_lse,
+                            sc_lse, sc_rl, sc_prod, labs, pbatch, DRAW ? T : 0);
     else
-      normalise_tile_chunked<RBW, kGeneric>(ka, Lt, LS, etab, K, K16, Nb, n0, wave, lane, false, nullptr, nullptr, out_lse,
-                                            sc_lse, sc_rl, sc_prod, labs, pbatch, 0);
+      normalise_tile_chunked<RBW, NM>(ka, Lt, LS, etab, K, K16, Nb, n0, wave, lane, DRAW, nullptr, nullptr,
+                                      DRAW ? nullptr : out_lse, sc_lse, sc_rl, sc_prod, labs, pbatch, DRAW ? T : 0);
     wg_sync();
+    }
 
     // ---- S += R Phi: step s contracts rows {s, s + 8, s + 16, s + 24}; A lane (i = j, kk = q) = R[8 q + s][16 rb + j],
-    // B lane (kk = q, col = j) = Phi[8 q + s][16 cb + j] ----------------------------------------------------------
+    // B lane (kk = q, col = j) = Phi[8 q + s][16 cb + j]; label modes: R = one-hot(labels), R[n][k] = labs[n] == k ----
     if (a.do_stats) {
       // operands of step s + 1 are read before the MFMAs of step s are issued
       // opaque offsets per tile (not pointers: those would lose the LDS address space): every read below is
@@ -224,10 +250,13 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
       }
       double avq[2][SP], bvq[2][SP];
       auto fetch = [&](int s, int slot) {
+        int lab = -1;
+        if constexpr (LM != kBatchedSoftmax) lab = labs[8 * q + s];
 #pragma unroll
         for (int i = 0; i < SP; ++i) {
           if (i < npw) {
-            avq[slot][i] = Lt[lot[i] + s * LS];
+            if constexpr (LM == kBatchedSoftmax) avq[slot][i] = Lt[lot[i] + s * LS];
+            else avq[slot][i] = lab == lk[i] ? 1.0 : 0.0;
             bvq[slot][i] = Ph[pot[i] + s * RS];
           }
         }
@@ -263,6 +292,11 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
         for (int r = 0; r < 4; ++r) Pb[(size_t)(16 * rb + q + 4 * r) * F16 + 16 * cb + j] = sacc[i][r];
       }
     }
+  }
+  if constexpr (LM != kBatchedSoftmax) {
+    // no scalars in the label modes (and red, which holds the labels, is left alone)
+    if (tid < 4) Pb[(size_t)Kpad * F16 + tid] = 0.0;
+    return;
   }
   sc_lse = wave_sum(sc_lse);
   sc_rl = wave_sum(sc_rl);
@@ -321,30 +355,31 @@ __global__ __launch_bounds__(256) void batched_reduce_kernel(const double* __res
 
 typedef void (*batched_fn)(const BatchedArgs);
 
-template <int RBW>
+template <int RBW, int LM>
 static batched_fn pick_batched(int ncb) {
   switch (ncb) {
-    case 1: return batched_kernel<1, RBW>;
-    case 2: return batched_kernel<2, RBW>;
-    case 3: return batched_kernel<3, RBW>;
-    case 4: return batched_kernel<4, RBW>;
-    case 5: return batched_kernel<5, RBW>;
-    case 6: return batched_kernel<6, RBW>;
-    case 7: return batched_kernel<7, RBW>;
-    case 8: return batched_kernel<8, RBW>;
+    case 1: return batched_kernel<1, RBW, LM>;
+    case 2: return batched_kernel<2, RBW, LM>;
+    case 3: return batched_kernel<3, RBW, LM>;
+    case 4: return batched_kernel<4, RBW, LM>;
+    case 5: return batched_kernel<5, RBW, LM>;
+    case 6: return batched_kernel<6, RBW, LM>;
+    case 7: return batched_kernel<7, RBW, LM>;
+    case 8: return batched_kernel<8, RBW, LM>;
     default: break;
   }
   if constexpr (RBW == 1) {
-    if (ncb == 9) return batched_kernel<9, 1>;
-    if (ncb == 10) return batched_kernel<10, 1>;
+    if (ncb == 9) return batched_kernel<9, 1, LM>;
+    if (ncb == 10) return batched_kernel<10, 1, LM>;
   }
   return nullptr;
 }
 
-hipError_t launch_batched(const BatchedArgs& a, int grid, hipStream_t stream) {
+template <int LM>
+static hipError_t launch_mode(const BatchedArgs& a, int grid, hipStream_t stream) {
   if (!batched_covers(a.K, a.D)) return hipErrorInvalidValue;
   const int ncb = a.F16 / 16;
-  batched_fn fn = a.K16 <= 4 ? pick_batched<1>(ncb) : pick_batched<2>(ncb);
+  batched_fn fn = a.K16 <= 4 ? pick_batched<1, LM>(ncb) : pick_batched<2, LM>(ncb);
   if (!fn) return hipErrorInvalidValue;
   if (grid <= 0) return hipSuccess;
   const size_t lds = batched_lds_bytes(a);
@@ -352,6 +387,22 @@ hipError_t launch_batched(const BatchedArgs& a, int grid, hipStream_t stream) {
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kWG), lds, stream, a);
   return hipGetLastError();
+}
+
+hipError_t launch_batched(const BatchedArgs& a, int grid, hipStream_t stream) {
+  return launch_mode<kBatchedSoftmax>(a, grid, stream);
+}
+
+hipError_t launch_batched_labels(const BatchedArgs& a, int mode, int grid, hipStream_t stream) {
+  if (mode == kBatchedDraw) {
+    if (!a.labels || (!a.u && !a.seeds)) return hipErrorInvalidValue;
+    return launch_mode<kBatchedDraw>(a, grid, stream);
+  }
+  if (mode == kBatchedGiven) {
+    if (!a.labels) return hipErrorInvalidValue;
+    return launch_mode<kBatchedGiven>(a, grid, stream);
+  }
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_batched_reduce(const double* partials, const int32_t* wg_off, int B, const uint8_t* feat, int K, int D,

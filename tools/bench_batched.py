@@ -7,6 +7,10 @@ largest relative difference of the outputs.  Writes <out>/bench_batched.json.
 Also times one iteration of meanfield_coordinate_descent_batched against B solo meanfield_iteration calls at shape 1
 (24 ILR models, K = 100, dx = dy = 1), split into host time and pass time.
 
+Gibbs leg (unless --no-gibbs): per shape, one batched label pass (BatchedHipEngine.gibbs_labels, Philox, statistics on)
+against the B solo HipEngine.gibbs_labels calls; and one resample_batched sweep over the 24 ILR models of shape 1 (host
+uniforms) against 24 solo sweeps, with the largest difference of the sampled parameters after two seeded sweeps.
+
 Shapes: 1. B = 24, N_b = 1600, Dz = 2, K = 100 (the reference's parallel ILR example); 2. B = 64, N_b = 1e4, Dz = 2, K = 4
 (restarts of the toy GMM); 3. B = 8, N_b = 2.5e5, Dz = 12, K = 64 (C4 per model)."""
 import argparse
@@ -81,6 +85,104 @@ def run_shape(sid, reps):
     beng.close()
     return {"shape": sid, "B": B, "N_b": N, "Dz": D, "K": K, "batched_ms": tb, "solo_sum_ms": ts, "speedup": ts / tb,
             "max_rel_diff": err, "solo_profile": prof, "reps": reps}
+
+
+def run_gibbs_shape(sid, reps):
+    """One batched label pass (Philox, statistics on) against the B solo label passes."""
+    B, N, D, K = SHAPES[sid]
+    Zs, c, b, W = inputs(B, N, D, K, seed=sid)
+    seeds = [1000 + i for i in range(B)]
+    beng = BatchedHipEngine(0)
+    beng.upload(Zs)
+    solos = []
+    for Z in Zs:
+        e = HipEngine(0)
+        e.upload(Z)
+        solos.append(e)
+    out = {}
+
+    def batched():
+        out["b"] = beng.gibbs_labels(c, b, W, seeds=seeds, sweep=1)
+
+    def solo():
+        out["s"] = [e.gibbs_labels(c[i], b[i], W[i], seed=seeds[i], sweep=1) for i, e in enumerate(solos)]
+
+    tb = timed(batched, reps)
+    ts = timed(solo, reps)
+    Lb, Sb = out["b"]
+    err, mismatched = 0., 0
+    for i, (L1, S1) in enumerate(out["s"]):
+        mismatched += int(np.sum(Lb[i] != L1))
+        for x, y in ((Sb[i].n, S1.n), (Sb[i].sx, S1.sx), (Sb[i].sxx, S1.sxx)):
+            err = max(err, float(np.abs(x - y).max() / max(np.abs(y).max(), 1.)))
+    solos[0].profile(True)
+    solos[0].profile_read(reset=True)
+    for _ in range(reps):
+        solos[0].gibbs_labels(c[0], b[0], W[0], seed=seeds[0], sweep=1)
+    prof = solos[0].profile_read(reset=True)
+    solos[0].profile(False)
+    for e in solos:
+        e.close()
+    beng.close()
+    return {"gibbs_shape": sid, "B": B, "N_b": N, "Dz": D, "K": K, "batched_ms": tb, "solo_sum_ms": ts, "speedup": ts / tb,
+            "max_rel_diff": err, "labels_mismatched": mismatched, "solo_profile": prof, "reps": reps}
+
+
+class _SweepClock:
+    """BatchedHipEngine that stamps the end of every label pass: consecutive stamps of resample_batched bound one sweep."""
+
+    def __init__(self, eng):
+        self.eng, self.stamps = eng, []
+
+    def upload(self, arrays):
+        self.eng.upload(arrays)
+
+    def label_stats(self, *a, **k):
+        out = self.eng.label_stats(*a, **k)
+        self.stamps.append(time.perf_counter())
+        return out
+
+    def gibbs_labels(self, *a, **k):
+        out = self.eng.gibbs_labels(*a, **k)
+        self.stamps.append(time.perf_counter())
+        return out
+
+
+def gibbs_driver_sweep(reps):
+    """One resample_batched sweep over the 24 ILR models of shape 1 against 24 solo sweeps (host uniforms)."""
+    from mimo_amd.mixtures.batched import resample_batched, _resample_params
+    B, N, _, K = SHAPES[1]
+    engines = [HipEngine(0) for _ in range(B)]
+    # outputs: two seeded sweeps from the same state, batched (numpy_seeds) against solo (numpy.random.seed before each)
+    models, data = ilr_models(B, N, K, engines)
+    ref, _ = ilr_models(B, N, K, engines)
+    resample_batched(models, data, init_labels='random', maxiter=2, numpy_seeds=range(B))
+    for i, (m, (x, y)) in enumerate(zip(ref, data)):
+        np.random.seed(i)
+        m.resample(x, y, init_labels='random', maxiter=2, progress_bar=False)
+    err = max(float(np.abs(m.models.likelihood.As - r.models.likelihood.As).max() / max(np.abs(r.models.likelihood.As).max(), 1.))
+              for m, r in zip(models, ref))
+    mismatched = int(sum(np.sum(m.labels_ != r.labels_) for m, r in zip(models, ref)))
+    # batched: one sweep = the host halves of the 24 models + one label pass
+    clock = _SweepClock(BatchedHipEngine(0))
+    resample_batched(models, data, init_labels='prior', maxiter=reps + 2, engine=clock)
+    batched = float(np.median(np.diff(clock.stamps)[2:])) * 1e3
+    # solo: the same sweep, model by model, each on its own engine with its data resident
+    S = []
+    for m, (x, y) in zip(models, data):
+        eng = m._bind(*m._scaled(x, y))
+        S.append(eng.label_stats(m.gating.likelihood.rvs(eng.N), K))
+    t = []
+    for it in range(reps + 2):
+        t0 = time.perf_counter()
+        for i, (m, (x, y)) in enumerate(zip(models, data)):
+            eng = m._bind(*m._scaled(x, y))
+            _resample_params(m, S[i], None)
+            _, S[i] = m._draw_labels(eng, 'host', 0, it + 1, stats=True, return_labels=False)
+        t.append(time.perf_counter() - t0)
+    solo = float(np.median(t[2:])) * 1e3
+    return {"gibbs_driver_shape": 1, "B": B, "batched_sweep_ms": batched, "solo_sweeps_ms": solo, "speedup": solo / batched,
+            "max_rel_diff_As": err, "labels_mismatched": mismatched, "reps": reps}
 
 
 class _TimedEngine:
@@ -167,12 +269,17 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--shapes", default="1,2,3")
-    ap.add_argument("--no-driver", action="store_true", help="skip the driver-iteration timing")
+    ap.add_argument("--no-driver", action="store_true", help="skip the driver timings (VI iteration, Gibbs sweep)")
+    ap.add_argument("--no-gibbs", action="store_true", help="skip the Gibbs leg")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     res = [run_shape(int(s), args.reps) for s in args.shapes.split(",")]
     if not args.no_driver:
         res.append(driver_iteration(min(args.reps, 10)))
+    if not args.no_gibbs:
+        res += [run_gibbs_shape(int(s), args.reps) for s in args.shapes.split(",")]
+        if not args.no_driver:
+            res.append(gibbs_driver_sweep(args.reps))
     for r in res:
         print(json.dumps(r))
     with open(os.path.join(args.out, "bench_batched.json"), "w") as f:

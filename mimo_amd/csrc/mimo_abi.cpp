@@ -6,6 +6,7 @@
 #include "mimo_kernels.h"
 #include "mimo_extra.h"
 #include "mimo_batched.h"
+#include "mimo_route.h"
 
 #include <algorithm>
 #include <cmath>
@@ -97,11 +98,6 @@ struct mimo_ctx {
 
   void* comm = nullptr;         // RCCL communicator (mimo_comm_init): every pass then returns statistics summed over the ranks
   int comm_world = 1;
-  bool rowwave_vi_call = false; // set by mimo_estep for the call in progress: row-owner softmax + statistics kernel
-  bool rowwave_call = false;    // set by mimo_gibbs_labels for the call in progress: Theta was uploaded in the row-owner layout
-  bool mid_labels_call = false; // set for the call in progress: label pass on the mid kernel (Theta in the permuted grouped image)
-  bool mid_call = false;        // set for the call in progress: Theta is in the grouped image of the mid kernel (mimo_mid.hip)
-  int narrow_call = 0;          // set for the call in progress: Theta is in the narrow image (1: softmax + statistics pass, 2: label pass, 3: label pass + statistics fused)
 
   // pending asynchronous call (MIMO_F_ASYNC)
   bool pending_async = false;
@@ -269,8 +265,7 @@ static void fill_args(mimo_ctx* ctx, int K, KernelArgs* a) {
   memset(a, 0, sizeof *a);
   a->Z = ctx->Z; a->N = ctx->N; a->D = ctx->D; a->K = K; a->K16 = (K + 15) / 16;
   a->F16 = ctx->F16;
-  a->ZS = (ctx->D + 2) | 1;      // odd stride: conflict-free row reads
-  if (a->K16 > 12) a->ZS = ctx->D + 2;   // K > 192: every byte counts to keep two workgroups per CU (<= 80 KB each)
+  a->ZS = route_zs(K, ctx->D);
   a->RS = ctx->F16 + rs_pad();
   a->F16_total = ctx->F16;
   a->cb0 = 0;
@@ -287,12 +282,6 @@ static void fill_args(mimo_ctx* ctx, int K, KernelArgs* a) {
 
 // (c, b, W) -> Theta[k][f] -> MFMA A-operand image [K16][F16/4][64] on the device.
 //   f = (D,D): c_k ; (a,D): b_k[a] ; (a,a): -W_aa/2 ; (a,b), a<b: -(W_ab + W_ba)/2
-// Does this (data, K) run on the small-shape VALU kernel (mimo_small.hip)?  Dz <= 4, K <= 32, 16-byte aligned rows.
-static bool use_small(const mimo_ctx* ctx, int K) {
-  static const bool on = [] { const char* e = getenv("MIMO_SMALL"); return !e || atoi(e) != 0; }();   // tuning knob
-  return on && small_covers(ctx->D, K) && (reinterpret_cast<uintptr_t>(ctx->Z) % 16) == 0;
-}
-
 // small-shape kernel: Theta[G KL][F] row-major over the FULL feature map (feat_index order); a structure hint only
 // decides which entries of W are read (diagonal: W_aa; linear: none — the shared quadratic term stays with the caller)
 static int upload_theta_small(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, double* inline_out) {
@@ -338,20 +327,11 @@ static int upload_theta_small(mimo_ctx* ctx, const double* c, const double* b, c
   return MIMO_OK;
 }
 
-// Label pass on the row-owner kernels (mimo_rowwave.hip): Dz <= 9 (beyond the small-shape kernel's range), full structure, nothing but labels
-// (+ their statistics) requested.
-static bool use_rowwave(const mimo_ctx* ctx, int K, bool wants_tables) {
-  static const bool on = [] { const char* e = getenv("MIMO_ROWWAVE"); return !e || atoi(e) != 0; }();   // tuning knob
-  if (!on || wants_tables) return false;
-  const int ZS = (K + 15) / 16 > 12 ? ctx->D + 2 : ((ctx->D + 2) | 1);      // as fill_args
-  return rowwave_covers(K, ctx->F16, ZS) && label_stats_covers(K, ctx->D, ctx->structure);
-}
-
 // Theta image of the row-owner label kernel: [NS][KB][64]; component k sits in A-row (k / V) + 4 (k % 4) of row block
 // (k % V) / 4, V = 4 KB, so that an output lane holds a contiguous quarter of the components (gibbs_rowwave_kernel)
 static int upload_theta_rowwave(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K) {
   const int D = ctx->D;
-  const int ZSk = (K + 15) / 16 > 12 ? D + 2 : ((D + 2) | 1);      // as fill_args
+  const int ZSk = route_zs(K, D);
   const int KB = rowwave_kb_shape(K, ctx->F16, ZSk), V = 4 * KB;
   const int NS = rowwave_image_ns(K, ctx->F16, ZSk);                // (whole chunks where the label kernel streams Theta)
   const size_t count = (size_t)NS * KB * 64;
@@ -392,26 +372,6 @@ static int upload_theta_rowwave(mimo_ctx* ctx, const double* c, const double* b,
   for (int k = K; k < 16 * KB; ++k) put(k, fidx(ctx, D, D), kPadLogDensity);
   HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   return MIMO_OK;
-}
-
-// Passes of the narrow shapes (mimo_narrow.hip: F <= 16 features, 32 < K <= 128 on the 4x4x4 matrix instruction): plain
-// requests only — nothing but statistics + scalars (softmax pass) or labels + their statistics (label pass).
-// Returns the kernel mode + 1 (1: softmax + statistics, 2: label draw with the label-statistics kernel behind it, 3: label draw +
-// statistics in one pass — few components over many features, MIMO_NARROW_FUSED_LABELS=0: off) or 0.
-static int use_narrow(const mimo_ctx* ctx, int K, bool gibbs, bool plain, bool stats) {
-  static const bool fused_labels = [] { const char* e = getenv("MIMO_NARROW_FUSED_LABELS"); return !e || atoi(e) != 0; }();
-  if (!plain) return 0;                 // (the small-shape kernel keeps the generic requests of its range and the shapes below narrow_covers' K)
-  const int ZS = (K + 15) / 16 > 12 ? ctx->D + 2 : ((ctx->D + 2) | 1);      // as fill_args
-  if (!gibbs) return narrow_covers(K, ctx->F, ctx->D, ZS, 0) ? 1 : 0;     // (rows with NaN: their mask is the row-weight vector of the pass)
-  const bool two = narrow_covers(K, ctx->F, ctx->D, ZS, 1) && label_stats_covers(K, ctx->D, ctx->structure);
-  const bool one = fused_labels && ctx->n_bad == 0 && narrow_covers(K, ctx->F, ctx->D, ZS, 2);
-  if (one && !two) return 3;
-  // both exist: the fused pass wins while its second product is cheap next to a second pass over Z (profiles/r03_wide_sweep_fused_labels.txt,
-  // N = 2e6, us per sweep, label kernel + label statistics / fused: Dz=8 K=4 154 / 93, K=8 154 / 129, K=16 181 / 194; Dz=12 K=8 237 / 208,
-  // K=16 312 / 395; Dz=16 K=4 256 / 213, K=8 315 / 374, K=16 430 / 649)
-  const int V = narrow_v(K), D = ctx->D;
-  if (one && stats && (V == 1 || (D <= 6 && V <= 6) || (D <= 12 && V <= 3))) return 3;
-  return two ? 2 : 0;
 }
 
 // Theta image of the narrow kernels: [NSF][V][16]; slice s V + c, entry 4 kk + j = Theta[component j V + c][feature 4 s + kk]
@@ -469,70 +429,6 @@ static int upload_theta_narrow(mimo_ctx* ctx, const double* c, const double* b, 
   return MIMO_OK;
 }
 
-// Softmax + statistics pass of the mid shapes (mimo_mid.hip): plain requests (statistics + scalars, row weights / the NaN mask
-// allowed), full feature map, K <= 32 where neither the narrow kernels (few components) nor the single-pass tile kernels do
-// better — measured per shape (profiles/r04_mid_kernel_sweep.txt): from Dz = 17 everything the narrow kernels do not take;
-// MIMO_MID_MIN_D moves the lower end (tuning knob)
-static int g_mid_min_d = [] { const char* e = getenv("MIMO_MID_MIN_D"); return e ? atoi(e) : 0; }();       // (mimo_tune "mid_min_d"; 0: the measured rule)
-static int g_mid_narrow_k = [] { const char* e = getenv("MIMO_MID_NARROW_K"); return e ? atoi(e) : 0; }(); // (mimo_tune "mid_narrow_k")
-static int use_narrow(const mimo_ctx* ctx, int K, bool gibbs, bool plain, bool stats);
-static bool use_mid(const mimo_ctx* ctx, int K, bool plain) {
-  const int D = ctx->D;
-  if (!plain || !mid_covers(K, D, ctx->structure)) return false;
-  if (g_mid_min_d > 0 || g_mid_narrow_k > 0)       // forced by the caller (tests, sweeps)
-    return D >= (g_mid_min_d > 0 ? g_mid_min_d : 5) &&
-           (K >= (g_mid_narrow_k > 0 ? g_mid_narrow_k : 33) || !use_narrow(ctx, K, false, plain, true));
-  // measured (tools/mid_sweep.py, profiles/r04_mid_kernel_sweep.txt; fraction of the float64 rate, other route -> mid):
-  //   K = 17 .. 32: from Dz = 13 (Dz=13 K=32 0.55 -> 0.61, Dz=14 0.58 -> 0.66, Dz=16 0.61 -> 0.64, Dz=20 0.41 -> 0.69, Dz=32 0.48 -> 0.75;
-  //                 Dz=12 K=32 0.61 -> 0.57 and Dz=11 0.53 -> 0.50 stay on the tile / row-owner kernels)
-  //   K = 13 .. 16: from Dz = 12 against the narrow kernels (Dz=12 K=16 0.41 -> 0.49, Dz=14 0.44 -> 0.58, Dz=16 0.42 -> 0.57; Dz=11 0.45 -> 0.43)
-  //   K <= 12: the narrow kernels where they exist (Dz=16 K=12 0.44 = 0.44, Dz=15 0.42 -> 0.38, Dz=20 K=8 0.37 -> 0.30) up to Dz = 23
-  //            (Dz=24 K=8 0.31 -> 0.32, Dz=26 K=8 0.19 -> 0.34); beyond them the two-stage path was all there was (Dz=20 K=12 0.18 -> 0.47)
-  //   K = 33 .. 48: from Dz = 9 (Dz=9 K=48 0.48 -> 0.55, Dz=12 0.56 -> 0.60, Dz=16 0.57 -> 0.67, Dz=20 0.46 -> 0.71, Dz=26 0.52 -> 0.80; Dz=10, 11: level)
-  //   K = 49 .. 64: from Dz = 18 (Dz=18 K=64 0.64 -> 0.68, Dz=20 0.61 -> 0.76, Dz=21 0.66 -> 0.79, one wave per SIMD from Dz = 22: Dz=24 0.57 -> 0.63,
-  //                 Dz=28 0.63 -> 0.68; below, ten column blocks do not divide over eight waves and the tile kernels keep K = 64: Dz=16 0.78 against 0.57)
-  //   K = 65 .. 96: wherever the kernels exist from Dz = 6 (five / six row blocks instead of the eight the tile and two-stage kernels pay for:
-  //                 Dz=8 K=96 0.43 -> 0.56, Dz=9 K=72 0.35 -> 0.56, Dz=12 K=96 0.46 -> 0.62, Dz=14 K=80 0.35 -> 0.71, Dz=16 K=80 0.42 -> 0.60; with one
-  //                 wave per SIMD: Dz=16 K=96 0.47 -> 0.61, Dz=20 K=96 0.48 -> 0.66, Dz=23 K=96 0.51 -> 0.66, Dz=26 K=80 0.49 -> 0.66, Dz=28 K=48 0.47 -> 0.66)
-  //   K = 97 .. 128 (seven / eight row blocks, one wave per SIMD): K <= 112 from Dz = 8 (Dz=8 K=112 0.49 -> 0.58, Dz=12 0.53 -> 0.62, Dz=20 0.58 -> 0.65);
-  //                 K = 113 .. 128 at Dz = 10 .. 15 (Dz=10 0.43 -> 0.51, Dz=14 0.54 -> 0.64; Dz <= 8: the tile kernels, 0.56 against 0.40; Dz >= 16:
-  //                 the wide two-stage kernels are level or ahead, Dz=18 0.74 against 0.70)
-  if (K >= 113) return D >= 10 && D <= 15;
-  if (K >= 97) return D >= 8;
-  if (K >= 65) return D >= 6;
-  if (K >= 49) return D >= 18;
-  if (K >= 33) return D >= 9;
-  if (K >= 17) return D >= 13;
-  if (K >= 13) return D >= 12;
-  if (K <= 4) return !use_narrow(ctx, K, false, plain, true);        // (one slot of the narrow kernels: Dz=28 K=4 0.30 against 0.17 on 16-padded tiles)
-  return D >= 24 || !use_narrow(ctx, K, false, plain, true);
-}
-
-// Label pass of the mid shapes (mimo_mid.hip, label mode + the label-statistics kernels): K <= 48 at Dz >= 10, plain requests, where it
-// measured ahead of the row-owner label kernels (profiles/r04_mid_label_sweep.txt); "mid_labels_min_d" (mimo_tune) moves the lower end
-static int g_mid_labels_min_d = [] { const char* e = getenv("MIMO_MID_LABELS_MIN_D"); return e ? atoi(e) : 0; }();
-static int g_bound_promote_mid_k = 16;     // largest K of a mid-kernel shape whose bound-only pass runs as the plain pass (profiles/r04_bound_pass.txt: N = 2e6, ms generic / plain:
-                                           // Dz=20 K=16 1.02 / 0.73, Dz=32 K=16 1.73 / 1.51 — but Dz=24 K=32 1.51 / 1.68, Dz=16 K=48 0.99 / 1.31; every narrow shape gains: Dz=2 K=50
-                                           // 0.37 / 0.16, Dz=1 K=100 0.77 / 0.20, Dz=4 K=128 0.75 / 0.62, Dz=16 K=4 0.65 / 0.23, Dz=32 K=4 1.73 / 0.81)
-static int g_mid_labels_narrow_k = 0;      // (mimo_tune "mid_labels_narrow_k": K from which the label mode goes before the narrow label kernels; 0: measured rule)
-static bool use_mid_labels(const mimo_ctx* ctx, int K, bool wants_tables) {
-  if (wants_tables || !mid_labels_covers(K, ctx->D, ctx->structure) || !label_stats_covers(K, ctx->D, ctx->structure)) return false;
-  if (g_mid_labels_min_d > 0) return ctx->D >= g_mid_labels_min_d;
-  // measured (tools/mid_label_sweep.py, N = 2e6, fraction of the float64 rate of the whole sweep, row-owner label kernels -> mid label mode):
-  //   K <= 16 from Dz = 17 (the streamed kernel pads to 32 components: Dz=17 K=16 0.23 -> 0.34, Dz=24 0.28 -> 0.45, Dz=32 0.29 -> 0.47; Dz=28 K=8 0.15 -> 0.26)
-  //   K = 33 .. 48 from Dz = 14 (Dz=14 0.45 -> 0.49, Dz=20 0.46 -> 0.55, Dz=28 0.48 -> 0.64); K = 17 .. 32 from Dz = 20 (0.48 -> 0.51, Dz=32 0.56 -> 0.58)
-  //   below: the row-owner kernels with Theta resident in LDS stay ahead (Dz=16 K=32 0.51 against 0.41)
-  const int D = ctx->D;
-  return K >= 33 ? D >= 14 : K >= 17 ? D >= 20 : D >= 17;
-}
-
-static bool mid_labels_before_narrow(const mimo_ctx* ctx, int K) {
-  if (g_mid_labels_narrow_k > 0) return K >= g_mid_labels_narrow_k;
-  // measured (profiles/r04_mid_label_sweep.txt, second block): the narrow label kernels stay ahead up to Dz = 20 (Dz=16 K=16 0.34 against 0.33,
-  // K=8 0.23 against 0.17); from Dz = 24 their one-wave-per-SIMD variants fall behind for K = 5 .. 8 (Dz=24 K=8 1.11 -> 0.67 ms, Dz=26 1.29 -> 0.74)
-  return K >= 5 && ctx->D >= 24;
-}
-
 // Theta image of the mid kernel: [steps][KB][64] in the grouped feature order + mid_pf() zero slices
 static int upload_theta_mid(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, bool labels = false) {
   const int D = ctx->D, KB = (K + 15) / 16, NS = mid_steps(D), V = 4 * KB;
@@ -572,8 +468,7 @@ static int upload_theta_mid(mimo_ctx* ctx, const double* c, const double* b, con
   return MIMO_OK;
 }
 
-static int upload_theta(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, KernelArgs* a = nullptr) {
-  if (use_small(ctx, K)) return upload_theta_small(ctx, c, b, W, K, a ? a->theta_inline : nullptr);
+static int upload_theta(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K) {
   const int D = ctx->D, F16 = ctx->F16;
   const int K16 = ((K + 15) / 16 <= 4) ? 4 : 16;   // every wave streams 1 (K<=64) or up to 4 row blocks; unused ones are zero
   // fused kernels step through F16/4 slices per row block; the chunked E-step through whole chunks
@@ -630,6 +525,47 @@ static int upload_theta(mimo_ctx* ctx, const double* c, const double* b, const d
   return MIMO_OK;
 }
 
+// The Theta image the route's kernels read
+static int upload_theta_for(mimo_ctx* ctx, const Route& route, const double* c, const double* b, const double* W, int K, KernelArgs* a) {
+  switch (route.image) {
+    case Image::Small: return upload_theta_small(ctx, c, b, W, K, a->theta_inline);
+    case Image::Narrow: return upload_theta_narrow(ctx, c, b, W, K, route.narrow_mode - 1);
+    case Image::Mid: return upload_theta_mid(ctx, c, b, W, K);
+    case Image::MidLabels: return upload_theta_mid(ctx, c, b, W, K, true);
+    case Image::RowOwner: return upload_theta_rowwave(ctx, c, b, W, K);
+    case Image::Generic: break;
+  }
+  return upload_theta(ctx, c, b, W, K);
+}
+
+// What the router reads of the context
+static Route route_for(const mimo_ctx* ctx, int K, const RouteRequest& q) {
+  const RouteShape s = {ctx->D, ctx->F, ctx->F16, ctx->structure, ctx->N, ctx->n_bad, reinterpret_cast<uintptr_t>(ctx->Z) % 16 == 0};
+  return choose_route(s, K, q, g_route_tunables);
+}
+
+// Workgroups of the pass's first kernel (what mimo_plan reports; the label-statistics stage behind a label kernel has label_stats_grid)
+static int route_grid(const Route& route, const KernelArgs& a, int num_cu, int F, int src) {
+  switch (route.family) {
+    case Family::Small: return small_grid(a, num_cu, src);
+    case Family::Narrow: return narrow_grid(a, num_cu, F, route.narrow_mode - 1);
+    case Family::Mid: return mid_grid(a, num_cu);
+    case Family::MidLabels: return mid_labels_grid(a, num_cu);
+    case Family::Rowwave: case Family::RowwaveVi: return rowwave_grid(a, num_cu);
+    case Family::LabelStats: return label_stats_grid(a, num_cu);
+    case Family::TwoStage:
+      // two-stage pass on the pipelined E-step (mimo_wide.hip): that kernel is built for two workgroups per CU whatever K is
+      // (fused_grid's fallback assumes one for K > 128); the statistics launches of the pass share the grid (partial blocks)
+      if (src == kSrcEstep && wide_estep_covers(a.K16, a.D, a.F16, a.gibbs)) {
+        const int64_t g2 = 2 * (int64_t)num_cu;
+        return (int)(g2 < a.ntiles ? g2 : (a.ntiles > 0 ? a.ntiles : 1));
+      }
+      [[fallthrough]];
+    case Family::Fused: break;
+  }
+  return fused_grid(a, num_cu, src);
+}
+
 static void drain_profile(mimo_ctx* ctx) {
   for (auto& pr : ctx->pending) {
     float ms = 0.f;
@@ -666,6 +602,8 @@ static int timed_launch(mimo_ctx* ctx, const char* name, L&& launch) {
   ctx->pending.push_back({e0, e1, prof_slot(ctx, name)});
   return MIMO_OK;
 }
+// (a single launch under its profile name)
+#define TIMED_HIP(ctx, name, expr) timed_launch(ctx, name, [&]() -> int { HIP_TRY(ctx, expr); return MIMO_OK; })
 
 // buffers of the presorted tiles for a label-statistics pass of several launches (Dz >= 10: windows / feature slices)
 static int prepare_label_presort(mimo_ctx* ctx, KernelArgs& a) {
@@ -680,31 +618,16 @@ static int prepare_label_presort(mimo_ctx* ctx, KernelArgs& a) {
   return MIMO_OK;
 }
 
-// run the pass (one fused kernel, the two-stage sequence, or the small-shape kernel) -> reduce -> unpack;
+// run the pass (the kernels of route.family) -> reduce -> unpack;
 // deliver S / scalars to host or device pointers
-static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S, double* scalars) {
+static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S, double* scalars, const Route& route) {
   const int K = a.K, D = a.D;
   const int Kpad = a.K16 * 16;
-  const bool small = use_small(ctx, K) && ctx->narrow_call == 0;
+  const bool small = route.family == Family::Small;
   if (small) { a.F16_total = 16; a.F16 = 16; }
-  const bool rowwave = src == kSrcEstep && ctx->rowwave_call;                       // label pass + label statistics
-  const bool rowvi = src == kSrcEstep && ctx->rowwave_vi_call;                      // row-owner softmax + statistics pass
-  const bool narrow_g1 = src == kSrcEstep && ctx->narrow_call == 3;                 // narrow label pass with the statistics of the labels in the same kernel
-  const bool narrow_vi = src == kSrcEstep && (ctx->narrow_call == 1 || narrow_g1);  // narrow softmax + statistics pass (or the above: same launch shape)
-  const bool narrow_g = src == kSrcEstep && ctx->narrow_call == 2;                  // narrow label pass + label statistics
-  const bool mid_g = src == kSrcEstep && ctx->mid_labels_call;                       // mid label pass + label statistics
-  const bool lstats = !small && ((src == kSrcLabels && label_stats_covers(K, D, ctx->structure)) || rowwave || narrow_g || mid_g);
-  const bool mid = src == kSrcEstep && ctx->mid_call;                               // mid shapes: row-owner E-step + column-owner statistics
-  int grid = small ? small_grid(a, ctx->num_cu, src) : lstats ? label_stats_grid(a, ctx->num_cu)
-             : rowvi ? rowwave_grid(a, ctx->num_cu) : narrow_vi ? narrow_grid(a, ctx->num_cu, ctx->F, narrow_g1 ? 2 : 0)
-             : mid ? mid_grid(a, ctx->num_cu) : fused_grid(a, ctx->num_cu, src);
-  // two-stage pass on the pipelined E-step (mimo_wide.hip): that kernel is built for two workgroups per CU whatever K is
-  // (fused_grid's fallback assumes one for K > 128); the statistics launches of the pass share the grid (partial blocks)
-  if (!small && !lstats && !rowvi && !narrow_vi && !mid && src == kSrcEstep && !fused_covers(a.K16, a.F16 / 16, src) &&
-      wide_estep_covers(a.K16, D, a.F16, a.gibbs)) {
-    const int64_t g2 = 2 * (int64_t)ctx->num_cu;
-    grid = (int)(g2 < a.ntiles ? g2 : (a.ntiles > 0 ? a.ntiles : 1));
-  }
+  const int kgrid = route_grid(route, a, ctx->num_cu, ctx->F, src);
+  const bool lstats = route.label_draw() || route.family == Family::LabelStats;     // the label-statistics kernels close the pass
+  const int grid = lstats ? label_stats_grid(a, ctx->num_cu) : kgrid;               // partial blocks
   const size_t pstride = (size_t)Kpad * a.F16 + 4;
   int rc;
   if ((rc = ensure_dev(ctx, &ctx->partials, &ctx->partials_cap, pstride * (size_t)grid))) return rc;
@@ -719,80 +642,42 @@ static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S,
   }
 #endif
   const int ncb_total = a.F16 / 16;
-  if (lstats) {
-    if (rowwave) {
-      // the resident-Theta label kernel counts its labels for the slot table of the statistics kernel behind it
-      // (not with NaN rows: their labels are masked before the statistics; MIMO_FUSE_LABEL_HIST=0: off)
-      static const bool fuse_on = [] { const char* e = getenv("MIMO_FUSE_LABEL_HIST"); return !e || atoi(e) != 0; }();
-      a.fuse_hist = fuse_on && a.do_stats && ctx->n_bad == 0 && a.aux && label_stats_uses_slots(K, D, a.N) &&
-                    gibbs_rowwave_counts_labels(K, a.F16, a.ZS) ? 1 : 0;
-      rc = timed_launch(ctx, "gibbs_rowwave_kernel", [&]() -> int {
-        if (a.fuse_hist) HIP_TRY(ctx, launch_label_hist_reset(a, ctx->stream));
-        HIP_TRY(ctx, launch_gibbs_rowwave(a, rowwave_grid(a, ctx->num_cu), ctx->stream));
-        return MIMO_OK;
-      });
-      if (rc) return rc;
-    } else if (mid_g) {
-      rc = timed_launch(ctx, "mid_kernel (labels)", [&]() -> int {
-        HIP_TRY(ctx, launch_mid_labels(a, mid_labels_grid(a, ctx->num_cu), ctx->stream));
-        return MIMO_OK;
-      });
-      if (rc) return rc;
-    } else if (narrow_g) {
-      static const bool fuse_on = [] { const char* e = getenv("MIMO_FUSE_LABEL_HIST"); return !e || atoi(e) != 0; }();
-      a.fuse_hist = fuse_on && a.do_stats && ctx->n_bad == 0 && a.aux && label_stats_uses_slots(K, D, a.N) ? 1 : 0;
-      rc = timed_launch(ctx, "narrow_kernel", [&]() -> int {
-        if (a.fuse_hist) HIP_TRY(ctx, launch_label_hist_reset(a, ctx->stream));
-        HIP_TRY(ctx, launch_narrow(a, ctx->F, 1, narrow_grid(a, ctx->num_cu, ctx->F, 1), ctx->stream));
-        return MIMO_OK;
-      });
-      if (rc) return rc;
-    }
-    if (a.do_stats) {
-      if ((rc = prepare_label_presort(ctx, a))) return rc;
-      rc = timed_launch(ctx, "label_stats_kernel", [&]() -> int {
-        HIP_TRY(ctx, launch_label_stats(a, ctx->structure, grid, ctx->stream));
-        return MIMO_OK;
-      });
-      if (rc) return rc;
-    }
-  } else if (rowvi) {
-    rc = timed_launch(ctx, "vi_rowwave_kernel", [&]() -> int {
-      HIP_TRY(ctx, launch_vi_rowwave(a, grid, ctx->stream));
+  // a resident-Theta label kernel counts its labels for the slot table of the statistics kernel behind it
+  // (not with NaN rows: their labels are masked before the statistics; MIMO_FUSE_LABEL_HIST=0: off)
+  static const bool fuse_on = [] { const char* e = getenv("MIMO_FUSE_LABEL_HIST"); return !e || atoi(e) != 0; }();
+  const bool fuse_hist = fuse_on && a.do_stats && ctx->n_bad == 0 && a.aux && label_stats_uses_slots(K, D, a.N);
+  rc = MIMO_OK;
+  switch (route.family) {
+  case Family::LabelStats: break;
+  case Family::Rowwave:
+    a.fuse_hist = fuse_hist && gibbs_rowwave_counts_labels(K, a.F16, a.ZS) ? 1 : 0;
+    rc = timed_launch(ctx, "gibbs_rowwave_kernel", [&]() -> int {
+      if (a.fuse_hist) HIP_TRY(ctx, launch_label_hist_reset(a, ctx->stream));
+      HIP_TRY(ctx, launch_gibbs_rowwave(a, kgrid, ctx->stream));
       return MIMO_OK;
     });
-    if (rc) return rc;
-  } else if (narrow_vi) {
+    break;
+  case Family::MidLabels: rc = TIMED_HIP(ctx, "mid_kernel (labels)", launch_mid_labels(a, kgrid, ctx->stream)); break;
+  case Family::Narrow:
+    a.fuse_hist = route.narrow_mode == 2 && fuse_hist ? 1 : 0;
     rc = timed_launch(ctx, "narrow_kernel", [&]() -> int {
-      HIP_TRY(ctx, launch_narrow(a, ctx->F, narrow_g1 ? 2 : 0, grid, ctx->stream));
+      if (a.fuse_hist) HIP_TRY(ctx, launch_label_hist_reset(a, ctx->stream));
+      HIP_TRY(ctx, launch_narrow(a, ctx->F, route.narrow_mode - 1, kgrid, ctx->stream));
       return MIMO_OK;
     });
-    if (rc) return rc;
-  } else if (mid) {
-    rc = timed_launch(ctx, "mid_kernel", [&]() -> int {
-      HIP_TRY(ctx, launch_mid(a, grid, ctx->stream));
-      return MIMO_OK;
-    });
-    if (rc) return rc;
-  } else if (small) {
-    rc = timed_launch(ctx, "small_kernel", [&]() -> int {
+    break;
+  case Family::RowwaveVi: rc = TIMED_HIP(ctx, "vi_rowwave_kernel", launch_vi_rowwave(a, grid, ctx->stream)); break;
+  case Family::Mid: rc = TIMED_HIP(ctx, "mid_kernel", launch_mid(a, grid, ctx->stream)); break;
+  case Family::Small: case Family::Fused:
+    rc = timed_launch(ctx, small ? "small_kernel" : "fused_kernel", [&]() -> int {
       bool unsupported = false;
-      hipError_t he = launch_small(a, src, grid, ctx->stream, &unsupported);
-      if (unsupported) return fail(ctx, MIMO_E_UNSUPPORTED, "no small-shape kernel for K=%d, Dz=%d", K, D);
+      hipError_t he = small ? launch_small(a, src, grid, ctx->stream, &unsupported) : launch_fused(a, src, grid, ctx->stream, &unsupported);
+      if (unsupported) return fail(ctx, MIMO_E_UNSUPPORTED, "no %s kernel for K=%d, Dz=%d", small ? "small-shape" : "fused", K, D);
       HIP_TRY(ctx, he);
       return MIMO_OK;
     });
-    if (rc) return rc;
-  } else if (fused_covers(a.K16, ncb_total, src)) {
-    rc = timed_launch(ctx, "fused_kernel", [&]() -> int {
-      bool unsupported = false;
-      hipError_t he = launch_fused(a, src, grid, ctx->stream, &unsupported);
-      if (unsupported) return fail(ctx, MIMO_E_UNSUPPORTED, "no fused kernel for K=%d, Dz=%d", K, D);
-      HIP_TRY(ctx, he);
-      return MIMO_OK;
-    });
-    if (rc) return rc;
-  } else {
+    break;
+  case Family::TwoStage: {
     // two-stage path: chunked E-step writes responsibilities / labels, then the statistics kernel
     // runs once per group of <= kMaxNCB feature column blocks, all into the same partial block.
     KernelArgs st = a;
@@ -808,17 +693,10 @@ static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S,
       }
       if (chunked_lds_bytes(e) > 160 * 1024)
         return fail(ctx, MIMO_E_UNSUPPORTED, "K=%d, Dz=%d needs more LDS than one CU has", K, D);
-      if (wide_estep_covers(a.K16, D, a.F16, e.gibbs)) {          // pipelined softmax / label pass (mimo_wide.hip)
-        rc = timed_launch(ctx, "wide_estep_kernel", [&]() -> int {
-          HIP_TRY(ctx, launch_wide_estep(e, grid, ctx->stream));
-          return MIMO_OK;
-        });
-      } else {
-        rc = timed_launch(ctx, "estep_chunked_kernel", [&]() -> int {
-          HIP_TRY(ctx, launch_estep_chunked(e, grid, ctx->stream));
-          return MIMO_OK;
-        });
-      }
+      if (wide_estep_covers(a.K16, D, a.F16, e.gibbs))            // pipelined softmax / label pass (mimo_wide.hip)
+        rc = TIMED_HIP(ctx, "wide_estep_kernel", launch_wide_estep(e, grid, ctx->stream));
+      else
+        rc = TIMED_HIP(ctx, "estep_chunked_kernel", launch_estep_chunked(e, grid, ctx->stream));
       if (rc) return rc;
       st.resp = e.resp; st.labels = e.labels; st.write_scalars = 0;
       stats_src = e.gibbs ? kSrcLabels : kSrcWeights;
@@ -834,11 +712,7 @@ static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S,
       KernelArgs g = st;
       g.gibbs = 0; g.do_stats = 1; g.logp = nullptr; g.lse = nullptr;
       if ((rc = prepare_label_presort(ctx, g))) return rc;
-      rc = timed_launch(ctx, "label_stats_kernel", [&]() -> int {
-        HIP_TRY(ctx, launch_label_stats(g, ctx->structure, grid, ctx->stream));
-        return MIMO_OK;
-      });
-      if (rc) return rc;
+      rc = TIMED_HIP(ctx, "label_stats_kernel", launch_label_stats(g, ctx->structure, grid, ctx->stream));
     } else if (a.do_stats) {
       const bool wide = stats_src == kSrcWeights && wide_stats_covers(a.K16, D);     // 8-wave statistics kernel (mimo_wide.hip)
       const int gmax = wide ? wide_stats_group_ncb(a.K16, ncb_total) : stats_group_ncb(a.K16);
@@ -849,10 +723,7 @@ static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S,
         g.gibbs = 0; g.do_stats = 1; g.logp = nullptr; g.lse = nullptr;
         if (cb0 > 0) g.write_scalars = 0;
         if (wide) {
-          rc = timed_launch(ctx, "wide_stats_kernel", [&]() -> int {
-            HIP_TRY(ctx, launch_wide_stats(g, grid, ctx->stream));
-            return MIMO_OK;
-          });
+          rc = TIMED_HIP(ctx, "wide_stats_kernel", launch_wide_stats(g, grid, ctx->stream));
         } else {
           rc = timed_launch(ctx, src == kSrcEstep ? "fused_kernel(statistics of a column group)" : "fused_kernel", [&]() -> int {
             bool unsupported = false;
@@ -865,9 +736,16 @@ static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S,
       }
     }
   }
+  }
+  if (rc) return rc;
+  if (lstats && a.do_stats) {
+    if ((rc = prepare_label_presort(ctx, a))) return rc;
+    if ((rc = TIMED_HIP(ctx, "label_stats_kernel", launch_label_stats(a, ctx->structure, grid, ctx->stream)))) return rc;
+  }
   if (ctx->prof) ctx->prof_n += 1;
   const bool async = (flags & MIMO_F_ASYNC) != 0;
-  const bool want_stats = a.do_stats && (S || async);
+  // (a promoted bound pass leaves its statistics in the partial blocks: nothing of them is reduced, all-reduced or copied)
+  const bool want_stats = a.do_stats && !route.promoted && (S || async);
   const bool device_out = (flags & MIMO_F_DEVICE_OUT) != 0;
   if (!want_stats && !scalars && !async) return MIMO_OK;
 
@@ -918,8 +796,8 @@ static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S,
 //   label pass   : labels first (no statistics), then the statistics of the labels with the NaN rows set to -1; the
 //                  labels drawn ON the NaN rows are counted per component for the gating update (mimo_nan_info);
 //   statistics of a caller's table / labels: masked copies.
-static int run_fused(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S, double* scalars) {
-  if (ctx->n_bad <= 0) return run_pass(ctx, a, src, flags, S, scalars);
+static int run_fused(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S, double* scalars, const Route& route) {
+  if (ctx->n_bad <= 0) return run_pass(ctx, a, src, flags, S, scalars, route);
   int rc;
   const int64_t N = ctx->N;
   ctx->bad_counts_K = 0;
@@ -931,17 +809,14 @@ static int run_fused(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S
       HIP_TRY(ctx, launch_mask_table(a.u, ctx->row_mask, ctx->table_tmp, 1, N, ctx->stream));
       a.u = ctx->table_tmp;
     }
-    return run_pass(ctx, a, src, flags, S, scalars);
+    return run_pass(ctx, a, src, flags, S, scalars, route);
   }
   if ((src == kSrcEstep && a.gibbs) || src == kSrcLabels) {
     const bool want = a.do_stats != 0;
     if (src == kSrcEstep) {
       if (flags & MIMO_F_ASYNC) return fail(ctx, MIMO_E_UNSUPPORTED, "asynchronous label pass on data with NaN rows");
       a.do_stats = 0;
-      if ((rc = run_pass(ctx, a, kSrcEstep, flags & ~(MIMO_F_DEVICE_OUT), nullptr, nullptr))) return rc;
-      ctx->rowwave_call = false;
-      ctx->narrow_call = 0;
-      ctx->mid_labels_call = false;
+      if ((rc = run_pass(ctx, a, kSrcEstep, flags & ~(MIMO_F_DEVICE_OUT), nullptr, nullptr, route))) return rc;
     }
     if ((rc = ensure_dev(ctx, &ctx->labels_tmp, &ctx->labels_tmp_cap, (size_t)N))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(ctx->cnt_d + 1, 0, 256 * sizeof(unsigned long long), ctx->stream));
@@ -950,14 +825,14 @@ static int run_fused(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S
     if (!want) return MIMO_OK;
     KernelArgs b = a;
     b.labels = ctx->labels_tmp; b.gibbs = 0; b.do_stats = 1; b.u = nullptr; b.logp = nullptr; b.lse = nullptr; b.resp = nullptr;
-    return run_pass(ctx, b, kSrcLabels, flags, S, scalars);
+    return run_pass(ctx, b, kSrcLabels, flags, S, scalars, route_for(ctx, a.K, {kSrcLabels}));
   }
   // kSrcWeights: statistics of a (K, N) table
   const size_t kn = (size_t)a.K * (size_t)N;
   if ((rc = ensure_dev(ctx, &ctx->table_tmp, &ctx->table_tmp_cap, kn))) return rc;
   HIP_TRY(ctx, launch_mask_table(a.resp, ctx->row_mask, ctx->table_tmp, a.K, N, ctx->stream));
   a.resp = ctx->table_tmp;
-  return run_pass(ctx, a, src, flags, S, scalars);
+  return run_pass(ctx, a, src, flags, S, scalars, route);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1154,16 +1029,6 @@ static int keep_tables(mimo_ctx* ctx, int K, int flags, KernelArgs* a) {
   return MIMO_OK;
 }
 
-// Which bound-only requests run as the plain pass (mimo_estep).  MIMO_BOUND_PROMOTE = 0: none, 2: every shape of the narrow / mid kernels.
-static bool bound_promote(const mimo_ctx* ctx, int K) {
-  static const int mode = [] { const char* e = getenv("MIMO_BOUND_PROMOTE"); return e ? atoi(e) : 1; }();
-  if (mode == 0) return false;
-  const bool md = use_mid(ctx, K, true);
-  const bool nv = !md && use_narrow(ctx, K, false, true, true) != 0;
-  if (mode == 2) return md || nv;
-  return (md && K <= g_bound_promote_mid_k) || nv;
-}
-
 int mimo_estep(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K,
                int flags, double* S, double* scalars) {
   return guarded(ctx, [&]() -> int {
@@ -1175,31 +1040,17 @@ int mimo_estep(mimo_ctx* ctx, const double* c, const double* b, const double* W,
     return fail(ctx, MIMO_E_INVALID, "mimo_estep: S is NULL without MIMO_F_NO_STATS / MIMO_F_ASYNC");
   KernelArgs a;
   fill_args(ctx, K, &a);
-  const bool tables = (flags & (MIMO_F_KEEP_RESP | MIMO_F_KEEP_LOGP | MIMO_F_KEEP_LSE | MIMO_F_ENTROPY_SPLIT)) != 0;
-  // A bound-only request (no statistics, no tables: the full-data pass of every SVI outer iteration, gmm.py:319-326 / ilr.py:270-277
-  // of the reference) used to take the generic tile kernels whatever the shape; where the plain pass runs on the narrow or mid kernels
-  // those pay for 16 x 16 padding the plain pass does not have, and the plain pass with its statistics left in the partial blocks is
-  // the faster bound (bound_promote(): measured rule).
-  const bool promote = no_stats && !tables && !(flags & MIMO_F_DEVICE_OUT) && bound_promote(ctx, K);
-  a.do_stats = (no_stats && !promote) ? 0 : 1;
+  RouteRequest q;
+  q.tables = (flags & (MIMO_F_KEEP_RESP | MIMO_F_KEEP_LOGP | MIMO_F_KEEP_LSE | MIMO_F_ENTROPY_SPLIT)) != 0;
+  q.stats = !no_stats;
+  q.device_out = (flags & MIMO_F_DEVICE_OUT) != 0;
+  const Route route = route_for(ctx, K, q);
+  a.do_stats = (no_stats && !route.promoted) ? 0 : 1;
   a.split = (flags & MIMO_F_ENTROPY_SPLIT) ? 1 : 0;
   if ((rc = keep_tables(ctx, K, flags, &a))) return rc;
-  // plain softmax + statistics pass at K <= 64, Dz <= 9: the row-owner kernel (Theta in the row-owner image)
-  const bool plain = (!no_stats || promote) && !tables;
-  const bool md = use_mid(ctx, K, plain);                     // mid shapes (K <= 32 over wide rows): mimo_mid.hip
-  const bool nv = !md && use_narrow(ctx, K, false, plain, true) != 0;      // narrow shapes (Dz <= 4, 32 < K <= 128; few components over many features): mimo_narrow.hip
-  const bool rv = !nv && !md && plain && ctx->n_bad == 0 && ctx->D <= 16 && !use_small(ctx, K) && vi_rowwave_covers(K, ctx->F16, a.ZS);
-  if ((rc = nv ? upload_theta_narrow(ctx, c, b, W, K, 0) : md ? upload_theta_mid(ctx, c, b, W, K)
-            : rv ? upload_theta_rowwave(ctx, c, b, W, K) : upload_theta(ctx, c, b, W, K, &a))) return rc;
+  if ((rc = upload_theta_for(ctx, route, c, b, W, K, &a))) return rc;
   a.theta = ctx->theta_d;
-  ctx->rowwave_vi_call = rv;
-  ctx->narrow_call = nv ? 1 : 0;
-  ctx->mid_call = md;
-  rc = run_fused(ctx, a, kSrcEstep, flags, no_stats ? nullptr : S, scalars);
-  ctx->rowwave_vi_call = false;
-  ctx->narrow_call = 0;
-  ctx->mid_call = false;
-  return rc;
+  return run_fused(ctx, a, kSrcEstep, flags, no_stats ? nullptr : S, scalars, route);
   });
 }
 
@@ -1215,10 +1066,11 @@ int mimo_estep_weighted(mimo_ctx* ctx, const double* c, const double* b, const d
   KernelArgs a;
   fill_args(ctx, K, &a);
   // the narrow kernels take the weights on their normaliser (plain requests: statistics + scalars only)
-  const bool plain_w = (flags & (MIMO_F_KEEP_RESP | MIMO_F_KEEP_LOGP | MIMO_F_KEEP_LSE | MIMO_F_ENTROPY_SPLIT)) == 0;
-  const bool md = use_mid(ctx, K, plain_w);              // mid shapes (K <= 32 over wide rows)
-  const bool nv = !md && use_narrow(ctx, K, false, plain_w, true) != 0;
-  if (!nv && !md && !fused_covers(a.K16, a.F16 / 16, kSrcEstep))
+  RouteRequest q;
+  q.tables = (flags & (MIMO_F_KEEP_RESP | MIMO_F_KEEP_LOGP | MIMO_F_KEEP_LSE | MIMO_F_ENTROPY_SPLIT)) != 0;
+  q.weighted = true;
+  const Route route = route_for(ctx, K, q);
+  if (route.family == Family::TwoStage)
     return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_estep_weighted: K=%d, Dz=%d runs on the two-stage path, which takes "
                 "its weights as a table (mimo_estep + mimo_weighted_stats)", K, ctx->D);
   a.split = (flags & MIMO_F_ENTROPY_SPLIT) ? 1 : 0;
@@ -1236,14 +1088,9 @@ int mimo_estep_weighted(mimo_ctx* ctx, const double* c, const double* b, const d
     a.u = ctx->u_d;
     ctx->weights_resident = true;
   }
-  if ((rc = nv ? upload_theta_narrow(ctx, c, b, W, K, 0) : md ? upload_theta_mid(ctx, c, b, W, K) : upload_theta(ctx, c, b, W, K, &a))) return rc;
+  if ((rc = upload_theta_for(ctx, route, c, b, W, K, &a))) return rc;
   a.theta = ctx->theta_d;
-  ctx->narrow_call = nv ? 1 : 0;
-  ctx->mid_call = md;
-  rc = run_fused(ctx, a, kSrcEstep, flags, S, scalars);
-  ctx->narrow_call = 0;
-  ctx->mid_call = false;
-  return rc;
+  return run_fused(ctx, a, kSrcEstep, flags, S, scalars, route);
   });
 }
 
@@ -1290,22 +1137,14 @@ int mimo_gibbs_labels(mimo_ctx* ctx, const double* c, const double* b, const dou
       ctx->weights_resident = false;
     }
   }
-  const bool wants_tables = (flags & (MIMO_F_KEEP_LOGP | MIMO_F_KEEP_LSE)) != 0;
-  int nw = use_narrow(ctx, K, true, !wants_tables, !no_stats);
-  const bool ml = !use_small(ctx, K) && use_mid_labels(ctx, K, wants_tables) && (!nw || mid_labels_before_narrow(ctx, K));
-  if (ml) nw = 0;
-  const bool rw = !nw && !ml && !use_small(ctx, K) && use_rowwave(ctx, K, wants_tables);
-  if ((rc = nw ? upload_theta_narrow(ctx, c, b, W, K, nw - 1) : ml ? upload_theta_mid(ctx, c, b, W, K, true)
-            : rw ? upload_theta_rowwave(ctx, c, b, W, K) : upload_theta(ctx, c, b, W, K, &a))) return rc;
+  RouteRequest q;
+  q.gibbs = true;
+  q.tables = (flags & (MIMO_F_KEEP_LOGP | MIMO_F_KEEP_LSE)) != 0;
+  q.stats = !no_stats;
+  const Route route = route_for(ctx, K, q);
+  if ((rc = upload_theta_for(ctx, route, c, b, W, K, &a))) return rc;
   a.theta = ctx->theta_d;
-  ctx->rowwave_call = rw;
-  ctx->narrow_call = nw;
-  ctx->mid_labels_call = ml;
-  rc = run_fused(ctx, a, kSrcEstep, flags, no_stats ? nullptr : S, nullptr);
-  ctx->rowwave_call = false;
-  ctx->narrow_call = 0;
-  ctx->mid_labels_call = false;
-  if (rc) return rc;
+  if ((rc = run_fused(ctx, a, kSrcEstep, flags, no_stats ? nullptr : S, nullptr, route))) return rc;
   if (labels_out && !(flags & MIMO_F_DEVICE_OUT)) {
     HIP_TRY(ctx, hipMemcpyAsync(labels_out, ctx->labels, (size_t)ctx->N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1334,7 +1173,7 @@ int mimo_weighted_stats(mimo_ctx* ctx, const double* resp, int K, int flags, dou
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     a.resp = ctx->win;
   }
-  return run_fused(ctx, a, kSrcWeights, flags, S, nullptr);
+  return run_fused(ctx, a, kSrcWeights, flags, S, nullptr, route_for(ctx, K, {kSrcWeights}));
   });
 }
 
@@ -1357,7 +1196,7 @@ int mimo_label_stats(mimo_ctx* ctx, const int32_t* labels, int K, int flags, dou
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     a.labels = ctx->lin;
   }
-  return run_fused(ctx, a, kSrcLabels, flags, S, nullptr);
+  return run_fused(ctx, a, kSrcLabels, flags, S, nullptr, route_for(ctx, K, {kSrcLabels}));
   });
 }
 
@@ -1418,7 +1257,7 @@ int mimo_random_resp_stats(mimo_ctx* ctx, int K, uint64_t seed, int flags, doubl
   KernelArgs a;
   fill_args(ctx, K, &a);
   a.resp = ctx->resp;
-  return run_fused(ctx, a, kSrcWeights, flags, S, nullptr);
+  return run_fused(ctx, a, kSrcWeights, flags, S, nullptr, route_for(ctx, K, {kSrcWeights}));
   });
 }
 
@@ -1694,26 +1533,15 @@ int mimo_tune(mimo_ctx* ctx, const char* key, int64_t value) {
       set_narrow_big_vi((int)value);
       return MIMO_OK;
     }
-    if (!strcmp(key, "mid_labels_narrow_k")) {
-      if (value < 0 || value > 64) return fail(ctx, MIMO_E_INVALID, "mimo_tune: mid_labels_narrow_k = %lld outside [0, 64]", (long long)value);
-      g_mid_labels_narrow_k = (int)value;
-      return MIMO_OK;
-    }
-    if (!strcmp(key, "mid_labels_min_d")) {
-      if (value < 0 || value > 64) return fail(ctx, MIMO_E_INVALID, "mimo_tune: mid_labels_min_d = %lld outside [0, 64]", (long long)value);
-      g_mid_labels_min_d = (int)value;
-      return MIMO_OK;
-    }
-    if (!strcmp(key, "mid_narrow_k")) {
-      if (value < 0 || value > 64) return fail(ctx, MIMO_E_INVALID, "mimo_tune: mid_narrow_k = %lld outside [0, 64]", (long long)value);
-      g_mid_narrow_k = (int)value;
-      return MIMO_OK;
-    }
-    if (!strcmp(key, "mid_min_d")) {
-      if (value < 0 || value > 64) return fail(ctx, MIMO_E_INVALID, "mimo_tune: mid_min_d = %lld outside [0, 64]", (long long)value);
-      g_mid_min_d = (int)value;
-      return MIMO_OK;
-    }
+    RouteTunables& t = g_route_tunables;     // process-wide, as sorted_range and narrow_big_vi (include/mimo_hip.h)
+    const struct { const char* key; int* knob; } mid_keys[] = {{"mid_labels_narrow_k", &t.mid_labels_narrow_k}, {"mid_labels_min_d", &t.mid_labels_min_d},
+                                                              {"mid_narrow_k", &t.mid_narrow_k}, {"mid_min_d", &t.mid_min_d}};
+    for (const auto& m : mid_keys)
+      if (!strcmp(key, m.key)) {
+        if (value < 0 || value > 64) return fail(ctx, MIMO_E_INVALID, "mimo_tune: %s = %lld outside [0, 64]", key, (long long)value);
+        *m.knob = (int)value;
+        return MIMO_OK;
+      }
     return fail(ctx, MIMO_E_INVALID, "mimo_tune: unknown key '%s'", key);
   });
 }
@@ -1762,9 +1590,9 @@ int mimo_profile_kernels(mimo_ctx* ctx, char* buf, int len) {
   });
 }
 
-// The routing decision of mimo_plan without anything that needs a device: kind, launches, passes (out8[6] — the grid — stays 0),
-// and a one-line description of the kernels (desc, may be null).
-static void plan_route(const mimo_ctx* ctx, const KernelArgs& a, int K, int gibbs, int64_t* out8, char* desc, size_t dlen) {
+// The route of a plain pass (the one run_pass launches from) described without anything that needs a device: kind, launches, passes
+// (out8[6] — the grid — stays 0), and a one-line description of the kernels (desc, may be null).
+static void plan_route(const mimo_ctx* ctx, const Route& route, const KernelArgs& a, int K, int gibbs, int64_t* out8, char* desc, size_t dlen) {
   const int ncb = a.F16 / 16, D = ctx->D;
   char lst[160] = "";           // the label-statistics stage of a label pass
   auto label_stage = [&]() {
@@ -1779,39 +1607,41 @@ static void plan_route(const mimo_ctx* ctx, const KernelArgs& a, int K, int gibb
   memset(out8, 0, 8 * sizeof(int64_t));
   out8[4] = 1;                           // passes over Z
   out8[5] = gibbs ? 1 : 0;               // passes over the labels
-  if (!gibbs && use_mid(ctx, K, true)) {
+  const Family f = route.family;
+  if (f == Family::Mid) {
     out8[0] = MIMO_PLAN_MID; out8[1] = 1;
     if (desc) snprintf(desc, dlen, "mid_kernel<Dz=%d, row blocks %d, %d waves>", D, (K + 15) / 16, mid_rows_per_step(K, D) / 16);
-  } else if (gibbs && use_mid_labels(ctx, K, false) && !use_small(ctx, K) && (mid_labels_before_narrow(ctx, K) || !use_narrow(ctx, K, true, true, true))) {
+  } else if (f == Family::MidLabels) {
     const int ll = label_stage();
     out8[0] = MIMO_PLAN_MID; out8[1] = 1 + ll; out8[4] = 1 + ll; out8[5] = 1 + ll;
     if (desc) snprintf(desc, dlen, "mid_kernel<Dz=%d, row blocks %d, label draw> + %s", D, (K + 15) / 16, lst);
-  } else if (const int nm = use_narrow(ctx, K, gibbs != 0, true, true)) {
+  } else if (f == Family::Narrow) {
+    const int nm = route.narrow_mode;
     out8[0] = MIMO_PLAN_NARROW; out8[1] = nm == 2 ? 2 : 1;
     if (nm == 2) { out8[4] = 2; out8[5] = 2; }       // label kernel + label-statistics kernel (nm == 3: one kernel, labels written once)
     if (nm == 2) label_stage();
     if (desc) snprintf(desc, dlen, "narrow_kernel<%d slots, %d steps%s, %s>%s%s", narrow_v(K), narrow_steps(K, ctx->F, D, nm - 1),
                        narrow_dt(K, ctx->F, D, nm - 1) ? ", grouped" : "", nm == 1 ? "softmax + statistics" : nm == 2 ? "label draw" : "label draw + statistics",
                        nm == 2 ? " + " : "", nm == 2 ? lst : "");
-  } else if (use_small(ctx, K)) {
+  } else if (f == Family::Small) {
     out8[0] = MIMO_PLAN_SMALL; out8[1] = 1;
     if (desc) snprintf(desc, dlen, "small_kernel<%d components per lane, %d lanes per row>", small_kl(D, K), small_g(D, K));
-  } else if (!gibbs && ctx->n_bad == 0 && D <= 16 && vi_rowwave_covers(K, ctx->F16, a.ZS)) {
+  } else if (f == Family::RowwaveVi) {
     out8[0] = MIMO_PLAN_ROWWAVE_VI; out8[1] = 1;
     if (desc) snprintf(desc, dlen, "vi_rowwave_kernel<%d row blocks>", K <= 32 ? 2 : 4);
-  } else if (gibbs && use_rowwave(ctx, K, false)) {
+  } else if (f == Family::Rowwave) {
     const int ll = label_stage();     // (> 1: the sliced statistics of the large shapes)
     out8[0] = MIMO_PLAN_ROWWAVE; out8[1] = 1 + ll;
     out8[4] = 1 + ll;                    // Z: label kernel + every statistics launch
     out8[5] = 1 + ll;                    // labels written once, read once per statistics launch
     if (desc) snprintf(desc, dlen, "%s<%d row blocks> + %s", gibbs_rowwave_counts_labels(K, ctx->F16, a.ZS) ? "gibbs_rowwave_kernel" : "gibbs_stream_kernel",
                        rowwave_kb_shape(K, ctx->F16, a.ZS), lst);
-  } else if (fused_covers(a.K16, ncb, kSrcEstep)) {
+  } else if (f == Family::Fused) {
     out8[0] = MIMO_PLAN_FUSED; out8[1] = 1;
     if (desc) snprintf(desc, dlen, "fused_kernel<%d column blocks, %d row block%s per wave%s>", ncb, a.K16 <= 4 ? 1 : a.K16 <= 8 ? 2 : a.K16 <= 12 ? 3 : 4,
                        a.K16 <= 4 ? "" : "s", K <= 32 && D >= 7 ? ", work split over the waves" : "");
   } else {
-    const bool wide = !gibbs && wide_stats_covers(a.K16, D);       // as run_pass
+    const bool wide = !gibbs && wide_stats_covers(a.K16, D);       // (the sub-kernels of the family: as run_pass picks them)
     const int gmax = wide ? wide_stats_group_ncb(a.K16, ncb) : stats_group_ncb(a.K16), groups = (ncb + gmax - 1) / gmax;
     out8[0] = MIMO_PLAN_TWO_STAGE; out8[1] = 1 + groups;
     out8[2] = gibbs ? 0 : 1;             // the (K, N) responsibility table goes through HBM
@@ -1819,7 +1649,7 @@ static void plan_route(const mimo_ctx* ctx, const KernelArgs& a, int K, int gibb
     out8[4] = 1 + groups;                // Z: the E-step + every statistics launch
     out8[5] = gibbs ? 1 + groups : 0;
     const char* est = wide_estep_covers(a.K16, D, a.F16, gibbs) ? "wide_estep_kernel" : "estep_chunked_kernel";
-    if (gibbs && label_stats_covers(K, D, ctx->structure)) {      // label-indexed statistics (as run_pass)
+    if (gibbs && label_stats_covers(K, D, ctx->structure)) {      // label-indexed statistics
       const int ll = label_stage();
       out8[1] = 1 + ll; out8[4] = 1 + ll; out8[5] = 1 + ll;
       if (desc) snprintf(desc, dlen, "%s (label draw) + %s", est, lst);
@@ -1839,20 +1669,9 @@ int mimo_plan(mimo_ctx* ctx, int K, int gibbs, int64_t* out8) {
   KernelArgs a;
   fill_args(ctx, K, &a);
   a.gibbs = gibbs ? 1 : 0;
-  plan_route(ctx, a, K, gibbs, out8, nullptr, 0);
-  switch (out8[0]) {
-    case MIMO_PLAN_MID: out8[6] = gibbs ? mid_labels_grid(a, ctx->num_cu) : mid_grid(a, ctx->num_cu); break;
-    case MIMO_PLAN_NARROW: out8[6] = narrow_grid(a, ctx->num_cu, ctx->F, use_narrow(ctx, K, gibbs != 0, true, true) - 1); break;
-    case MIMO_PLAN_SMALL: out8[6] = small_grid(a, ctx->num_cu, kSrcEstep); break;
-    case MIMO_PLAN_ROWWAVE_VI: case MIMO_PLAN_ROWWAVE: out8[6] = rowwave_grid(a, ctx->num_cu); break;
-    case MIMO_PLAN_FUSED: out8[6] = fused_grid(a, ctx->num_cu, kSrcEstep); break;
-    default:
-      out8[6] = fused_grid(a, ctx->num_cu, kSrcEstep);
-      if (wide_estep_covers(a.K16, ctx->D, a.F16, gibbs)) {                // as run_pass: two workgroups per CU
-        const int64_t g2 = 2 * (int64_t)ctx->num_cu;
-        out8[6] = g2 < a.ntiles ? g2 : (a.ntiles > 0 ? a.ntiles : 1);
-      }
-  }
+  const Route route = route_for(ctx, K, {kSrcEstep, gibbs != 0});
+  plan_route(ctx, route, a, K, gibbs, out8, nullptr, 0);
+  out8[6] = route_grid(route, a, ctx->num_cu, ctx->F, kSrcEstep);
   out8[7] = ctx->num_cu;
   return MIMO_OK;
   });
@@ -1872,7 +1691,7 @@ int mimo_plan_shape(int Dz, int K, int structure, int64_t N, int gibbs, int64_t*
   fill_args(&ctx, K, &a);
   a.gibbs = gibbs ? 1 : 0;
   if (desc && desc_len > 0) desc[0] = 0;
-  plan_route(&ctx, a, K, gibbs, out8, desc, desc && desc_len > 0 ? (size_t)desc_len : 0);
+  plan_route(&ctx, route_for(&ctx, K, {kSrcEstep, gibbs != 0}), a, K, gibbs, out8, desc, desc && desc_len > 0 ? (size_t)desc_len : 0);
   return MIMO_OK;
   });
 }

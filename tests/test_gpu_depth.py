@@ -280,6 +280,56 @@ def test_plan_with_data_agrees_with_the_shape_router(engine):
                 assert p["kind"] == kinds[out[0]] and p["kernels_per_pass"] == out[1] and p["data_passes"] == out[4], (D, K, gibbs, p, list(out))
 
 
+def test_plan_agrees_with_the_kernels_a_pass_launches(engine):
+    """mimo_plan describes the route the pass is launched from: one pass under the profiler per shape and pass kind, and the
+    names the profile recorded against plan(K)["kind"].  The profile holds one name per timed launch site, some shared
+    (label_stats_kernel: every label-statistics variant; gibbs_rowwave_kernel: the streamed label kernel too), so the table
+    below is at that level.  N = 2^17 rows: the slot-table label statistics are on, as in ROUTING.md.  Label passes of kind
+    fused / two-stage exist only under a structure hint (diagonal W)."""
+    N = 1 << 17
+    own = {"small": {"small_kernel"}, "narrow": {"narrow_kernel"}, "rowwave-vi": {"vi_rowwave_kernel"},
+           "rowwave": {"gibbs_rowwave_kernel"}, "fused": {"fused_kernel"}}
+    estep_names = {"wide_estep_kernel", "estep_chunked_kernel"}
+    stats_names = {"wide_stats_kernel", "fused_kernel(statistics of a column group)", "label_stats_kernel"}
+    shapes = [("full", D, K) for D, K in ((2, 4), (2, 50), (3, 200), (12, 6), (8, 32), (9, 64), (16, 16), (20, 16), (20, 80), (24, 160))]
+    shapes += [("diag", 12, 32), ("diag", 20, 16), ("diag", 32, 100)]
+    rng = np.random.default_rng(5)
+    seen = set()
+    try:
+        for structure, D, K in shapes:
+            Z, c, b, W = _random_problem(rng, 4096, D, K)
+            if structure == "diag":
+                W = W * np.eye(D)
+            engine.set_structure(structure)
+            engine.upload(np.ascontiguousarray(np.tile(Z, (N // 4096, 1))))
+            for gibbs in (False, True):
+                p = engine.plan(K, gibbs=gibbs)
+                engine.profile(True)
+                engine.profile_read(reset=True)
+                if gibbs:
+                    engine.gibbs_labels(c, b, W, seed=3, sweep=1)
+                else:
+                    engine.estep(c, b, W)
+                prof = engine.profile_kernels()
+                engine.profile(False)
+                names, kind, where = set(prof), p["kind"], (structure, D, K, gibbs, p, prof)
+                print(structure, D, K, "labels" if gibbs else "softmax", kind, p["kernels_per_pass"], sorted(names))
+                seen.add((kind, gibbs))
+                if kind == "two-stage":
+                    assert len(names & estep_names) == 1 and len(names & stats_names) == 1 and len(names) == 2, where
+                    assert prof[(names & estep_names).pop()]["launches"] == 1, where
+                    continue
+                first = ({"mid_kernel (labels)"} if gibbs else {"mid_kernel"}) if kind == "mid" else own[kind]
+                behind = {"label_stats_kernel"} if gibbs and p["kernels_per_pass"] > 1 else set()
+                assert names == first | behind, where
+                assert all(v["launches"] == 1 for v in prof.values()), where
+    finally:
+        engine.profile(False)
+        engine.set_structure("full")
+    kinds = {"small", "narrow", "mid", "rowwave-vi", "rowwave", "fused", "two-stage"}
+    assert {k for k, _ in seen} == kinds and seen >= {(k, g) for k in kinds - {"rowwave-vi", "rowwave"} for g in (False, True)}, seen
+
+
 @pytest.mark.gpu
 def test_graft_entry_smoke_runs():
     """__graft_entry__.smoke() — what the driver runs on a fresh box before the bench — inside the suite: its routing assertions

@@ -532,7 +532,7 @@ int mimo_data_checksum(mimo_ctx* ctx, uint64_t out[2]);
  *   "resp_skip_log2" (per context, default 60) the mean-field pass on the fused kernel at Dz >= 14 leaves out of the statistics of a
  *                  16-component row block every datum whose 16 responsibilities there are all below tau = 2^-value; each
  *                  statistic moves by at most tau * sum_n |phi_nf|, the ELBO scalars not at all.  0: every weight enters.
- *   "sorted_range" (process-wide) cap on the 256-row tiles per range of label_stats_sorted_kernel (default and maximum 80;
+ *   "sorted_range" (process-wide) cap on the 256-row tiles per range of label_stats_gram_kernel (default and maximum 80;
  *                  0 restores it): with a low cap a workgroup takes several ranges ("first range writes, later ranges add").
  *   "mid_min_d", "mid_narrow_k" (process-wide) 0 / 0: the mid kernels (mimo_mid.hip) run where they measured fastest.  Otherwise
  *                  they take every shape they exist for with Dz >= mid_min_d (default 5; > 32: the route is off), and the narrow

@@ -605,15 +605,19 @@ static int timed_launch(mimo_ctx* ctx, const char* name, L&& launch) {
 // (a single launch under its profile name)
 #define TIMED_HIP(ctx, name, expr) timed_launch(ctx, name, [&]() -> int { HIP_TRY(ctx, expr); return MIMO_OK; })
 
-// buffers of the presorted tiles for a label-statistics pass of several launches (Dz >= 10: windows / feature slices)
+// buffers of the ranked tiles for a label-statistics pass of several launches (Dz = 10 .. 16: windows) or the one-pass kernel.
+// Tiles of 256 rows: label_tile_sort_kernel<256> writes, and label_stats_wide_kernel / label_stats_gram_kernel read, list entries
+// [256 t, 256 t + 256) and starts [257 t, 257 t + 256] of the tiles t < ceil(N / 256) and nothing else.
+// The one-pass kernel is the only route of its shapes, so it gets its buffers for an empty data set too (one tile nobody reads:
+// every workgroup then writes an all-zero block); the windowed launches rank their own tiles without them.
 static int prepare_label_presort(mimo_ctx* ctx, KernelArgs& a) {
   a.sort_list = nullptr; a.sort_start = nullptr;
-  if (ctx->structure != 0 || a.D < 10 || a.N < 1 ||
-      (label_stats_launches(a.K, a.D, ctx->structure) < 2 && !label_stats_sorted(a.K, a.D, ctx->structure))) return MIMO_OK;
-  const size_t tiles128 = (size_t)((a.N + 127) / 128);
+  if (ctx->structure != 0 || a.D < 10) return MIMO_OK;
+  if (!label_stats_sorted(a.K, a.D, ctx->structure) && (a.N < 1 || label_stats_launches(a.K, a.D, ctx->structure) < 2)) return MIMO_OK;
+  const size_t tiles = a.N < 1 ? 1 : (size_t)((a.N + 255) / 256);
   int rc;
-  if ((rc = ensure_dev(ctx, &ctx->sort_list, &ctx->sort_list_cap, tiles128 * 128 + 256))) return rc;
-  if ((rc = ensure_dev(ctx, &ctx->sort_start, &ctx->sort_start_cap, tiles128 * 257 + 257))) return rc;
+  if ((rc = ensure_dev(ctx, &ctx->sort_list, &ctx->sort_list_cap, tiles * 256))) return rc;
+  if ((rc = ensure_dev(ctx, &ctx->sort_start, &ctx->sort_start_cap, tiles * 257))) return rc;
   a.sort_list = ctx->sort_list; a.sort_start = ctx->sort_start;
   return MIMO_OK;
 }
@@ -1598,10 +1602,9 @@ static void plan_route(const mimo_ctx* ctx, const Route& route, const KernelArgs
   auto label_stage = [&]() {
     const int ll = label_stats_launches(K, D, ctx->structure);
     if (label_stats_uses_slots(K, D, a.N)) snprintf(lst, sizeof lst, "label_slots_kernel + label_stats_slots_kernel");
-    else if (ctx->structure == 0 && D >= 10 && label_stats_sorted(K, D, ctx->structure)) snprintf(lst, sizeof lst, "label_tile_sort_kernel + label_stats_sorted_kernel");
+    else if (label_stats_sorted(K, D, ctx->structure)) snprintf(lst, sizeof lst, "label_tile_sort_kernel + label_stats_gram_kernel");
     else if (ctx->structure != 0 || D <= 9) snprintf(lst, sizeof lst, "label_stats_kernel");
-    else if (D <= 16 && ll * 128 >= K && (K <= 64 || ll == (K + 127) / 128)) snprintf(lst, sizeof lst, "label_stats_wide_kernel x %d", ll);
-    else snprintf(lst, sizeof lst, "label_stats_xwide_kernel x %d", ll);
+    else snprintf(lst, sizeof lst, "label_stats_wide_kernel x %d", ll);
     return ll;
   };
   memset(out8, 0, 8 * sizeof(int64_t));

@@ -34,7 +34,7 @@ hipError_t launch_wide_stats(const KernelArgs& a, int grid, hipStream_t stream);
 bool wide_estep_covers(int K16, int D, int F16, int gibbs);
 hipError_t launch_wide_estep(const KernelArgs& a, int grid, hipStream_t stream);
 
-// label statistics (mimo_rowwave.hip): launches of one pass — 1, or the slice groups of the Dz > 16 / large-K kernel
+// label statistics (mimo_label_stats.hip): launches of one pass — 1, or the 128-component windows of label_stats_wide_kernel
 int label_stats_launches(int K, int D, int structure);
 bool label_stats_sorted(int K, int D, int structure);       // the one-pass kernel over the ranked tiles serves the shape (needs the presort buffers)
 void set_sorted_range_cap(int tiles);                        // tiles per range of the one-pass kernel at most (mimo_tune "sorted_range"; 0: default)

@@ -43,14 +43,14 @@ struct KernelArgs {
   int do_stats;
   int split;              // also accumulate sum_k r l (entropy split of the ELBO scalars)
   int64_t ntiles;
-  int cb0;                // statistics modes: first 16-wide feature column block of this launch (label_stats_xwide_kernel: first feature slice)
+  int cb0;                // statistics modes: first 16-wide feature column block of this launch
   int F16_total;          // padded feature count of the whole problem (partials row stride)
   int write_scalars;      // write the 4 scalar slots of the partial block (0: another launch owns them)
   int diag;               // feature table is a reduced one (diagonal: 2 Dz + 1, linear: Dz + 1 features): table-driven E-step kernels
   unsigned long long* stamps;  // diagnostic builds (-DMIMO_STAMPS) only: [grid][4 waves][8] phase cycle sums
   double theta_inline[40];  // small-shape kernel with one lane per row (G = 1): Theta itself (kThetaInline doubles at most)
   uint32_t* aux;          // label_stats_slots_kernel: label histogram + slot table (label_stats_aux_words() words)
-  uint16_t* sort_list;    // label_tile_sort_kernel -> label_stats_wide / _xwide_kernel: per tile the rows in component order, [ntiles][T]
+  uint16_t* sort_list;    // label_tile_sort_kernel -> label_stats_wide / _gram_kernel: per tile the rows in component order, [ntiles][T]
   uint16_t* sort_start;   // ... and the first list position of every component, [ntiles][257] (entry 256: rows in the list)
   int presort;            // the statistics launch reads sort_list / sort_start instead of ranking the tile's labels itself
   int k0;                 // label_stats_wide_kernel: first component of the launch's window (components k0 .. k0 + 127 of K > 128)
@@ -107,8 +107,9 @@ bool small_covers(int D, int K);
 int small_grid(const KernelArgs& a, int num_cu, int src);
 hipError_t launch_small(const KernelArgs& a, int src, int grid, hipStream_t stream, bool* unsupported);
 
-// Large-K Gibbs sweep (mimo_rowwave.hip): row-owner label kernel (Theta stationary in LDS, draw in registers) and
-// the label-indexed statistics kernel.  theta: [NS][KB][64] with the component permutation of rowwave_component().
+// Large-K Gibbs sweep: row-owner label kernel (mimo_rowwave.hip: Theta stationary in LDS, draw in registers) and the
+// label-indexed statistics kernels (mimo_label_stats.hip).  theta: [NS][KB][64] with the component permutation of rowwave_component().
+int rowwave_min_k();                              // smallest K of the row-owner route and of the label statistics (MIMO_ROWWAVE_MIN_K)
 size_t rowwave_lds_bytes(int KB, int NS, int ZS);
 int rowwave_kb(int K);
 int rowwave_kb_shape(int K, int F16, int ZS);     // ... for the shape (the streamed walk may take two more than rowwave_kb)

@@ -87,8 +87,8 @@ def test_full_size_properties_c4_ilr_softmax_pass(engine):
 
 
 def test_full_size_properties_one_pass_label_statistics(engine):
-    """label_stats_sorted_kernel at N = 1.2e7, Dz = 20, K = 96: 46 875 tiles on 512 workgroups need ranges of 92 tiles, the cap is
-    80, so 74 workgroups take a SECOND range (first range writes, later ranges add).  counts = bincount, sum_k moments = the
+    """label_stats_gram_kernel at N = 1.2e7, Dz = 20, K = 96: 46 875 tiles on 1024 workgroups need ranges of 46 tiles, the kernel's cap
+    at Dz = 20 is 40, so 148 workgroups take a SECOND range (first range writes, later ranges add).  counts = bincount, sum_k moments = the
     data's, one component against a direct sum, a second launch returns the same bits, halves add up."""
     N, D, K = 12_000_000, 20, 96
     rng = np.random.default_rng(13)
@@ -115,7 +115,7 @@ def test_full_size_properties_one_pass_label_statistics(engine):
 @pytest.mark.parametrize("ranges", [2, 3, 7])
 @pytest.mark.parametrize("D,K", [(20, 96), (32, 40), (17, 256)])
 def test_one_pass_label_statistics_over_several_ranges_per_workgroup(engine, D, K, ranges):
-    """label_stats_sorted_kernel with 8 workgroups (mimo_tune "num_cu" = 4) and the range cap lowered (mimo_tune "sorted_range") so
+    """label_stats_gram_kernel with 8 workgroups (mimo_tune "num_cu" = 4) and the range cap lowered (mimo_tune "sorted_range") so
     that every workgroup walks 2, 3 or 7 ranges: "first range writes, later ranges add", components that start in one range and
     go on in the next, components without a row in a workgroup's first range — against the oracle, bit-identical on a second
     launch, and through a whole Gibbs sweep (streamed label kernel in front)."""

@@ -696,7 +696,7 @@ def test_small_shape_kernel_structures(engine, D, K):
 @pytest.mark.parametrize("N", [1, 15, 4099, 8 * 256 * 16 * 3 + 7])
 def test_large_k_label_pass_and_label_statistics(engine, D, K, N):
     """The row-owner label kernel (Theta in LDS, draw in registers; every instantiation KB = 6..16) and the
-    label-indexed statistics kernel (bitmap + popcount ranks, ascending rows per component) of mimo_rowwave.hip against
+    label-indexed statistics kernel (bitmap + popcount ranks, ascending rows per component) of mimo_rowwave.hip / mimo_label_stats.hip against
     the oracle: labels bit-exact for host uniforms and the Philox stream, counts exact, statistics to 1e-11, identical bits
     on a second launch; also with every row on ONE component and on three components (long per-component lists)."""
     from oracle import mimo_oracle as O
@@ -733,8 +733,9 @@ def test_large_k_label_pass_and_label_statistics(engine, D, K, N):
                                  (16, 256), (12, 129), (31, 64), (23, 33)])
 @pytest.mark.parametrize("N", [1, 4099, 20011])
 def test_sliced_label_statistics(engine, D, K, N):
-    """Label-indexed statistics where one launch cannot hold a component's accumulators (Dz = 17 .. 32, and K > 64 at
-    Dz = 10 .. 16: label_stats_xwide_kernel, feature slices over several launches): after the label draw of the sweep
+    """Label-indexed statistics where one launch cannot hold a component's accumulators (Dz = 17 .. 32:
+    label_tile_sort_kernel + label_stats_gram_kernel, one pass; K > 64 at Dz = 10 .. 16: label_stats_wide_kernel, two feature
+    slices per component, windows of 128 components per launch; K > 128 from Dz = 15: the one-pass kernels again): after the label draw of the sweep
     and for caller-supplied labels, against the oracle — labels and counts exact, statistics to 1e-11, identical bits on
     a second launch, every row on one component / on three components."""
     from oracle import mimo_oracle as O

@@ -41,6 +41,6 @@ def test_baseline_and_example_shapes_keep_their_families():
     assert launches == 2 and zpasses == 2 and "gibbs_rowwave_kernel" in desc and "label_stats_slots_kernel" in desc
     assert "label_stats_kernel" in rt.route(lib, 8, 256, True, N=100_000)[3] and "slots" not in rt.route(lib, 8, 256, True, N=100_000)[3]
     # one-pass label statistics from Dz = 17, streamed label kernel where Theta does not fit LDS
-    assert "gibbs_stream_kernel" in rt.route(lib, 32, 128, True)[3] and "label_stats_sorted_kernel" in rt.route(lib, 32, 128, True)[3]
+    assert "gibbs_stream_kernel" in rt.route(lib, 32, 128, True)[3] and "label_stats_gram_kernel" in rt.route(lib, 32, 128, True)[3]
     # structured blocks: reduced maps on the same families
     assert rt.route(lib, 16, 64, False, structure=2)[0] == "narrow" and rt.route(lib, 32, 64, False, structure=1)[0] == "fused"

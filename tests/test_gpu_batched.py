@@ -5,15 +5,13 @@ import numpy as np
 import pytest
 from scipy.special import logsumexp
 
+from batched_checks import TOL, check_against, oracle, problems, qerr
 from conftest import load_golden
 from mimo_amd import _lib
 from mimo_amd.batched import BatchedHipEngine
 from mimo_amd.engine import HipEngine, _ptr
-from oracle import mimo_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-11
 
 
 @pytest.fixture(scope="module")
@@ -24,51 +22,6 @@ def beng():
 @pytest.fixture(scope="module")
 def solo():
     return HipEngine(0)
-
-
-def problems(rng, rows, D, K, off=True):
-    """Data and (c, b, W) of len(rows) problems; component 0 of every problem switched off (c = -inf) when `off`."""
-    B = len(rows)
-    Zs = [rng.standard_normal((n, D)) * 1.5 + rng.standard_normal(D) for n in rows]
-    A = rng.standard_normal((B, K, D, D))
-    W = A @ A.transpose(0, 1, 3, 2) / D + 0.3 * np.eye(D)
-    b = rng.standard_normal((B, K, D))
-    c = rng.standard_normal((B, K))
-    if off and K > 1:
-        c[:, 0] = -np.inf
-    return Zs, c, b, W
-
-
-def oracle(Z, c, b, W):
-    """(n, sx, sxx, scalars[3], lse) of one problem, naively."""
-    K, D = b.shape
-    if len(Z) == 0:
-        return np.zeros(K), np.zeros((K, D)), np.zeros((K, D, D)), np.zeros(3), np.zeros(0)
-    L = O.canonical_eval(Z, c, b, W)
-    lse = logsumexp(L, axis=0)
-    r = np.exp(L - lse)
-    n, sx, sxx = O.packed_stats(Z, r)
-    srl = np.sum(np.where(r > 0, r * np.where(np.isfinite(L), L, 0.), 0.))
-    return n, sx, sxx, np.array([lse.sum(), srl, lse.sum() - srl]), lse
-
-
-def qerr(a, ref, floor=1.0):
-    """Relative error of one quantity at its own scale (per component for the statistics), with an absolute floor."""
-    a, ref = np.asarray(a, dtype=float), np.asarray(ref, dtype=float)
-    if ref.size == 0:
-        return 0.0
-    if ref.ndim >= 2:          # per component k
-        ax = tuple(range(1, ref.ndim))
-        scale = np.maximum(np.abs(ref).max(axis=ax), floor)
-        return float((np.abs(a - ref).max(axis=ax) / scale).max())
-    return float((np.abs(a - ref) / np.maximum(np.abs(ref), floor)).max())
-
-
-def check_against(S, sc, lse, ref):
-    n, sx, sxx, scal, l = ref
-    errs = {"n": qerr(S.n[:, None], n[:, None]), "sx": qerr(S.sx, sx), "sxx": qerr(S.sxx, sxx),
-            "scalars": qerr(sc, scal), "lse": qerr(lse, l)}
-    assert max(errs.values()) <= TOL, errs
 
 
 CASES = [  # (rows, Dz, K)

@@ -10,6 +10,8 @@ import numpy as np
 import numpy.random as npr
 import pytest
 
+from batched_checks import TOL, check_stats, qerr
+from batched_checks import problems as random_problems
 from conftest import ROOT, load_golden, rel_err
 import model_checks as mc
 from mimo_amd import _lib
@@ -19,8 +21,6 @@ from mimo_amd.mixtures.batched import resample_batched
 from oracle import mimo_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-11
 
 
 @pytest.fixture(scope="module")
@@ -34,34 +34,8 @@ def solo():
 
 
 def problems(rng, rows, D, K):
-    """Data and (c, b, W) of len(rows) problems; component 1 of every problem switched off (c = -inf)."""
-    B = len(rows)
-    Zs = [rng.standard_normal((n, D)) * 1.5 + rng.standard_normal(D) for n in rows]
-    A = rng.standard_normal((B, K, D, D))
-    W = A @ A.transpose(0, 1, 3, 2) / D + 0.3 * np.eye(D)
-    b = rng.standard_normal((B, K, D))
-    c = rng.standard_normal((B, K))
-    if K > 2:
-        c[:, 1] = -np.inf
-    return Zs, c, b, W
-
-
-def qerr(a, ref):
-    """Largest error per component relative to that component's scale (floor 1)."""
-    a, ref = np.asarray(a, dtype=float), np.asarray(ref, dtype=float)
-    if ref.size == 0:
-        return 0.0
-    ax = tuple(range(1, ref.ndim))
-    scale = np.maximum(np.abs(ref).max(axis=ax), 1.0)
-    return float((np.abs(a - ref).max(axis=ax) / scale).max())
-
-
-def check_stats(S, Z, labels, K):
-    labels = np.asarray(labels, dtype=np.int64)
-    n, sx, sxx = O.packed_stats(Z, O.one_hot(labels, K)) if len(Z) else (np.zeros(K), 0 * S.sx, 0 * S.sxx)
-    assert np.array_equal(S.n, np.bincount(labels, minlength=K).astype(float))
-    assert np.array_equal(S.n, n)
-    assert qerr(S.sx, sx) <= TOL and qerr(S.sxx, sxx) <= TOL
+    """The shared random batch with component 1 of every problem switched off (c = -inf)."""
+    return random_problems(rng, rows, D, K, off=1)
 
 
 ROWS = [0, 1, 31, 33, 2500]

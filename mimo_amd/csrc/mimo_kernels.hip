@@ -559,40 +559,67 @@ void fused_kernel(const KernelArgs a) {
       // Soft responsibilities (SKIP): the rows of this wave's row block with a weight >= tau there (mask of the
       // normalise phase, wave-uniform: SGPRs) are contracted 4 at a time in ascending row order; lane (kk = q) takes
       // member q of the group, an empty slot repeats the group's first row with A = 0.  The rows left out hold weights
-      // < tau only; a tile with every row live costs the dense body's 8 steps.  Neither a dense fallback for full masks
-      // nor operands of the next group read ahead fit: both pushed this instantiation from 208 VGPRs into scratch
-      // (C2 shape: 4 and 23 - 138 spilled registers), so each group's LDS latency is left to the co-resident workgroup.
+      // < tau only; a tile with every row live costs the dense body's 8 steps.  The loop is pipelined without a second
+      // operand set (a dense fallback for full masks or double-buffered B operands pushed this instantiation from 208
+      // VGPRs into scratch: 4 and 23 - 138 spilled registers at the C2 shape).  An MFMA reads its sources when it issues,
+      // so each B register is refilled with the NEXT group's value by the LDS read right behind the MFMA that consumed it:
+      // the read for column block cb is covered by the NCB - cb MFMAs still to issue.  The next group's descriptor is
+      // scalar work done before the current group's MFMAs; the only new vector state is the next row's two offsets and
+      // the next A value (read after the first MFMA, selected at the group boundary).  The sched_barriers pin the
+      // MFMA / read pairs (hipcc would otherwise collect the reads behind the MFMAs, where nothing covers them); the last
+      // group (wave-uniform branch) issues its MFMAs alone.  Same groups, same order, one accumulator per column block:
+      // the sums are bit-equal to the unpipelined loop's.  Registers and scratch of the three instantiations, and what
+      // the loop gained: profiles/r06_c2_skip_refill.txt.
       auto stats_skip = [&](uint32_t mrow) {
         const double* ltc = Lt + (16 * wave + j);
         const double* phc = Ph + j;
-        double avq, bvq[NCB];
-        auto fetch = [&]() {
-          const int cnt = __builtin_popcount(mrow);   // (scalar) members left: the group takes min(cnt, 4)
+        // (scalar) descriptor of the next group: takes its (up to) 4 members off mrow; row = this lane's member
+        auto next_group = [&](int& row, int& cnt) {
+          cnt = __builtin_popcount(mrow);             // members left: the group takes min(cnt, 4)
+          // (the mask is opaque between each test and the decrement after it: hipcc otherwise folds the pair into a
+          // VALU subtract with borrow and a readfirstlane, a round trip through the pipe the MFMAs occupy)
+          auto drop = [&]() { asm volatile("" : "+s"(mrow)); mrow &= mrow - 1; };
           const uint32_t d0 = __builtin_ctz(mrow);
-          mrow &= mrow - 1;
+          drop();
           const uint32_t d1 = mrow ? __builtin_ctz(mrow) : d0;
-          mrow &= mrow - 1;
+          drop();
           const uint32_t d2 = mrow ? __builtin_ctz(mrow) : d0;
-          mrow &= mrow - 1;
+          drop();
           const uint32_t d3 = mrow ? __builtin_ctz(mrow) : d0;
-          mrow &= mrow - 1;
+          drop();
           const uint32_t packed = d0 | (d1 << 8) | (d2 << 16) | (d3 << 24);
-          const int row = (int)((packed >> (8 * q)) & 0xFFu);
-          const double v = ltc[row * LS];
-          avq = q < cnt ? v : 0.0;
+          row = (int)((packed >> (8 * q)) & 0xFFu);
+        };
+        if (!mrow) return;
+        int row, cnt;
+        next_group(row, cnt);
+        double bvq[NCB];
+        const double v0 = ltc[row * LS];
+        double avq = q < cnt ? v0 : 0.0;
+        {
           const double* pb = phc + row * RS;
 #pragma unroll
           for (int cb = 0; cb < NCB; ++cb) bvq[cb] = pb[16 * cb];
-        };
-        auto issue = [&]() {
-#pragma unroll
-          for (int cb = 0; cb < NCB; ++cb)
-            sacc[0][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(avq, bvq[cb], sacc[0][cb], 0, 0, 0);
-        };
-        while (mrow) {
-          fetch();
-          issue();
         }
+        while (mrow) {                                // (scalar) a group follows this one: refill while it issues
+          next_group(row, cnt);
+          int lt_off = row * LS, ph_off = row * RS;
+          asm volatile("" : "+v"(lt_off), "+v"(ph_off));   // offsets, not pointers (see above): one read per register
+          const double* pb = phc + ph_off;
+          double avn = 0.0;
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb) {
+            sacc[0][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(avq, bvq[cb], sacc[0][cb], 0, 0, 0);
+            if (cb == 0) avn = ltc[lt_off];
+            bvq[cb] = pb[16 * cb];
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          avq = q < cnt ? avn : 0.0;
+        }
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb)              // last group: nothing to refill
+          sacc[0][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(avq, bvq[cb], sacc[0][cb], 0, 0, 0);
       };
       if constexpr (MODE == kFastGibbs || MODE == kModeLabels) stats_labels();
       else if constexpr (MODE == kGeneric) { if (gibbs) stats_labels(); else stats_nact(std::false_type{}); }

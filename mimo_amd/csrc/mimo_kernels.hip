@@ -189,6 +189,13 @@ void fused_kernel(const KernelArgs a) {
   // fetched into registers while the current one is processed, so the HBM latency is off the
   // critical path (T*D <= 512 for the fused E-step modes, Dz <= 16; <= 1024 for the statistics modes).
   constexpr int ZPT = (SRC == kSrcEstep && DS > 0) ? 2 : 4;   // DS = 0: table-driven features, Dz up to 32
+  // TRIM: the select-free feature build (step 2, build_features_static) and the scalar-side staging below are compiled into the
+  // fast VI kernels that own a shape by default (one row block per wave, not split, Dz >= 10: C2, C4).  Elsewhere they are not
+  // free: they move the register allocation of instantiations that already spill (fast Gibbs and generic at Dz = 16: 108 -> 140
+  // and 348 -> 388 bytes of scratch) or that sit at an occupancy step (generic split at Dz = 14: 168 -> 170 VGPRs, three waves per
+  // SIMD -> two; the statistics modes: + 4 VGPRs).  Those keep the forms they had and their device code does not change;
+  // the ten TRIM instantiations keep their occupancy with 0 scratch (profiles/r07_c2_valu_trim.txt).
+  constexpr bool TRIM = MODE == kFastVI && DS >= 10 && RBW == 1 && SPLIT == 0;
   int zoff[ZPT];
 #pragma unroll
   for (int i = 0; i < ZPT; ++i) {
@@ -197,12 +204,39 @@ void fused_kernel(const KernelArgs a) {
     zoff[i] = e < T * D ? pt * ZS + (e - pt * D) : -1;
   }
   double zr[ZPT];
+  // TRIM: everything about a tile's place in Z is wave-uniform; only tid + kWG * i is per lane.  So the tile's first element and
+  // the number of elements it has in Z (T * D wherever the tile lies wholly inside N, 0 where it lies past the data, as the
+  // prefetches behind a workgroup's last tile do) are scalar work, and the only per-lane test is the 32-bit element index against
+  // that count — which is also what zoff[i] >= 0 says.  As t * T * D + tid + kWG * i < N * D per lane, address and bound
+  // were 64-bit VALU arithmetic on every tile (C2 kernel: v_mad_u64_u32, three v_lshl_add_u64, two v_cmp_gt_i64 and their
+  // moves, 11 VALU per load and 7 per store, now 5 and 5) in front of the prefetch's global loads.  Same elements loaded, same
+  // zeros stored.  Measured at C2: 4.5 VALU fewer and 22 SALU more per wave-tile, step - 0.05 ms on its own.
+  // clamp_scalar: min(max(x, 0), hi) of a wave-uniform 64-bit x as shifts and masks.  gfx950 has no scalar 64-bit ordered
+  // compare, and `x > 0 ? .. : ..` on SGPRs is compiled to v_cmp_*_i64, issue slots of the pipe this is meant to spare (the
+  // sign words are opaque, or LLVM turns the masks back into those compares).
+  auto clamp_scalar = [](int64_t x, const int hi) -> int {
+    int64_t y = x - hi, sg = y >> 63;
+    asm volatile("" : "+s"(sg));
+    y = (y & sg) + hi;
+    sg = y >> 63;
+    asm volatile("" : "+s"(sg));
+    return (int)(y & ~sg);
+  };
   auto load_z = [&](int64_t t) {
-    const int64_t base = t * T * D, total = N * D;
+    if constexpr (TRIM) {
+      const int64_t base = t * T * D;                           // (scalar)
+      const int lim = clamp_scalar(N * D - base, T * D);        // (scalar) elements of this tile that exist
+      const gptr_t zp = (gptr_t)a.Z + base;                     // (scalar; dereferenced only where lim > 0)
 #pragma unroll
-    for (int i = 0; i < ZPT; ++i) {
-      const int64_t g = base + tid + kWG * i;
-      zr[i] = (zoff[i] >= 0 && g < total) ? a.Z[g] : 0.0;
+      for (int i = 0; i < ZPT; ++i)                             // element tid + kWG * i: the kWG * i on the scalar side of both
+        zr[i] = tid < lim - kWG * i ? (zp + kWG * i)[(unsigned)tid] : 0.0;
+    } else {
+      const int64_t base = t * T * D, total = N * D;
+#pragma unroll
+      for (int i = 0; i < ZPT; ++i) {
+        const int64_t g = base + tid + kWG * i;
+        zr[i] = (zoff[i] >= 0 && g < total) ? a.Z[g] : 0.0;
+      }
     }
   };
   auto store_z = [&](int64_t t) {
@@ -210,7 +244,9 @@ void fused_kernel(const KernelArgs a) {
     for (int i = 0; i < ZPT; ++i)
       if (zoff[i] >= 0) Zs[zoff[i]] = zr[i];
     if (tid < T) {
-      Zs[tid * ZS + D] = (t * T + tid) < N ? 1.0 : 0.0;  // rows past N contribute nothing
+      // rows past N contribute nothing (TRIM: the rows of this tile that exist, on the scalar side)
+      if constexpr (TRIM) Zs[tid * ZS + D] = tid < clamp_scalar(N - t * T, T) ? 1.0 : 0.0;
+      else Zs[tid * ZS + D] = (t * T + tid) < N ? 1.0 : 0.0;
       Zs[tid * ZS + D + 1] = 0.0;                        // padded features read this slot
     }
   };
@@ -255,20 +291,23 @@ void fused_kernel(const KernelArgs a) {
     // per 64-cycle MFMA.
     __builtin_amdgcn_s_setprio(2);
     if constexpr (DS > 0) {
-      // compile-time feature map: the z~ row goes to registers once, every product has static operands
-      double zl[DS + 2];
+      // compile-time feature map: the z~ row goes to registers once, every product has static operands.  zb is the same row
+      // read one element further on in the upper half of the wave (build_features_static; z~[D + 1] is the zero slot, so
+      // the last read stays inside the row: ZS >= D + 2); the elements a wave's features do not use are never read.
+      double zl[DS + 2], zb[DS + 1];
       const double* zrow = Zs + frow * ZS;
+      const double* zrowb = zrow + (lane >> 5);
 #pragma unroll
-      for (int d = 0; d <= DS; ++d) zl[d] = zrow[d];
+      for (int d = 0; d <= DS; ++d) { zl[d] = zrow[d]; zb[d] = TRIM ? zrowb[d] : 0.0; }
       zl[DS + 1] = 0.0;
       double* prow = Ph + frow * RS + (lane >> 5);
       constexpr int FW = 4 * NCB;
       using Seq = std::make_integer_sequence<int, FW / 2>;
       switch (wave) {   // scalar: no divergence
-        case 0: build_features_static<DS, FW, 0>(zl, prow, (lane >> 5) != 0, Seq{}); break;
-        case 1: build_features_static<DS, FW, 1>(zl, prow, (lane >> 5) != 0, Seq{}); break;
-        case 2: build_features_static<DS, FW, 2>(zl, prow, (lane >> 5) != 0, Seq{}); break;
-        default: build_features_static<DS, FW, 3>(zl, prow, (lane >> 5) != 0, Seq{}); break;
+        case 0: build_features_static<DS, FW, 0, TRIM>(zl, zb, prow, (lane >> 5) != 0, Seq{}); break;
+        case 1: build_features_static<DS, FW, 1, TRIM>(zl, zb, prow, (lane >> 5) != 0, Seq{}); break;
+        case 2: build_features_static<DS, FW, 2, TRIM>(zl, zb, prow, (lane >> 5) != 0, Seq{}); break;
+        default: build_features_static<DS, FW, 3, TRIM>(zl, zb, prow, (lane >> 5) != 0, Seq{}); break;
       }
     } else {
       const double* zrow = Zs + frow * ZS;

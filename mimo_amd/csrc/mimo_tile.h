@@ -77,12 +77,28 @@ struct FeatAB {
   static constexpr int b = pad ? D + 1 : a + (F - base_of(a));
 };
 
-// lane (row = lane & 31, parity = lane >> 5) of wave W writes features W*FW + 2i + parity, i < FW/2
-template <int D, int FW, int W, int... I>
-__device__ __forceinline__ void build_features_static(const double (&z)[D + 2], double* __restrict__ prow,
-                                                      const bool parity, std::integer_sequence<int, I...>) {
-  ((prow[W * FW + 2 * I] = (parity ? z[FeatAB<D, W * FW + 2 * I + 1>::a] : z[FeatAB<D, W * FW + 2 * I>::a]) *
-                           (parity ? z[FeatAB<D, W * FW + 2 * I + 1>::b] : z[FeatAB<D, W * FW + 2 * I>::b])),
+// lane (row = lane & 31, parity = lane >> 5) of wave W writes features W*FW + 2i + parity, i < FW/2.
+// ZB: the two parities of a pair almost always differ by one position of ONE operand (same a, b + 1), so the parity rides on
+// an LDS address instead of a per-lane select: zl[d] = z~[d] for both halves of the wave, zb[d] = z~[d + parity] (the same row
+// read 8 bytes further on in the upper half; zb[D] is z~[D] or the zero slot).  An operand whose index is the same for both
+// features comes from zl, one that steps by one from zb: static registers, no v_cndmask.  Only the pairs that straddle the
+// end of a triangle row — (a, D) beside (a+1, a+1), 8 of the 77 pairs at Dz = 16 — keep a select, for their b operand
+// alone (the a operand steps by one).  A select between z~[i] and z~[j] is two v_cndmask_b32: 101 of them beside the 77
+// products of the Dz = 16 kernel, 17 now; 20 VALU fewer per wave-tile at C2 (profiles/r07_c2_valu_trim.txt).  The factors of
+// every product are the doubles they were.  !ZB (the instantiations fused_kernel leaves as they were): both operands selected.
+template <int D, int I0, int I1, bool ZB>
+__device__ __forceinline__ double feature_operand(const double (&zl)[D + 2], const double (&zb)[D + 1], const bool parity) {
+  if constexpr (I1 == I0) return zl[I0];
+  else if constexpr (ZB && I1 == I0 + 1 && I0 <= D) return zb[I0];
+  else return parity ? zl[I1] : zl[I0];
+}
+template <int D, int FW, int W, bool ZB, int... I>
+__device__ __forceinline__ void build_features_static(const double (&zl)[D + 2], const double (&zb)[D + 1],
+                                                      double* __restrict__ prow, const bool parity,
+                                                      std::integer_sequence<int, I...>) {
+  ((prow[W * FW + 2 * I] =
+        feature_operand<D, FeatAB<D, W * FW + 2 * I>::a, FeatAB<D, W * FW + 2 * I + 1>::a, ZB>(zl, zb, parity) *
+        feature_operand<D, FeatAB<D, W * FW + 2 * I>::b, FeatAB<D, W * FW + 2 * I + 1>::b, ZB>(zl, zb, parity)),
    ...);
 }
 
@@ -127,29 +143,42 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
           for (int c = 0; c < 8; ++c)
             if (c < CPP && k0 + c < K) out_logp[(int64_t)(k0 + c) * N + n] = x[c];
         }
-        double m = tree_max8(x);
-        m = fmax(m, __shfl_xor(m, 8));
+        const double ml = tree_max8(x);     // the lane's own maximum (SKIP, FULL: kept for the live mask)
+        double m = fmax(ml, __shfl_xor(ml, 8));
         m = fmax(m, __shfl_xor(m, 16));
         m = fmax(m, __shfl_xor(m, 32));
 
         if constexpr (SKIP) {
-          // bit b of lb: one of this lane's slots in row block b is live (masked slots hold -inf: never live).
-          // FULL: the lane's 8 slots lie in one row block (part >> 1); else 2*K16 < 8 slots may straddle two.
-          uint32_t lb = 0;
+          uint32_t bytes = 0;               // byte b: the live rows of this wave in row block b
+          if constexpr (FULL) {
+            // The lane's 8 slots lie in one row block (part >> 1), and x -> fl(x - m) is monotone, so "one of the slots
+            // has l - m >= lnt" is exactly ml - m >= lnt: one subtract and one compare instead of eight of each with
+            // their selects, and ONE ballot holds all four row blocks — lanes 16 b .. 16 b + 15 are the two parts of
+            // block b, rows 8 wave + (0 .. 7) each; the OR of the two bytes is scalar work.  Same decisions, same masks;
+            // 23 VALU fewer per wave-tile at C2 (profiles/r07_c2_valu_trim.txt).  (The builtin takes the predicate as it
+            // is: __ballot() goes through an int, a v_cndmask and a v_cmp_ne of their own.)
+            const uint64_t bal = __builtin_amdgcn_ballot_w64(valid && ml - m >= lnt);
 #pragma unroll
-          for (int c = 0; c < 8; ++c)
-            if (ok(c) && x[c] - m >= lnt) lb |= FULL ? 1u << (part >> 1) : 1u << ((k0 + c) >> 4);
-          if (!valid) lb = 0;
-          // per row block: ballot over the wave (bit 8 part + i: row 8 wave + i), OR over the 8 parts -> one byte
-          uint32_t bytes = 0;
+            for (int b = 0; b < 4; ++b)
+              bytes |= (uint32_t)(((bal >> (16 * b)) | (bal >> (16 * b + 8))) & 0xFFu) << (8 * b);
+          } else {
+            // 2*K16 < 8 slots may straddle two row blocks: per slot.  Bit b of lb: one of this lane's slots in row block
+            // b is live (masked slots hold -inf: never live).
+            uint32_t lb = 0;
 #pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            if (b < K16) {
-              const uint64_t bal = __ballot((lb >> b) & 1u);
-              uint32_t v = (uint32_t)bal | (uint32_t)(bal >> 32);
-              v |= v >> 16;
-              v |= v >> 8;
-              bytes |= (v & 0xFFu) << (8 * b);
+            for (int c = 0; c < 8; ++c)
+              if (ok(c) && x[c] - m >= lnt) lb |= 1u << ((k0 + c) >> 4);
+            if (!valid) lb = 0;
+            // per row block: ballot over the wave (bit 8 part + i: row 8 wave + i), OR over the 8 parts -> one byte
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+              if (b < K16) {
+                const uint64_t bal = __ballot((lb >> b) & 1u);
+                uint32_t v = (uint32_t)bal | (uint32_t)(bal >> 32);
+                v |= v >> 16;
+                v |= v >> 8;
+                bytes |= (v & 0xFFu) << (8 * b);
+              }
             }
           }
           if (lane < K16) reinterpret_cast<uint8_t*>(live)[4 * lane + wave] = (uint8_t)(bytes >> (8 * lane));

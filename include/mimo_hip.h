@@ -493,6 +493,12 @@ int mimo_profile_read(mimo_ctx* ctx, double* kernel_ms, int64_t* launches, int r
  * its sustained leg. */
 int mimo_shader_clock_mhz(mimo_ctx* ctx, double* mhz);
 
+/* Device self-test of the in-register lane exchanges the kernels' per-datum reductions use (DPP rotations and permlane swaps,
+ * mimo_device.h): one wave runs each of them next to the same butterfly stage written with __shfl_xor, on per-lane-distinct
+ * doubles (-inf, -1e300, denormals and both zeros among them) and ints; *mismatches = lanes x checks whose bits differ (0 on a
+ * correct build).  No reference counterpart. */
+int mimo_lane_exchange_selftest(mimo_ctx* ctx, int* mismatches);
+
 /* Per-kernel breakdown of the same measurement: one text line "name<TAB>total_ms<TAB>launches" per kernel of the
  * passes since the last reset (mimo_profile_read with reset = 1 clears it). */
 int mimo_profile_kernels(mimo_ctx* ctx, char* buf, int len);

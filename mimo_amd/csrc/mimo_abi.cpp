@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -1468,6 +1469,40 @@ int mimo_shader_clock_mhz(mimo_ctx* ctx, double* mhz) {
     if (v.empty()) return fail(ctx, MIMO_E_HIP, "mimo_shader_clock_mhz: no samples");
     std::sort(v.begin(), v.end());
     *mhz = v[v.size() / 2];
+    return MIMO_OK;
+  });
+}
+
+int mimo_lane_exchange_selftest(mimo_ctx* ctx, int* mismatches) {
+  return guarded(ctx, [&]() -> int {
+    int rc = bind(ctx); if (rc) return rc;
+    if (!mismatches) return fail(ctx, MIMO_E_INVALID, "mimo_lane_exchange_selftest: out is NULL");
+    if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
+    // round 0: distinct ordinary values; round 4: +0 in lanes of even bit count, -0 in the others, so that every mask pairs the two
+    // zeros in both operand orders (the swaps hand the upper half its operands the other way round); rounds 1 .. 3: the values the kernels' reductions meet at their edges (-inf of masked slots,
+    // -1e300 of padding components, the clamp of the exponential, denormals, both zeros), permuted so that every mask pairs unequal lanes
+    const double inf = std::numeric_limits<double>::infinity(), den = std::numeric_limits<double>::denorm_min();
+    const double special[] = {-inf, -1e300, den, -den, 0.0, -0.0, 1.0, -707.0, 8e-308, 1.1e-308, -1.1e-308, 3.5, -inf, 0x1p-1074 * 5, -1e-300, 64.0, -0.0};
+    constexpr int NS = (int)(sizeof special / sizeof special[0]), R = 5;
+    std::vector<double> v(64 * R);
+    std::vector<int> iv(64 * R);
+    for (int r = 0; r < R; ++r)
+      for (int l = 0; l < 64; ++l) {
+        v[64 * r + l] = r == 0 ? 1.37 * l - 20.5 + 1e-9 * l * l : r == 4 ? (__builtin_popcount(l) & 1 ? -0.0 : 0.0) : special[(l * (2 * r + 5) + 3 * r) % NS];
+        iv[64 * r + l] = r == 0 ? l : (int)(2654435761u * (unsigned)(64 * r + l + 1)) >> (r == 1 ? 3 : 8);      // (sums of two stay inside int)
+      }
+    if ((rc = ensure_dev(ctx, &ctx->partials, &ctx->partials_cap, (size_t)64 * R + 32 * R + 1))) return rc;
+    double* dv = ctx->partials;
+    int* div = reinterpret_cast<int*>(dv + 64 * R);
+    unsigned int* dout = reinterpret_cast<unsigned int*>(dv + 64 * R + 32 * R);
+    HIP_TRY(ctx, hipMemcpyAsync(dv, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(div, iv.data(), iv.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(dout, 0, sizeof(double), ctx->stream));
+    HIP_TRY(ctx, launch_lane_exchange_selftest(dv, div, R, dout, ctx->stream));
+    unsigned int h = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&h, dout, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *mismatches = (int)h;
     return MIMO_OK;
   });
 }

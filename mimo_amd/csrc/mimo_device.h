@@ -51,6 +51,79 @@ __host__ __device__ inline double philox_uniform(uint64_t seed, uint64_t row, ui
   return ((double)(c0 >> 5) * 67108864.0 + (double)(c1 >> 6)) * (1.0 / 9007199254740992.0);
 }
 
+// ------------------------------------------------------------------------------------------
+// Lane exchanges with a compile-time XOR mask, in registers.  __shfl_xor(v, MASK) is ds_bpermute_b32 per 32-bit word:
+// a per-lane address (v_xor, v_cmp, v_cndmask, v_lshlrev) and a round trip through the LDS pipe, queued behind the
+// co-resident wave's MFMA operand reads, with s_waitcnt lgkmcnt(0) behind it.  A butterfly reduction needs neither:
+//   MASK 1, 2   DPP quad_perm;   MASK 4   DPP row_shr:4 into banks 1, 3 and row_shl:4 into banks 0, 2;
+//   MASK 8      DPP row_ror:8 (rotation by half a row of 16 lanes = lane ^ 8);
+//   MASK 16, 32 v_permlane16_swap / v_permlane32_swap, which are HALF exchanges: the odd rows (upper half) of the first
+//               operand trade places with the even rows (lower half) of the second.  With both operands a copy of v, one
+//               result then holds the lane's own value and the other its partner's — which of the two depends on the
+//               lane, and a commutative op(a, b) does not care: no select.
+// lane_xor_pair returns {a, b} = {v, v of lane ^ MASK} in lane-dependent order; lane_xor_max / lane_xor_sum return
+// op(v, v of lane ^ MASK), bit for bit what op(v, __shfl_xor(v, MASK)) returns (max and + are commutative, signed zeros
+// included: v_max_f64 orders -0 < +0 whichever operand holds which).  All 64 lanes must be active.
+// ------------------------------------------------------------------------------------------
+struct LanePair { int a, b; };
+template <int MASK>
+__device__ __forceinline__ LanePair lane_xor_pair(int v) {
+  static_assert(MASK == 1 || MASK == 2 || MASK == 4 || MASK == 8 || MASK == 16 || MASK == 32, "one bit of a wave64 lane index");
+  if constexpr (MASK == 32) {
+    const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    return {(int)r[0], (int)r[1]};
+  } else if constexpr (MASK == 16) {
+    const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+    return {(int)r[0], (int)r[1]};
+  } else if constexpr (MASK == 8) {
+    return {v, __builtin_amdgcn_update_dpp(v, v, 0x128 /* row_ror:8 */, 0xf, 0xf, false)};
+  } else if constexpr (MASK == 4) {
+    const int up = __builtin_amdgcn_update_dpp(v, v, 0x114 /* row_shr:4 */, 0xf, 0xa, false);     // lanes 4-7, 12-15 <- lane - 4
+    return {v, __builtin_amdgcn_update_dpp(up, v, 0x104 /* row_shl:4 */, 0xf, 0x5, false)};       // lanes 0-3, 8-11  <- lane + 4
+  } else {
+    return {v, __builtin_amdgcn_update_dpp(v, v, MASK == 1 ? 0xb1 /* quad_perm:[1,0,3,2] */ : 0x4e /* [2,3,0,1] */, 0xf, 0xf, false)};
+  }
+}
+template <int MASK>
+__device__ __forceinline__ double lane_xor_max(double v) {
+  const LanePair lo = lane_xor_pair<MASK>(__double2loint(v)), hi = lane_xor_pair<MASK>(__double2hiint(v));
+  return fmax(__hiloint2double(hi.a, lo.a), __hiloint2double(hi.b, lo.b));
+}
+template <int MASK>
+__device__ __forceinline__ double lane_xor_sum(double v) {
+  const LanePair lo = lane_xor_pair<MASK>(__double2loint(v)), hi = lane_xor_pair<MASK>(__double2hiint(v));
+  return __hiloint2double(hi.a, lo.a) + __hiloint2double(hi.b, lo.b);
+}
+template <int MASK>
+__device__ __forceinline__ int lane_xor_sum(int v) {
+  const LanePair p = lane_xor_pair<MASK>(v);
+  return p.a + p.b;
+}
+// One stage of a butterfly with the exchange chosen at compile time (REG: in registers, else __shfl_xor): kernels whose
+// register allocation the register form would move for the worse keep the form they had, same bits either way.
+template <bool REG, int MASK, typename T>
+__device__ __forceinline__ T butterfly_sum(T v) {
+  if constexpr (REG) return lane_xor_sum<MASK>(v);
+  else return v + __shfl_xor(v, MASK);
+}
+template <bool REG, int MASK>
+__device__ __forceinline__ double butterfly_max(double v) {
+  if constexpr (REG) return lane_xor_max<MASK>(v);
+  else return fmax(v, __shfl_xor(v, MASK));
+}
+
+// ... and the whole butterfly over the G adjacent lanes of a group, stages 1, 2, .. G / 2 (G a power of two)
+template <bool REG, int G, int S = 1, typename T>
+__device__ __forceinline__ T group_sum(T v) {
+  if constexpr (S < G) return group_sum<REG, G, 2 * S>(butterfly_sum<REG, S>(v));
+  else return v;
+}
+template <bool REG, int G, int S = 1>
+__device__ __forceinline__ double group_max(double v) {
+  if constexpr (S < G) return group_max<REG, G, 2 * S>(butterfly_max<REG, S>(v));
+  else return v;
+}
+
 __device__ inline double wave_sum(double v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);

@@ -25,6 +25,9 @@ hipError_t launch_gather_columns(const double* table, int K, int64_t N, const in
 // shader clock under float64 load (mimo_small.hip): out[2 g] = shader-clock ticks, out[2 g + 1] = 100 MHz ticks of workgroup g
 hipError_t launch_clock_probe(unsigned long long* out, int grid, int iters, hipStream_t stream);
 
+// in-register lane exchanges against __shfl_xor on one wave (mimo_small.hip): out[0] += mismatching lanes x checks over `rounds` sets of 64 values
+hipError_t launch_lane_exchange_selftest(const double* vals, const int* ivals, int rounds, unsigned int* out, hipStream_t stream);
+
 // wide shapes (Dz > 16), statistics of a K-major weight table: one 8-wave workgroup per CU (mimo_wide.hip)
 bool wide_stats_covers(int K16, int D);
 int wide_stats_group_ncb(int K16, int ncb_total);     // feature column blocks per launch

@@ -85,6 +85,23 @@ double philox_uniform_host(uint64_t seed, uint64_t row, uint64_t sweep) {
 #endif
 // SKIP (fast VI, one row block per wave, not split, Dz >= 14; launched when KernelArgs::resp_skip > 0): the statistics of a
 // row block contract only the rows with a weight >= 2^-resp_skip in it (step 5).
+// The per-datum reductions of the normalise phase exchange lanes in registers (lane_xor_max / lane_xor_sum, mimo_device.h)
+// instead of through ds_bpermute — in every instantiation but the twelve below, whose register allocation the register form
+// moves for the worse (more VGPRs or scratch, or an occupancy step: fast VI at Dz = 7, 8 went from four workgroups per CU to
+// three; profiles/r08_c2_lane_exchange.txt).  Those keep __shfl_xor and their device code; the bits are the same either way.
+// Rows: {NCB, RBW, MODE, DS, SPLIT} as in the template parameters of fused_kernel (none of them a SKIP instantiation).
+// The list records what this toolchain's register allocator did.  To regenerate it after a compiler update: make this function
+// return true, compare `make resources` (VGPRs, scratch, occupancy per kernel) with the output of the same target on a tree where it
+// returns false, and list the instantiations that came out worse.  The same goes for the lists in mimo_mid.hip, mimo_rowwave.hip
+// and mimo_small.hip.
+constexpr bool fused_lane_regs(int NCB, int RBW, int MODE, int DS, int SPLIT, bool SKIP) {
+  constexpr int keep_shfl[][5] = {{2, 4, 2, 5, 0}, {2, 4, 2, 6, 0}, {3, 1, 0, 7, 0}, {3, 1, 0, 8, 0}, {3, 2, 2, 0, 0}, {3, 2, 2, 7, 0},
+                                  {3, 2, 2, 8, 0}, {3, 4, 0, 0, 0}, {3, 4, 0, 7, 0}, {3, 4, 1, 7, 0}, {3, 4, 1, 8, 0}, {5, 2, 1, 0, 0}};
+  for (const auto& k : keep_shfl)
+    if (!SKIP && NCB == k[0] && RBW == k[1] && MODE == k[2] && DS == k[3] && SPLIT == k[4]) return false;
+  return true;
+}
+
 template <int NCB, int RBW, int MODE, int DS = 0, int SPLIT = 0, bool SKIP = false>
 __global__ __launch_bounds__(kWG, (RBW == 1 ? 2 : (MODE <= kGeneric && RBW == 2) ? 2 : (MODE <= kGeneric && NCB <= 3) ? MIMO_RBW4_ESTEP_WGS
                                    : (MODE > kGeneric && RBW * NCB <= 12) ? 2 : 1))
@@ -196,6 +213,7 @@ void fused_kernel(const KernelArgs a) {
   // SIMD -> two; the statistics modes: + 4 VGPRs).  Those keep the forms they had and their device code does not change;
   // the ten TRIM instantiations keep their occupancy with 0 scratch (profiles/r07_c2_valu_trim.txt).
   constexpr bool TRIM = MODE == kFastVI && DS >= 10 && RBW == 1 && SPLIT == 0;
+  constexpr bool LX = fused_lane_regs(NCB, RBW, MODE, DS, SPLIT, SKIP);
   int zoff[ZPT];
 #pragma unroll
   for (int i = 0; i < ZPT; ++i) {
@@ -441,11 +459,11 @@ void fused_kernel(const KernelArgs a) {
       // ---- 4. normalise over k: 8 lanes per datum, 2*K16 consecutive components per lane ----------
       __builtin_amdgcn_s_setprio(2);
       if constexpr (RBW == 1)
-        normalise_tile<RBW, MODE, E2K, SKIP>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
+        normalise_tile<RBW, MODE, E2K, SKIP, LX>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
                                              out_lse, sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T, lnt,
                                              live);
       else
-        normalise_tile_chunked<RBW, MODE>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
+        normalise_tile_chunked<RBW, MODE, LX>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
                                           out_lse, sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T);
       if constexpr (MODE != kGeneric) {
         if (++prod_tiles == 64) {   // K^64 <= 256^64 = 2^512 stays inside the float64 range
@@ -926,10 +944,10 @@ __global__ __launch_bounds__(kWG, (RBW <= 2 ? 2 : 1)) void estep_chunked_kernel(
     STAMP(6);
     __builtin_amdgcn_s_setprio(2);
     if constexpr (RBW == 1)
-      normalise_tile<RBW, kGeneric>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, a.logp, a.resp, a.lse,
+      normalise_tile<RBW, kGeneric, false, false, true>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, a.logp, a.resp, a.lse,
                                     sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T);
     else
-      normalise_tile_chunked<RBW, kGeneric>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, a.logp, a.resp,
+      normalise_tile_chunked<RBW, kGeneric, true>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, a.logp, a.resp,
                                             a.lse, sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T);
     MFMA_PRIO();
     STAMP(7);

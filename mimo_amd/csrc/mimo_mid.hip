@@ -23,6 +23,16 @@
 #include "mimo_narrow_kernel.h"      // NarrowGroup, narrow_group_steps, narrow_group_pos
 
 namespace mimo {
+// Lane exchanges of the softmax / label draw in registers (mimo_device.h), but for the twelve instantiations {DT, KB, NW} of the
+// softmax mode that it costs VGPRs or scratch (profiles/r08_c2_lane_exchange.txt): those keep __shfl_xor, same bits.
+// (List from a `make resources` comparison of both forms: see fused_lane_regs in mimo_kernels.hip for how to regenerate it.)
+constexpr bool mid_lane_regs(int DT, int KB, int NW, int MODE) {
+  constexpr int keep_shfl[][3] = {{5, 2, 4}, {9, 3, 4}, {9, 7, 4}, {13, 2, 4}, {13, 5, 8}, {13, 7, 8},
+                                  {14, 5, 8}, {14, 6, 8}, {14, 7, 8}, {15, 5, 8}, {16, 5, 8}, {31, 2, 8}};
+  for (const auto& k : keep_shfl)
+    if (MODE == 0 && DT == k[0] && KB == k[1] && NW == k[2]) return false;
+  return true;
+}
 
 constexpr int kMidPF = 8;                                        // Theta slices in flight per wave
 constexpr int mid_zs(int D) { return (D + 4) | 1; }              // row stride: z, 1, three zero slots; odd
@@ -54,6 +64,7 @@ constexpr size_t mid_lds_bytes(int D, int KB) { return mid_nbuf(D, KB) * mid_til
 template <int DT, int KB, int NW, int MODE = 0>
 __global__ __launch_bounds__(64 * NW, MODE == 1 ? 2 : mid_wgs_per_cu(DT, KB)) void mid_kernel(const KernelArgs a) {
   constexpr int PF = (MODE == 0 && mid_big(DT, KB)) ? 16 : kMidPF;
+  constexpr bool LX = mid_lane_regs(DT, KB, NW, MODE);
   constexpr NarrowGroup<DT> GR{};
   constexpr int NSG = narrow_group_steps(DT);
   constexpr int NCB = mid_ncb(DT), NCBW = (NCB + NW - 1) / NW;
@@ -172,8 +183,8 @@ __global__ __launch_bounds__(64 * NW, MODE == 1 ? 2 : mid_wgs_per_cu(DT, KB)) vo
 #pragma unroll
         for (int r = 0; r < 4; ++r) mv[r] = fmax(mv[r], acc[rb][r]);
       m = fmax(fmax(mv[0], mv[1]), fmax(mv[2], mv[3]));
-      m = fmax(m, __shfl_xor(m, 16));
-      m = fmax(m, __shfl_xor(m, 32));
+      m = butterfly_max<LX, 16>(m);
+      m = butterfly_max<LX, 32>(m);
     }
     if constexpr (MODE == 1) {
       // inclusive cumulative sums of e = exp(l - max) over the lane's quarter (component q V + 4 rb + r sits in acc[rb][r]), then over
@@ -201,8 +212,8 @@ __global__ __launch_bounds__(64 * NW, MODE == 1 ? 2 : mid_wgs_per_cu(DT, KB)) vo
       for (int rb = 0; rb < KB; ++rb)
 #pragma unroll
         for (int r = 0; r < 4; ++r) cnt += tl > acc[rb][r] ? 1 : 0;
-      cnt += __shfl_xor(cnt, 16);
-      cnt += __shfl_xor(cnt, 32);
+      cnt = butterfly_sum<LX, 16>(cnt);
+      cnt = butterfly_sum<LX, 32>(cnt);
       if (q == 0 && valid) a.labels[n] = cnt < K ? cnt : K - 1;
       __builtin_amdgcn_s_setprio(0);
       continue;
@@ -216,8 +227,8 @@ __global__ __launch_bounds__(64 * NW, MODE == 1 ? 2 : mid_wgs_per_cu(DT, KB)) vo
         sv[r] += acc[rb][r];
       }
     double ssum = (sv[0] + sv[1]) + (sv[2] + sv[3]);
-    ssum += __shfl_xor(ssum, 16);
-    ssum += __shfl_xor(ssum, 32);
+    ssum = butterfly_sum<LX, 16>(ssum);
+    ssum = butterfly_sum<LX, 32>(ssum);
     double inv = __builtin_amdgcn_rcp(ssum);
     inv = fma(fma(-ssum, inv, 1.0), inv, inv);
     inv = fma(fma(-ssum, inv, 1.0), inv, inv);

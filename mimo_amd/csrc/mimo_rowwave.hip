@@ -28,6 +28,12 @@
 #include <type_traits>
 
 namespace mimo {
+// Lane exchanges of the per-row reductions in registers (mimo_device.h) — but for the instantiations {KB, NS4} the register form
+// costs an occupancy step (label kernel: 168 -> 170 VGPRs, three workgroups' worth of waves -> two) or VGPRs (softmax kernel):
+// those keep __shfl_xor, same bits (profiles/r08_c2_lane_exchange.txt).  No instantiation of the streamed label kernel moves.
+// (Lists from a `make resources` comparison of both forms: see fused_lane_regs in mimo_kernels.hip for how to regenerate them.)
+constexpr bool gibbs_rowwave_lane_regs(int KB, int NS4) { return !((KB == 4 && NS4 == 9) || (KB == 6 && NS4 == 6) || (KB == 8 && NS4 == 5)); }
+constexpr bool vi_rowwave_lane_regs(int KB, int NS4) { return !((KB == 2 && NS4 == 1) || (KB == 4 && NS4 == 3)); }
 
 // ------------------------------------------------------------------------------------------
 // Label pass.  KB = row blocks (16 components each) the accumulators cover; K <= 16 KB.
@@ -162,8 +168,8 @@ __global__ __launch_bounds__(kRowWaveWG, 1) void gibbs_rowwave_kernel(const Kern
 #pragma unroll
         for (int r = 0; r < 4; ++r) mv[r] = fmax(mv[r], acc[rb][r]);
       m = fmax(fmax(mv[0], mv[1]), fmax(mv[2], mv[3]));
-      m = fmax(m, __shfl_xor(m, 16));
-      m = fmax(m, __shfl_xor(m, 32));
+      m = butterfly_max<gibbs_rowwave_lane_regs(KB, NS4), 16>(m);
+      m = butterfly_max<gibbs_rowwave_lane_regs(KB, NS4), 32>(m);
     }
     // e = exp(l - max), then inclusive cumulative sums inside chunks of 8 (independent chains across the chunks)
     double base[NCH + 1];
@@ -208,8 +214,8 @@ __global__ __launch_bounds__(kRowWaveWG, 1) void gibbs_rowwave_kernel(const Kern
 #pragma unroll
       for (int i = 0; i < 8; ++i) cnt += tc > acc[2 * c + (i >> 2)][i & 3] ? 1 : 0;
     }
-    cnt += __shfl_xor(cnt, 16);
-    cnt += __shfl_xor(cnt, 32);
+    cnt = butterfly_sum<gibbs_rowwave_lane_regs(KB, NS4), 16>(cnt);
+    cnt = butterfly_sum<gibbs_rowwave_lane_regs(KB, NS4), 32>(cnt);
     const int label = cnt < K ? cnt : K - 1;
     if (q == 0 && valid) {
       a.labels[n] = label;
@@ -381,8 +387,8 @@ __global__ __launch_bounds__(kRowWaveWG, 1) void gibbs_stream_kernel(const Kerne
 #pragma unroll
         for (int r = 0; r < 4; ++r) mv[r] = fmax(mv[r], acc[rb][r]);
       m = fmax(fmax(mv[0], mv[1]), fmax(mv[2], mv[3]));
-      m = fmax(m, __shfl_xor(m, 16));
-      m = fmax(m, __shfl_xor(m, 32));
+      m = butterfly_max<true, 16>(m);
+      m = butterfly_max<true, 32>(m);
     }
     double base[NCH + 1];
     base[0] = 0.0;
@@ -426,8 +432,8 @@ __global__ __launch_bounds__(kRowWaveWG, 1) void gibbs_stream_kernel(const Kerne
 #pragma unroll
       for (int i = 0; i < 8; ++i) cnt += tc > acc[2 * c + (i >> 2)][i & 3] ? 1 : 0;
     }
-    cnt += __shfl_xor(cnt, 16);
-    cnt += __shfl_xor(cnt, 32);
+    cnt = butterfly_sum<true, 16>(cnt);
+    cnt = butterfly_sum<true, 32>(cnt);
     const int label = cnt < K ? cnt : K - 1;
     if (q == 0 && valid) a.labels[n] = label;
     __builtin_amdgcn_s_setprio(0);
@@ -721,8 +727,8 @@ __global__ __launch_bounds__(kRowWaveWG, 1) void vi_rowwave_kernel(const KernelA
 #pragma unroll
         for (int r = 0; r < 4; ++r) mv[r] = fmax(mv[r], acc[rb][r]);
       m = fmax(fmax(mv[0], mv[1]), fmax(mv[2], mv[3]));
-      m = fmax(m, __shfl_xor(m, 16));
-      m = fmax(m, __shfl_xor(m, 32));
+      m = butterfly_max<vi_rowwave_lane_regs(KB, NS4), 16>(m);
+      m = butterfly_max<vi_rowwave_lane_regs(KB, NS4), 32>(m);
     }
     double sv[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -733,8 +739,8 @@ __global__ __launch_bounds__(kRowWaveWG, 1) void vi_rowwave_kernel(const KernelA
         sv[r] += acc[rb][r];
       }
     double ssum = (sv[0] + sv[1]) + (sv[2] + sv[3]);
-    ssum += __shfl_xor(ssum, 16);
-    ssum += __shfl_xor(ssum, 32);
+    ssum = butterfly_sum<vi_rowwave_lane_regs(KB, NS4), 16>(ssum);
+    ssum = butterfly_sum<vi_rowwave_lane_regs(KB, NS4), 32>(ssum);
     double inv = __builtin_amdgcn_rcp(ssum);
     inv = fma(fma(-ssum, inv, 1.0), inv, inv);
     inv = fma(fma(-ssum, inv, 1.0), inv, inv);

@@ -23,6 +23,12 @@
 #include <type_traits>
 
 namespace mimo {
+// Lane exchanges of the per-row reductions in registers (DPP only: the G <= 16 lanes of a row share a row of 16; mimo_device.h),
+// but for three instantiations {DZ, KL, G, MODE} that it costs a VGPR (profiles/r08_c2_lane_exchange.txt): same bits either way.
+// (List from a `make resources` comparison of both forms: see fused_lane_regs in mimo_kernels.hip for how to regenerate it.)
+constexpr bool small_lane_regs(int DZ, int KL, int G, int MODE) {
+  return !((DZ == 2 && KL == 4 && G == 2 && MODE == 0) || (DZ == 4 && KL == 2 && G == 2 && MODE == 0) || (DZ == 4 && KL == 2 && G == 8 && MODE == 1));
+}
 
 namespace {
 
@@ -180,8 +186,7 @@ void small_kernel(const KernelArgs a) {
       double m = l[0];
 #pragma unroll
       for (int c = 1; c < KL; ++c) m = fmax(m, l[c]);
-#pragma unroll
-      for (int s = 1; s < G; s <<= 1) m = fmax(m, __shfl_xor(m, s));
+      m = group_max<small_lane_regs(DZ, KL, G, MODE), G>(m);
       double e[KL];
 #pragma unroll
 #if MIMO_SMALL_EXP2048
@@ -193,15 +198,13 @@ void small_kernel(const KernelArgs a) {
       if constexpr (MODE == kGeneric) {     // sum_k e l feeds the entropy split of the ELBO scalars (switched-off / padding: 0)
 #pragma unroll
         for (int c = 0; c < KL; ++c) sel += e[c] * ((g * KL + c < K && l[c] > kOffLogDensity) ? l[c] : 0.0);
-#pragma unroll
-        for (int s = 1; s < G; s <<= 1) sel += __shfl_xor(sel, s);
+        sel = group_sum<small_lane_regs(DZ, KL, G, MODE), G>(sel);
       }
       if (!gibbs) {
         double ssum = e[0];
 #pragma unroll
         for (int c = 1; c < KL; ++c) ssum += e[c];
-#pragma unroll
-        for (int s = 1; s < G; s <<= 1) ssum += __shfl_xor(ssum, s);
+        ssum = group_sum<small_lane_regs(DZ, KL, G, MODE), G>(ssum);
         double inv = __builtin_amdgcn_rcp(ssum);
         inv = fma(fma(-ssum, inv, 1.0), inv, inv);
         inv = fma(fma(-ssum, inv, 1.0), inv, inv);
@@ -255,8 +258,7 @@ void small_kernel(const KernelArgs a) {
         int cnt = 0;
 #pragma unroll
         for (int c = 0; c < KL; ++c) cnt += tl > E[c] ? 1 : 0;
-#pragma unroll
-        for (int s = 1; s < G; s <<= 1) cnt += __shfl_xor(cnt, s);
+        cnt = group_sum<small_lane_regs(DZ, KL, G, MODE), G>(cnt);
         const int label = cnt < K ? cnt : K - 1;
         if (g == 0 && valid && a.labels) a.labels[n] = label;
 #pragma unroll
@@ -660,6 +662,40 @@ __global__ __launch_bounds__(kWG) void clock_probe_kernel(unsigned long long* __
 
 hipError_t launch_clock_probe(unsigned long long* out, int grid, int iters, hipStream_t stream) {
   hipLaunchKernelGGL(clock_probe_kernel, dim3(grid), dim3(kWG), 0, stream, out, iters, 0.999, 1e-3);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Self-test of the in-register lane exchanges (mimo_device.h): one wave runs lane_xor_max / lane_xor_sum (double and int)
+// for every mask next to the same stage written with __shfl_xor, on `rounds` sets of 64 per-lane values from the caller,
+// and checks that lane_xor_pair returns the lane's own word and its partner's; out[0] += lanes x checks whose bits differ.
+// ------------------------------------------------------------------------------------------
+template <int MASK>
+__device__ __forceinline__ unsigned lane_exchange_mismatches(const double v, const int iv) {
+  unsigned bad = 0;
+  bad += __double_as_longlong(lane_xor_max<MASK>(v)) != __double_as_longlong(fmax(v, __shfl_xor(v, MASK)));
+  bad += __double_as_longlong(lane_xor_sum<MASK>(v)) != __double_as_longlong(v + __shfl_xor(v, MASK));
+  bad += lane_xor_sum<MASK>(iv) != iv + __shfl_xor(iv, MASK);
+  const LanePair p = lane_xor_pair<MASK>(iv);
+  const int other = __shfl_xor(iv, MASK);
+  bad += !((p.a == iv && p.b == other) || (p.a == other && p.b == iv));
+  return bad;
+}
+__global__ __launch_bounds__(64) void lane_exchange_selftest_kernel(const double* __restrict__ vals, const int* __restrict__ ivals,
+                                                                    int rounds, unsigned int* __restrict__ out) {
+  const int lane = threadIdx.x;
+  unsigned bad = 0;
+  for (int r = 0; r < rounds; ++r) {      // (wave-uniform: all 64 lanes take every exchange)
+    const double v = vals[64 * r + lane];
+    const int iv = ivals[64 * r + lane];
+    bad += lane_exchange_mismatches<1>(v, iv) + lane_exchange_mismatches<2>(v, iv) + lane_exchange_mismatches<4>(v, iv);
+    bad += lane_exchange_mismatches<8>(v, iv) + lane_exchange_mismatches<16>(v, iv) + lane_exchange_mismatches<32>(v, iv);
+  }
+  if (bad) atomicAdd(out, bad);
+}
+
+hipError_t launch_lane_exchange_selftest(const double* vals, const int* ivals, int rounds, unsigned int* out, hipStream_t stream) {
+  hipLaunchKernelGGL(lane_exchange_selftest_kernel, dim3(1), dim3(64), 0, stream, vals, ivals, rounds, out);
   return hipGetLastError();
 }
 

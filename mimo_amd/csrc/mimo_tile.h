@@ -110,8 +110,10 @@ __device__ __forceinline__ void build_features_static(const double (&zl)[D + 2],
 // when one of its 16 components there has l - m >= lnt = ln tau, i.e. e >= tau; r = e / sum e <= e, so every weight
 // of a row left out of block b is below tau.  live[b] (32 bits, LDS) gets bit pt for each live row of the tile: wave w
 // writes byte w of every word (its rows 8w .. 8w+7), so the words need no clearing between tiles.
+// LX: the butterfly stages (lane ^ 8, ^ 16, ^ 32) of the maximum, the sums and the label count exchange lanes in registers
+// (lane_xor_max / lane_xor_sum, mimo_device.h) instead of through __shfl_xor; the caller says which, same bits either way.
 // ------------------------------------------------------------------------------------------
-template <int RBW, int MODE, bool E2K = false, bool SKIP = false>
+template <int RBW, int MODE, bool E2K = false, bool SKIP = false, bool LX = false>
 __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __restrict__ Lt, const int LS,
                                                const double* __restrict__ etab, const int K, const int K16,
                                                const int64_t N, const int64_t n0, const int wave, const int lane,
@@ -144,9 +146,9 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
             if (c < CPP && k0 + c < K) out_logp[(int64_t)(k0 + c) * N + n] = x[c];
         }
         const double ml = tree_max8(x);     // the lane's own maximum (SKIP, FULL: kept for the live mask)
-        double m = fmax(ml, __shfl_xor(ml, 8));
-        m = fmax(m, __shfl_xor(m, 16));
-        m = fmax(m, __shfl_xor(m, 32));
+        double m = butterfly_max<LX, 8>(ml);
+        m = butterfly_max<LX, 16>(m);
+        m = butterfly_max<LX, 32>(m);
 
         if constexpr (SKIP) {
           uint32_t bytes = 0;               // byte b: the live rows of this wave in row block b
@@ -197,16 +199,16 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
 #pragma unroll
           for (int c = 0; c < 8; ++c) t[c] = x[c] * lsave[c];
           sel = tree_sum8(t);
-          sel += __shfl_xor(sel, 8);
-          sel += __shfl_xor(sel, 16);
-          sel += __shfl_xor(sel, 32);
+          sel = butterfly_sum<LX, 8>(sel);
+          sel = butterfly_sum<LX, 16>(sel);
+          sel = butterfly_sum<LX, 32>(sel);
         }
 
         if (!gibbs) {
           double ssum = tree_sum8(x);
-          ssum += __shfl_xor(ssum, 8);
-          ssum += __shfl_xor(ssum, 16);
-          ssum += __shfl_xor(ssum, 32);
+          ssum = butterfly_sum<LX, 8>(ssum);
+          ssum = butterfly_sum<LX, 16>(ssum);
+          ssum = butterfly_sum<LX, 32>(ssum);
           // 1 / sum: v_rcp_f64 seed + two Newton steps (5 dependent f64 ops instead of the IEEE divide's
           // ~12; every one of them waits for a matrix-pipe slot); relative error <= 1 ulp-ish (2^-52).
           double inv = __builtin_amdgcn_rcp(ssum);
@@ -279,9 +281,9 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
 #pragma unroll
           for (int c = 0; c < 8; ++c)     // (padding slots can only be counted above the last real one: capped below)
             cnt += (ok(c) && tl > x[c]) ? 1 : 0;
-          cnt += __shfl_xor(cnt, 8);
-          cnt += __shfl_xor(cnt, 16);
-          cnt += __shfl_xor(cnt, 32);
+          cnt = butterfly_sum<LX, 8>(cnt);
+          cnt = butterfly_sum<LX, 16>(cnt);
+          cnt = butterfly_sum<LX, 32>(cnt);
           const int label = cnt < K ? cnt : K - 1;
           if (part == 0) {
             labs[pt] = valid ? label : -1;      // the statistics phase builds its one-hot operand from this
@@ -299,7 +301,7 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
 //   pass 3: softmax: e scaled by 1/sum.  Gibbs: the chunk that holds the crossing is located from the
 //           chunk totals, and only ITS eight e are read back, scanned and compared — 8 LDS reads and 12
 //           compares instead of 32 + 32.
-template <int RBW, int MODE>
+template <int RBW, int MODE, bool LX = false>
 __device__ __forceinline__ void normalise_tile_chunked(const KernelArgs& a, double* __restrict__ Lt, const int LS,
                                                        const double* __restrict__ etab, const int K, const int K16,
                                                        const int64_t N, const int64_t n0, const int wave,
@@ -336,9 +338,9 @@ __device__ __forceinline__ void normalise_tile_chunked(const KernelArgs& a, doub
     }
   }
   double m = tree_max8(mv);
-  m = fmax(m, __shfl_xor(m, 8));
-  m = fmax(m, __shfl_xor(m, 16));
-  m = fmax(m, __shfl_xor(m, 32));
+  m = butterfly_max<LX, 8>(m);
+  m = butterfly_max<LX, 16>(m);
+  m = butterfly_max<LX, 32>(m);
 
   double T[RBW], selv[RBW];
 #pragma unroll
@@ -375,16 +377,16 @@ __device__ __forceinline__ void normalise_tile_chunked(const KernelArgs& a, doub
   if constexpr (MODE == kGeneric) {
 #pragma unroll
     for (int ch = 0; ch < RBW; ++ch) sel += selv[ch];
-    sel += __shfl_xor(sel, 8);
-    sel += __shfl_xor(sel, 16);
-    sel += __shfl_xor(sel, 32);
+    sel = butterfly_sum<LX, 8>(sel);
+    sel = butterfly_sum<LX, 16>(sel);
+    sel = butterfly_sum<LX, 32>(sel);
   }
 
   if (!gibbs) {
     double ssum = cum;
-    ssum += __shfl_xor(ssum, 8);
-    ssum += __shfl_xor(ssum, 16);
-    ssum += __shfl_xor(ssum, 32);
+    ssum = butterfly_sum<LX, 8>(ssum);
+    ssum = butterfly_sum<LX, 16>(ssum);
+    ssum = butterfly_sum<LX, 32>(ssum);
     double inv = __builtin_amdgcn_rcp(ssum);
     inv = fma(fma(-ssum, inv, 1.0), inv, inv);
     inv = fma(fma(-ssum, inv, 1.0), inv, inv);
@@ -461,9 +463,9 @@ __device__ __forceinline__ void normalise_tile_chunked(const KernelArgs& a, doub
 #pragma unroll
       for (int cc = 0; cc < 8; ++cc) cnt += ((FULL || 8 * j + cc < CPP) && tj > x[cc]) ? 1 : 0;
     }
-    cnt += __shfl_xor(cnt, 8);
-    cnt += __shfl_xor(cnt, 16);
-    cnt += __shfl_xor(cnt, 32);
+    cnt = butterfly_sum<LX, 8>(cnt);
+    cnt = butterfly_sum<LX, 16>(cnt);
+    cnt = butterfly_sum<LX, 32>(cnt);
     const int label = cnt < K ? cnt : K - 1;
     if (part == 0) {
       labs[pt] = valid ? label : -1;

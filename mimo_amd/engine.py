@@ -273,6 +273,12 @@ class HipEngine(BoundDataGuard):
         self._check(self._lib.mimo_shader_clock_mhz(self._ctx, C.byref(out)))
         return out.value
 
+    def lane_exchange_selftest(self):
+        """Lanes x checks on which an in-register lane exchange differs from __shfl_xor (mimo_lane_exchange_selftest): 0."""
+        out = C.c_int(-1)
+        self._check(self._lib.mimo_lane_exchange_selftest(self._ctx, C.byref(out)))
+        return out.value
+
     def plan(self, K, gibbs=False):
         """How a pass with K components runs on the resident data (mimo_plan): kind, kernels, HBM passes."""
         o = (C.c_int64 * 8)()

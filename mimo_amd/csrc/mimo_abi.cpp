@@ -7,6 +7,7 @@
 #include "mimo_extra.h"
 #include "mimo_batched.h"
 #include "mimo_route.h"
+#include "mimo_theta.h"
 
 #include <algorithm>
 #include <cmath>
@@ -208,13 +209,6 @@ static int bind(mimo_ctx* ctx) {
 }
 
 // feature table for dimension D: pairs (a,b), a <= b <= D over z~ = [z, 1]; padding -> (D+1,D+1)
-static int fidx(const mimo_ctx* ctx, int a, int b) {   // feature of the pair (a, b), a <= b <= D; -1: not in the map
-  const int D = ctx->D;
-  if (ctx->structure == MIMO_STRUCT_DIAG) return (a == b || b == D) ? diag_feat_index(D, a, b) : -1;
-  if (ctx->structure == MIMO_STRUCT_LINEAR) return b == D ? a : -1;
-  return feat_index(D, a, b);
-}
-
 static int prepare_features(mimo_ctx* ctx, int D) {
   if (ctx->feat_D == D && ctx->feat_structure == ctx->structure) return MIMO_OK;
   const int st = ctx->structure;
@@ -223,7 +217,7 @@ static int prepare_features(mimo_ctx* ctx, int D) {
   ctx->feat_h.assign((size_t)ctx->F16 * 2, (uint8_t)(D + 1));
   for (int a = 0; a <= D; ++a)
     for (int b = a; b <= D; ++b) {
-      const int f = fidx(ctx, a, b);
+      const int f = struct_feat_index(st, D, a, b);
       if (f < 0) continue;
       ctx->feat_h[2 * f] = (uint8_t)a;
       ctx->feat_h[2 * f + 1] = (uint8_t)b;
@@ -281,262 +275,79 @@ static void fill_args(mimo_ctx* ctx, int K, KernelArgs* a) {
   a->resp_skip = ctx->resp_skip_log2;
 }
 
-// (c, b, W) -> Theta[k][f] -> MFMA A-operand image [K16][F16/4][64] on the device.
-//   f = (D,D): c_k ; (a,D): b_k[a] ; (a,a): -W_aa/2 ; (a,b), a<b: -(W_ab + W_ba)/2
-// small-shape kernel: Theta[G KL][F] row-major over the FULL feature map (feat_index order); a structure hint only
-// decides which entries of W are read (diagonal: W_aa; linear: none — the shared quadratic term stays with the caller)
-static int upload_theta_small(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, double* inline_out) {
-  const int D = ctx->D, F = feat_count(D), Kp = small_g(D, K) * small_kl(D, K);
-  const size_t count = (size_t)Kp * F;
-  // one lane per row (G = 1): Theta goes into the kernel arguments — no staging buffer to wait for, no transfer to enqueue
-  const bool inl = inline_out && small_g(D, K) == 1 && count <= (size_t)kThetaInline;
+// Why pack_theta (mimo_theta.h) refused a parameter block, in the wording of the entry points (batched: `what`, problem p)
+static int theta_fail(mimo_ctx* ctx, const ThetaFail& f, const char* what, int p) {
+  switch (f.kind) {
+    case ThetaFail::kBadC:
+      return what ? fail(ctx, MIMO_E_INVALID, "%s: c[%d][%d] is NaN or +inf", what, p, f.k)
+                  : fail(ctx, MIMO_E_INVALID, "c[%d] is NaN or +inf", f.k);
+    case ThetaFail::kLinearW:
+      return fail(ctx, MIMO_E_INVALID, "linear structure is set (mimo_set_structure) but W[%d] differs from W[0]", f.k);
+    case ThetaFail::kDiagOffDiag:
+      return fail(ctx, MIMO_E_INVALID, "diagonal structure is set (mimo_set_structure) but W[%d] has the "
+                  "off-diagonal entry (%d,%d)", f.k, f.a, f.b);
+    default:
+      return what ? fail(ctx, MIMO_E_INVALID, "%s: b or W of problem %d holds a NaN or an infinity", what, p)
+                  : fail(ctx, MIMO_E_INVALID, "b or W holds a NaN or an infinity");
+  }
+}
+
+// The images of B problems' (c, b, W) back to back in the placement `pl`, followed by `nextra` uint64 words (copied in the same
+// transfer), on the device at ctx->theta_d.  `what`: the batched entry point (its name leads the error texts), null for a single
+// problem.  inline_img: the image goes there and nowhere else — no staging buffer to wait for, no transfer to enqueue.
+template <typename Placement>
+static int stage_theta(mimo_ctx* ctx, const Placement& pl, const double* c, const double* b, const double* W, int B,
+                       const uint64_t* extra, size_t nextra, const char* what, double* inline_img = nullptr) {
+  const size_t D = ctx->D, K = pl.K, per = pl.count(), total = per * B + nextra;
   int rc;
-  if (!inl) {
-    if ((rc = ensure_dev(ctx, &ctx->theta_d, &ctx->theta_cap, count))) return rc;
-    if ((rc = ensure_pinned(ctx, &ctx->theta_h, &ctx->theta_hcap, count))) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));    // the staging buffer may still be in flight
+  if (!inline_img) {
+    if ((rc = ensure_dev(ctx, &ctx->theta_d, &ctx->theta_cap, total))) return rc;
+    if ((rc = ensure_pinned(ctx, &ctx->theta_h, &ctx->theta_hcap, total))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));    // the staging buffer may still be in flight from the previous call on this stream
   }
-  double* img = inl ? inline_out : ctx->theta_h;
-  memset(img, 0, count * sizeof(double));
-  bool finite = true;
-  auto chk = [&](double v) { finite = finite && std::fabs(v) <= 1.7976931348623157e308; return v; };
-  for (int k = 0; k < K; ++k) {
-    double* t = img + (size_t)k * F;
-    const double* bk = b + (size_t)k * D;
-    const double* Wk = W + (size_t)k * D * D;
-    if (c[k] != c[k] || c[k] > 1.7976931348623157e308) return fail(ctx, MIMO_E_INVALID, "c[%d] is NaN or +inf", k);
-    t[F - 1] = c[k] < kPadLogDensity ? kPadLogDensity : c[k];
-    for (int a = 0; a < D; ++a) t[feat_index(D, a, D)] = chk(bk[a]);
-    if (ctx->structure == MIMO_STRUCT_LINEAR) {
-      if (k > 0 && memcmp(Wk, W, sizeof(double) * D * D) != 0)
-        return fail(ctx, MIMO_E_INVALID, "linear structure is set (mimo_set_structure) but W[%d] differs from W[0]", k);
-      continue;
-    }
-    for (int a = 0; a < D; ++a) {
-      t[feat_index(D, a, a)] = chk(-0.5 * Wk[a * D + a]);
-      for (int bb = a + 1; bb < D; ++bb) {
-        if (ctx->structure == MIMO_STRUCT_FULL) t[feat_index(D, a, bb)] = chk(-0.5 * (Wk[a * D + bb] + Wk[bb * D + a]));
-        else if (Wk[a * D + bb] != 0.0 || Wk[bb * D + a] != 0.0)
-          return fail(ctx, MIMO_E_INVALID, "diagonal structure is set (mimo_set_structure) but W[%d] has the "
-                      "off-diagonal entry (%d,%d)", k, a, bb);
-      }
-    }
+  double* img = inline_img ? inline_img : ctx->theta_h;
+  for (int p = 0; p < B; ++p) {
+    const ThetaFail f = pack_theta(pl, ctx->structure, c + p * K, b + p * K * D, W + p * K * D * D, img + per * p);
+    if (f.kind) return theta_fail(ctx, f, what, p);
   }
-  if (!finite) return fail(ctx, MIMO_E_INVALID, "b or W holds a NaN or an infinity");
-  for (int k = K; k < Kp; ++k) img[(size_t)k * F + F - 1] = kPadLogDensity;
-  if (!inl) HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (nextra) memcpy(img + per * B, extra, nextra * sizeof(uint64_t));
+  if (!inline_img) HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   return MIMO_OK;
 }
 
-// Theta image of the row-owner label kernel: [NS][KB][64]; component k sits in A-row (k / V) + 4 (k % 4) of row block
-// (k % V) / 4, V = 4 KB, so that an output lane holds a contiguous quarter of the components (gibbs_rowwave_kernel)
-static int upload_theta_rowwave(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K) {
-  const int D = ctx->D;
-  const int ZSk = route_zs(K, D);
-  const int KB = rowwave_kb_shape(K, ctx->F16, ZSk), V = 4 * KB;
-  const int NS = rowwave_image_ns(K, ctx->F16, ZSk);                // (whole chunks where the label kernel streams Theta)
-  const size_t count = (size_t)NS * KB * 64;
-  int rc;
-  if ((rc = ensure_dev(ctx, &ctx->theta_d, &ctx->theta_cap, count))) return rc;
-  if ((rc = ensure_pinned(ctx, &ctx->theta_h, &ctx->theta_hcap, count))) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  double* img = ctx->theta_h;
-  memset(img, 0, count * sizeof(double));
-  bool finite = true;
-  auto put = [&](int k, int f, double v) {
-    const int t = k % V, rb = t / 4, i = k / V + 4 * (t % 4);
-    finite = finite && std::fabs(v) <= 1.7976931348623157e308;
-    img[((size_t)(f / 4) * KB + rb) * 64 + (f % 4) * 16 + i] = v;
-  };
-  for (int k = 0; k < K; ++k) {
-    const double* bk = b + (size_t)k * D;
-    const double* Wk = W + (size_t)k * D * D;
-    if (c[k] != c[k] || c[k] > 1.7976931348623157e308) return fail(ctx, MIMO_E_INVALID, "c[%d] is NaN or +inf", k);
-    put(k, fidx(ctx, D, D), c[k] < kPadLogDensity ? kPadLogDensity : c[k]);
-    for (int a = 0; a < D; ++a) put(k, fidx(ctx, a, D), bk[a]);
-    if (ctx->structure == MIMO_STRUCT_LINEAR) {       // the shared quadratic term stays with the caller (mimo_set_structure)
-      if (k > 0 && memcmp(Wk, W, sizeof(double) * D * D) != 0)
-        return fail(ctx, MIMO_E_INVALID, "linear structure is set (mimo_set_structure) but W[%d] differs from W[0]", k);
-      continue;
-    }
-    for (int a = 0; a < D; ++a) {
-      put(k, fidx(ctx, a, a), -0.5 * Wk[a * D + a]);
-      for (int bb = a + 1; bb < D; ++bb) {
-        if (ctx->structure == MIMO_STRUCT_FULL) put(k, feat_index(D, a, bb), -0.5 * (Wk[a * D + bb] + Wk[bb * D + a]));
-        else if (Wk[a * D + bb] != 0.0 || Wk[bb * D + a] != 0.0)
-          return fail(ctx, MIMO_E_INVALID, "diagonal structure is set (mimo_set_structure) but W[%d] has the "
-                      "off-diagonal entry (%d,%d)", k, a, bb);
-      }
-    }
-  }
-  if (!finite) return fail(ctx, MIMO_E_INVALID, "b or W holds a NaN or an infinity");
-  for (int k = K; k < 16 * KB; ++k) put(k, fidx(ctx, D, D), kPadLogDensity);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  return MIMO_OK;
-}
-
-// Theta image of the narrow kernels: [NSF][V][16]; slice s V + c, entry 4 kk + j = Theta[component j V + c][feature 4 s + kk]
-// (an output lane holds a contiguous quarter of the components: narrow_kernel)
-// Grouped variant (narrow_dt): the steps follow the rows of the upper triangle, feature (a, b) at narrow_group_pos.
-static int upload_theta_narrow(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, int mode) {
-  const int D = ctx->D, dt = narrow_dt(K, ctx->F, D, mode), NSF = narrow_steps(K, ctx->F, D, mode), V = narrow_v(K);
-  std::vector<int> gpos;                // grouped: 4 step + index of every feature of the full map
-  if (dt) {
-    gpos.assign((size_t)ctx->F, 0);
-    for (int aa = 0; aa <= D; ++aa)
-      for (int bb = aa; bb <= D; ++bb) {
-        int st, j;
-        narrow_group_pos(D, aa, bb, &st, &j);
-        gpos[feat_index(D, aa, bb)] = 4 * st + j;
-      }
-  }
-  const size_t count = (size_t)NSF * V * 16;
-  int rc;
-  if ((rc = ensure_dev(ctx, &ctx->theta_d, &ctx->theta_cap, count))) return rc;
-  if ((rc = ensure_pinned(ctx, &ctx->theta_h, &ctx->theta_hcap, count))) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  double* img = ctx->theta_h;
-  memset(img, 0, count * sizeof(double));
-  bool finite = true;
-  auto put = [&](int k, int f, double v) {
-    finite = finite && std::fabs(v) <= 1.7976931348623157e308;
-    const int g = dt ? gpos[f] : f;
-    img[((size_t)(g / 4) * V + k % V) * 16 + 4 * (g % 4) + k / V] = v;
-  };
-  for (int k = 0; k < K; ++k) {
-    const double* bk = b + (size_t)k * D;
-    const double* Wk = W + (size_t)k * D * D;
-    if (c[k] != c[k] || c[k] > 1.7976931348623157e308) return fail(ctx, MIMO_E_INVALID, "c[%d] is NaN or +inf", k);
-    put(k, fidx(ctx, D, D), c[k] < kPadLogDensity ? kPadLogDensity : c[k]);
-    for (int a = 0; a < D; ++a) put(k, fidx(ctx, a, D), bk[a]);
-    if (ctx->structure == MIMO_STRUCT_LINEAR) {       // the shared quadratic term stays with the caller (mimo_set_structure)
-      if (k > 0 && memcmp(Wk, W, sizeof(double) * D * D) != 0)
-        return fail(ctx, MIMO_E_INVALID, "linear structure is set (mimo_set_structure) but W[%d] differs from W[0]", k);
-      continue;
-    }
-    for (int a = 0; a < D; ++a) {
-      put(k, fidx(ctx, a, a), -0.5 * Wk[a * D + a]);
-      for (int bb = a + 1; bb < D; ++bb) {
-        if (ctx->structure == MIMO_STRUCT_FULL) put(k, feat_index(D, a, bb), -0.5 * (Wk[a * D + bb] + Wk[bb * D + a]));
-        else if (Wk[a * D + bb] != 0.0 || Wk[bb * D + a] != 0.0)
-          return fail(ctx, MIMO_E_INVALID, "diagonal structure is set (mimo_set_structure) but W[%d] has the "
-                      "off-diagonal entry (%d,%d)", k, a, bb);
-      }
-    }
-  }
-  if (!finite) return fail(ctx, MIMO_E_INVALID, "b or W holds a NaN or an infinity");
-  for (int k = K; k < 4 * V; ++k) put(k, fidx(ctx, D, D), kPadLogDensity);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  return MIMO_OK;
-}
-
-// Theta image of the mid kernel: [steps][KB][64] in the grouped feature order + mid_pf() zero slices
-static int upload_theta_mid(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, bool labels = false) {
-  const int D = ctx->D, KB = (K + 15) / 16, NS = mid_steps(D), V = 4 * KB;
-  const size_t count = ((size_t)NS * KB + mid_pf()) * 64;
-  int rc;
-  if ((rc = ensure_dev(ctx, &ctx->theta_d, &ctx->theta_cap, count))) return rc;
-  if ((rc = ensure_pinned(ctx, &ctx->theta_h, &ctx->theta_hcap, count))) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  double* img = ctx->theta_h;
-  memset(img, 0, count * sizeof(double));
-  bool finite = true;
-  auto put = [&](int k, int aa, int bb, double v) {
-    int st, jj;
-    narrow_group_pos(D, aa, bb, &st, &jj);
-    finite = finite && std::fabs(v) <= 1.7976931348623157e308;
-    int rb = k / 16, i = k % 16;
-    if (labels) {                       // label pass: lane quarter q holds components q V .. q V + V - 1 (slot i of row block rb: q = i & 3, r = i >> 2)
-      const int qq = k / V, t = k % V;
-      rb = t / 4; i = 4 * (t % 4) + qq;
-    }
-    img[((size_t)st * KB + rb) * 64 + 16 * jj + i] = v;
-  };
-  for (int k = 0; k < K; ++k) {
-    const double* bk = b + (size_t)k * D;
-    const double* Wk = W + (size_t)k * D * D;
-    if (c[k] != c[k] || c[k] > 1.7976931348623157e308) return fail(ctx, MIMO_E_INVALID, "c[%d] is NaN or +inf", k);
-    put(k, D, D, c[k] < kPadLogDensity ? kPadLogDensity : c[k]);
-    for (int a = 0; a < D; ++a) {
-      put(k, a, D, bk[a]);
-      put(k, a, a, -0.5 * Wk[a * D + a]);
-      for (int bb = a + 1; bb < D; ++bb) put(k, a, bb, -0.5 * (Wk[a * D + bb] + Wk[bb * D + a]));
-    }
-  }
-  if (!finite) return fail(ctx, MIMO_E_INVALID, "b or W holds a NaN or an infinity");
-  for (int k = K; k < 16 * KB; ++k) put(k, D, D, kPadLogDensity);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  return MIMO_OK;
-}
-
-static int upload_theta(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K) {
-  const int D = ctx->D, F16 = ctx->F16;
-  const int K16 = ((K + 15) / 16 <= 4) ? 4 : 16;   // every wave streams 1 (K<=64) or up to 4 row blocks; unused ones are zero
-  // fused kernels step through F16/4 slices per row block; the chunked E-step through whole chunks
-  const int NS = fused_covers((K + 15) / 16, F16 / 16, kSrcEstep) ? F16 / 4 : chunked_ns_pad(F16);
-  const size_t count = (size_t)K16 * NS * 64;
-  int rc;
-  if ((rc = ensure_dev(ctx, &ctx->theta_d, &ctx->theta_cap, count))) return rc;
-  if ((rc = ensure_pinned(ctx, &ctx->theta_h, &ctx->theta_hcap, count))) return rc;
-  // the staging buffer may still be in flight from the previous call on this stream
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  double* img = ctx->theta_h;
-  memset(img, 0, count * sizeof(double));
-  bool finite = true;
-  for (int k = 0; k < K; ++k) {
-    const int rb = k / 16, i = k % 16;
-    const double* bk = b + (size_t)k * D;
-    const double* Wk = W + (size_t)k * D * D;
-    auto put = [&](int f, double v) {
-      const int s = f / 4, kk = f % 4;
-      finite = finite && std::fabs(v) <= 1.7976931348623157e308;
-      img[((size_t)rb * NS + s) * 64 + kk * 16 + i] = v;
-    };
-    // a component switched off by its weight (log 0 = -inf in c_k, gmm.py:84 of the host mirror) enters like a
-    // padding component: l = -1e300 for every datum, r = 0 — an infinite operand would turn the zero features of the
-    // rows past N into NaN statistics
-    if (c[k] != c[k] || c[k] > 1.7976931348623157e308)
-      return fail(ctx, MIMO_E_INVALID, "c[%d] is NaN or +inf", k);
-    put(fidx(ctx, D, D), c[k] < kPadLogDensity ? kPadLogDensity : c[k]);
-    for (int a = 0; a < D; ++a) put(fidx(ctx, a, D), bk[a]);
-    if (ctx->structure == MIMO_STRUCT_LINEAR) {
-      // the common quadratic term stays with the caller (see mimo_set_structure); all W[k] must be one matrix
-      if (k > 0 && memcmp(Wk, W, sizeof(double) * D * D) != 0)
-        return fail(ctx, MIMO_E_INVALID, "linear structure is set (mimo_set_structure) but W[%d] differs from W[0]", k);
-      continue;
-    }
-    for (int a = 0; a < D; ++a) {
-      put(fidx(ctx, a, a), -0.5 * Wk[a * D + a]);
-      for (int bb = a + 1; bb < D; ++bb) {
-        if (ctx->structure == MIMO_STRUCT_FULL) put(feat_index(D, a, bb), -0.5 * (Wk[a * D + bb] + Wk[bb * D + a]));
-        else if (Wk[a * D + bb] != 0.0 || Wk[bb * D + a] != 0.0)
-          return fail(ctx, MIMO_E_INVALID, "diagonal structure is set (mimo_set_structure) but W[%d] has the "
-                      "off-diagonal entry (%d,%d)", k, a, bb);
-      }
-    }
-  }
-  if (!finite) return fail(ctx, MIMO_E_INVALID, "b or W holds a NaN or an infinity");
-  // padding components of the last row block: l = -1e300 for every datum, so the normalise phase needs no
-  // "does this component exist" test (exp -> 0, never the maximum, zero weight in the statistics)
-  for (int k = K; k < 16 * ((K + 15) / 16); ++k) {
-    const int f = fidx(ctx, D, D);
-    img[((size_t)(k / 16) * NS + f / 4) * 64 + (f % 4) * 16 + k % 16] = kPadLogDensity;
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  return MIMO_OK;
-}
-
-// The Theta image the route's kernels read
+// The Theta image the route's kernels read (placements: mimo_theta.h), and a->theta.  The structure rules hold for every image;
+// the mid images only ever see the full structure (mid_covers / mid_labels_covers admit no other, so use_mid / use_mid_labels
+// never route one there).
 static int upload_theta_for(mimo_ctx* ctx, const Route& route, const double* c, const double* b, const double* W, int K, KernelArgs* a) {
+  const int D = ctx->D, F16 = ctx->F16, st = ctx->structure, ZS = route_zs(K, D);
+  auto stage = [&](const auto& pl, double* inline_img = nullptr) {
+    const int rc = stage_theta(ctx, pl, c, b, W, 1, nullptr, 0, nullptr, inline_img);
+    a->theta = ctx->theta_d;
+    return rc;
+  };
   switch (route.image) {
-    case Image::Small: return upload_theta_small(ctx, c, b, W, K, a->theta_inline);
-    case Image::Narrow: return upload_theta_narrow(ctx, c, b, W, K, route.narrow_mode - 1);
-    case Image::Mid: return upload_theta_mid(ctx, c, b, W, K);
-    case Image::MidLabels: return upload_theta_mid(ctx, c, b, W, K, true);
-    case Image::RowOwner: return upload_theta_rowwave(ctx, c, b, W, K);
+    case Image::Small: {
+      // one lane per row (G = 1) and at most kThetaInline doubles: Theta goes into the kernel arguments
+      const ThetaSmall pl = {D, K, small_g(D, K) * small_kl(D, K)};
+      return stage(pl, small_g(D, K) == 1 && pl.count() <= (size_t)kThetaInline ? a->theta_inline : nullptr);
+    }
+    case Image::Narrow: {
+      const int mode = route.narrow_mode - 1, V = narrow_v(K), NSF = narrow_steps(K, ctx->F, D, mode);
+      if (!narrow_dt(K, ctx->F, D, mode)) return stage(ThetaNarrow{D, K, st, V, NSF, nullptr});
+      const ThetaGroupedOrder order(D);
+      return stage(ThetaNarrow{D, K, st, V, NSF, &order});
+    }
+    case Image::Mid: case Image::MidLabels: {
+      const ThetaGroupedOrder order(D);
+      return stage(ThetaMid{D, K, (K + 15) / 16, mid_steps(D), mid_pf(), route.image == Image::MidLabels, &order});
+    }
+    case Image::RowOwner: return stage(ThetaRowOwner{D, K, st, rowwave_kb_shape(K, F16, ZS), rowwave_image_ns(K, F16, ZS)});
     case Image::Generic: break;
   }
-  return upload_theta(ctx, c, b, W, K);
+  // every wave streams 1 (K <= 64) or up to 4 row blocks, unused ones are zero; the fused kernels step through F16 / 4 slices
+  // per row block, the chunked E-step through whole chunks
+  const int K16 = (K + 15) / 16;
+  return stage(ThetaGeneric{D, K, st, K16 <= 4 ? 4 : 16, fused_covers(K16, F16 / 16, kSrcEstep) ? F16 / 4 : chunked_ns_pad(F16)});
 }
 
 // What the router reads of the context
@@ -1054,7 +865,6 @@ int mimo_estep(mimo_ctx* ctx, const double* c, const double* b, const double* W,
   a.split = (flags & MIMO_F_ENTROPY_SPLIT) ? 1 : 0;
   if ((rc = keep_tables(ctx, K, flags, &a))) return rc;
   if ((rc = upload_theta_for(ctx, route, c, b, W, K, &a))) return rc;
-  a.theta = ctx->theta_d;
   return run_fused(ctx, a, kSrcEstep, flags, no_stats ? nullptr : S, scalars, route);
   });
 }
@@ -1094,7 +904,6 @@ int mimo_estep_weighted(mimo_ctx* ctx, const double* c, const double* b, const d
     ctx->weights_resident = true;
   }
   if ((rc = upload_theta_for(ctx, route, c, b, W, K, &a))) return rc;
-  a.theta = ctx->theta_d;
   return run_fused(ctx, a, kSrcEstep, flags, S, scalars, route);
   });
 }
@@ -1148,7 +957,6 @@ int mimo_gibbs_labels(mimo_ctx* ctx, const double* c, const double* b, const dou
   q.stats = !no_stats;
   const Route route = route_for(ctx, K, q);
   if ((rc = upload_theta_for(ctx, route, c, b, W, K, &a))) return rc;
-  a.theta = ctx->theta_d;
   if ((rc = run_fused(ctx, a, kSrcEstep, flags, no_stats ? nullptr : S, nullptr, route))) return rc;
   if (labels_out && !(flags & MIMO_F_DEVICE_OUT)) {
     HIP_TRY(ctx, hipMemcpyAsync(labels_out, ctx->labels, (size_t)ctx->N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -1807,46 +1615,12 @@ static int batched_ready(mimo_ctx* ctx, int K, const char* what) {
   return MIMO_OK;
 }
 
-// Stacked operand image [B][K16][NS][64] of the B problems' (c, b, W) (problem p's slice is the single-problem image),
-// followed by `extra` uint64 words (copied in the same transfer); on the device at ctx->theta_d.
+// Stacked operand image [B][K16][NS][64] of the B problems' (c, b, W) (problem p's slice is the single-problem image of the fused
+// kernels, K16 row blocks of it), followed by `extra` uint64 words; on the device at ctx->theta_d.
 static int batched_theta(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, const uint64_t* extra,
                          size_t nextra, const char* what) {
-  const int D = ctx->D, B = ctx->batch_B;
-  const int F16 = ctx->F16, K16 = (K + 15) / 16, NS = F16 / 4;
-  const size_t per = (size_t)K16 * NS * 64, count = per * B;
-  int rc;
-  if ((rc = ensure_dev(ctx, &ctx->theta_d, &ctx->theta_cap, count + nextra))) return rc;
-  if ((rc = ensure_pinned(ctx, &ctx->theta_h, &ctx->theta_hcap, count + nextra))) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // the staging buffer may still be in flight
-  double* img = ctx->theta_h;
-  memset(img, 0, count * sizeof(double));
-  bool finite = true;
-  for (int p = 0; p < B; ++p) {
-    double* ip = img + per * p;
-    for (int k = 0; k < 16 * K16; ++k) {
-      const int rb = k / 16, i = k % 16;
-      auto put = [&](int f, double v) {
-        finite = finite && std::fabs(v) <= 1.7976931348623157e308;
-        ip[((size_t)rb * NS + f / 4) * 64 + (f % 4) * 16 + i] = v;
-      };
-      if (k >= K) { ip[((size_t)rb * NS + feat_index(D, D, D) / 4) * 64 + (feat_index(D, D, D) % 4) * 16 + i] = kPadLogDensity; continue; }
-      const double ck = c[(size_t)p * K + k];
-      const double* bk = b + ((size_t)p * K + k) * D;
-      const double* Wk = W + ((size_t)p * K + k) * D * D;
-      if (ck != ck || ck > 1.7976931348623157e308)
-        return fail(ctx, MIMO_E_INVALID, "%s: c[%d][%d] is NaN or +inf", what, p, k);
-      put(feat_index(D, D, D), ck < kPadLogDensity ? kPadLogDensity : ck);   // c_k = -inf: a switched-off component
-      for (int a = 0; a < D; ++a) put(feat_index(D, a, D), bk[a]);
-      for (int a = 0; a < D; ++a) {
-        put(feat_index(D, a, a), -0.5 * Wk[a * D + a]);
-        for (int bb = a + 1; bb < D; ++bb) put(feat_index(D, a, bb), -0.5 * (Wk[a * D + bb] + Wk[bb * D + a]));
-      }
-    }
-    if (!finite) return fail(ctx, MIMO_E_INVALID, "%s: b or W of problem %d holds a NaN or an infinity", what, p);
-  }
-  if (nextra) memcpy(img + count, extra, nextra * sizeof(uint64_t));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, (count + nextra) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  return MIMO_OK;
+  const ThetaGeneric pl = {ctx->D, K, ctx->structure, (K + 15) / 16, ctx->F16 / 4};
+  return stage_theta(ctx, pl, c, b, W, ctx->batch_B, extra, nextra, what);
 }
 
 static BatchedArgs batched_args(mimo_ctx* ctx, int K) {

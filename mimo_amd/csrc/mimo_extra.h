@@ -63,7 +63,12 @@ void set_narrow_big_vi(int k);      // mimo_tune "narrow_big_vi": largest K of t
 // shape, else 0; contraction steps of the image either way; position of feature (a, b) in the grouped order
 int narrow_dt(int K, int F, int D, int gibbs);
 int narrow_steps(int K, int F, int D, int gibbs);
-void narrow_group_pos(int D, int a, int b, int* step, int* j);
+inline void narrow_group_pos(int D, int a, int b, int* step, int* j) {     // a <= b <= D
+  int s0 = 0;
+  for (int r = 0; r < a; ++r) s0 += (D + 1 - r + 3) / 4;
+  *step = s0 + (b - a) / 4;
+  *j = (b - a) % 4;
+}
 int narrow_grid(const KernelArgs& a, int num_cu, int F, int gibbs);
 hipError_t launch_narrow(const KernelArgs& a, int F, int gibbs, int grid, hipStream_t stream);
 

@@ -58,7 +58,7 @@ constexpr size_t mid_lds_bytes(int D, int KB) { return mid_nbuf(D, KB) * mid_til
 
 // MODE 0: softmax + statistics.  MODE 1: label draw (Gibbs sweep of the same shapes): the E-step as above, then the inverse-CDF draw on
 // the unnormalised cumulative sums in registers (mimo/utils/stats.py:8-21) — the operand image is permuted so that lane (q, j) holds
-// the CONTIGUOUS quarter q V .. q V + V - 1 (V = 4 KB) of row j's components (upload_theta_mid, as the row-owner label kernels);
+// the CONTIGUOUS quarter q V .. q V + V - 1 (V = 4 KB) of row j's components (ThetaMid of mimo_theta.h, as the row-owner label kernels);
 // no R tile, no second product, no workgroup barrier: the waves run on their own, the statistics of the labels come from the
 // label-statistics kernels behind it.
 template <int DT, int KB, int NW, int MODE = 0>

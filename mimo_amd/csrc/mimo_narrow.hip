@@ -71,13 +71,6 @@ int narrow_dt(int K, int F, int D, int gibbs) {
   return D;
 }
 int narrow_steps(int K, int F, int D, int gibbs) { return narrow_dt(K, F, D, gibbs) ? narrow_group_steps(D) : narrow_nsf(F); }
-// position of feature (a, b), a <= b <= D, in the grouped order: step and index inside the step
-void narrow_group_pos(int D, int a, int b, int* step, int* j) {
-  int s0 = 0;
-  for (int r = 0; r < a; ++r) s0 += (D + 1 - r + 3) / 4;
-  *step = s0 + (b - a) / 4;
-  *j = (b - a) % 4;
-}
 
 // Which (K, feature count F, Dz) the narrow kernels take (full structure or a reduced map alike: they read the feature
 // table).  MIMO_NARROW=0 switches the route off, MIMO_NARROW_MIN_K / MIMO_NARROW_MAX_K move its K range (tuning knobs).

@@ -26,7 +26,7 @@ struct RouteRequest {         // what the caller asks of the pass
 };
 
 enum class Family { Small, Narrow, Mid, MidLabels, Rowwave, RowwaveVi, Fused, TwoStage, LabelStats };   // LabelStats: kSrcLabels only
-enum class Image { Generic, Small, Narrow, Mid, MidLabels, RowOwner };                                  // Theta layouts (upload_theta_*)
+enum class Image { Generic, Small, Narrow, Mid, MidLabels, RowOwner };                                  // Theta layouts (placements of mimo_theta.h)
 
 struct Route {
   Family family = Family::Fused;

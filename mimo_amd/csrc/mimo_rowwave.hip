@@ -37,7 +37,7 @@ constexpr bool vi_rowwave_lane_regs(int KB, int NS4) { return !((KB == 2 && NS4 
 
 // ------------------------------------------------------------------------------------------
 // Label pass.  KB = row blocks (16 components each) the accumulators cover; K <= 16 KB.
-// Operand image (host, upload_theta_rowwave): slice e = s KB + rb, lane (i = lane & 15, kk = lane >> 4) holds
+// Operand image (host, ThetaRowOwner of mimo_theta.h): slice e = s KB + rb, lane (i = lane & 15, kk = lane >> 4) holds
 // Theta[comp(i, rb)][4 s + kk] with comp(i, rb) = (i & 3) V + 4 rb + (i >> 2), V = 4 KB: output lane (q, j)
 // register r of row block rb (= A-row q + 4 r) is component q V + 4 rb + r of data row j.
 // ------------------------------------------------------------------------------------------

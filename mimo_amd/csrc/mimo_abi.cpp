@@ -30,18 +30,61 @@ int destroy(void* comm);
 int allreduce_sum_f64(void* comm, double* buf, size_t count, hipStream_t stream, char* msg, size_t msglen);
 }
 
+struct mimo_ctx;
+static int fail(mimo_ctx* ctx, int code, const char* fmt, ...);
+
+#define HIP_TRY(ctx, expr)                                                                \
+  do {                                                                                    \
+    hipError_t e_ = (expr);                                                               \
+    if (e_ != hipSuccess)                                                                 \
+      return fail(ctx, MIMO_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
+  } while (0)
+
+// One owner per allocation: device memory (hipMalloc), or with Pinned its host sibling (hipHostMalloc).  Reads as the pointer it holds.
+template <typename T, bool Pinned = false>
+struct Buf {
+  T* p = nullptr;
+  size_t cap = 0;     // elements
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  ~Buf() { (void)release(); }
+  operator T*() const { return p; }
+  // free and forget in one step: the pointer is gone whatever the runtime answers, so nothing is freed twice
+  hipError_t release() {
+    T* old = p;
+    p = nullptr; cap = 0;
+    return !old ? hipSuccess : Pinned ? hipHostFree(old) : hipFree(old);
+  }
+  // room for `count` elements, at least one (an empty data set still gets an allocation).  Grows only; the contents do not survive
+  // a growth (the old block is freed before the new one is allocated); a HIP error goes to the context's error buffer.
+  int ensure(mimo_ctx* ctx, size_t count) {
+    if (count < 1) count = 1;
+    if (cap >= count && p) return MIMO_OK;
+    HIP_TRY(ctx, release());
+    if (Pinned) HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&p), count * sizeof(T), hipHostMallocDefault));
+    else HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)));
+    cap = count;
+    return MIMO_OK;
+  }
+};
+
+// cnt_d: [scan count | labels drawn on NaN rows per component (256) | content checksum of the upload (2)]
+constexpr int kCntLabels = 1, kCntChecksum = 257, kCntWords = 259;
+
 struct mimo_ctx {
   int device = 0;
   int num_cu = 256;       // what the grids are sized from (mimo_tune "num_cu" overrides it for tests)
   int hw_num_cu = 256;
   int resp_skip_log2 = 60;  // fused softmax pass: statistics skip the row blocks whose weights are all < 2^-60 (0: dense)
   hipStream_t own_stream = nullptr;
+  ~mimo_ctx() { if (own_stream) (void)hipStreamDestroy(own_stream); }     // (the buffers below free themselves after it)
   hipStream_t stream = nullptr;
   char err[512] = {0};   // fixed buffer: reporting an error never allocates
 
   // data
   const double* Z = nullptr;  // device
-  double* Z_owned = nullptr;
+  Buf<double> Z_owned;       // the library's copy of the rows (Z points at it, or at the caller's attached rows)
   int64_t N = 0;
   int D = 0;
   int64_t row0 = 0;
@@ -52,51 +95,51 @@ struct mimo_ctx {
   int feat_D = -1;
   int F = 0, F16 = 0;
   std::vector<uint8_t> feat_h;
-  uint8_t* feat_d = nullptr;
-  uint8_t* feat_full_d = nullptr;   // full map of the current D (small-shape kernel under a structure hint)
+  Buf<uint8_t> feat_d;
+  Buf<uint8_t> feat_full_d;         // full map of the current D (small-shape kernel under a structure hint)
   int feat_full_D = -1;
 
   // parameter image
-  double* theta_d = nullptr;  size_t theta_cap = 0;
-  double* theta_h = nullptr;  size_t theta_hcap = 0;   // pinned staging
+  Buf<double> theta_d;
+  Buf<double, true> theta_h;  // pinned staging
 
   // workspaces
-  double* partials = nullptr; size_t partials_cap = 0;
-  double* reduced = nullptr;  size_t reduced_cap = 0;
-  double* S_d = nullptr;      size_t S_cap = 0;         // packed stats + 3 scalars
-  double* S_h = nullptr;      size_t S_hcap = 0;        // pinned staging
+  Buf<double> partials;
+  Buf<double> reduced;
+  Buf<double> S_d;            // packed stats + 3 scalars
+  Buf<double, true> S_h;      // pinned staging
 
   // optional device-resident tables
-  double* resp = nullptr;  size_t resp_cap = 0;  int resp_K = 0;  bool resp_valid = false;
-  double* logp = nullptr;  size_t logp_cap = 0;  int logp_K = 0;  bool logp_valid = false;
-  double* lse = nullptr;   size_t lse_cap = 0;   bool lse_valid = false;
-  int32_t* labels = nullptr; size_t labels_cap = 0; bool labels_valid = false;
-  double* u_d = nullptr;   size_t u_cap = 0;
+  Buf<double> resp;  int resp_K = 0;  bool resp_valid = false;
+  Buf<double> logp;  int logp_K = 0;  bool logp_valid = false;
+  Buf<double> lse;   bool lse_valid = false;
+  Buf<int32_t> labels;  bool labels_valid = false;
+  Buf<double> u_d;
   bool weights_resident = false;     // u_d holds the row weights of the last mimo_estep_weighted (not uniforms of a label pass)
-  double* win = nullptr;   size_t win_cap = 0;    // staged host weights
-  int32_t* lin = nullptr;  size_t lin_cap = 0;    // staged host labels
+  Buf<double> win;    // staged host weights
+  Buf<int32_t> lin;   // staged host labels
 
   // rows with missing values (NaN): zeroed in the owned copy, excluded from every statistic through the mask
-  double* row_mask = nullptr;   size_t mask_cap = 0;      // (N,) 1 = complete row
+  Buf<double> row_mask;                                   // (N,) 1 = complete row
   int64_t n_bad = 0;
-  unsigned long long* cnt_d = nullptr;                    // [1 + 256 + 2]: scan count, labels drawn on NaN rows per component, content checksum of the upload
+  Buf<unsigned long long> cnt_d;                          // [kCntWords]: scan count, labels drawn on NaN rows per component, content checksum of the upload
   uint64_t data_sum[2] = {0, 0};                          // mimo_data_checksum: the rows as mimo_upload received them
   bool data_sum_valid = false;
-  int32_t* labels_tmp = nullptr; size_t labels_tmp_cap = 0;
-  uint32_t* ls_aux = nullptr;                              // label histogram + slot table of label_stats_slots_kernel
-  uint16_t* sort_list = nullptr; size_t sort_list_cap = 0;   // tiles ranked once for a multi-launch label-statistics pass (label_tile_sort_kernel)
-  uint16_t* sort_start = nullptr; size_t sort_start_cap = 0;
-  double* table_tmp = nullptr;  size_t table_tmp_cap = 0;
-  int bad_counts_K = 0;         // > 0: cnt_d[1..K] holds the label counts of the NaN rows of the last label pass
+  Buf<int32_t> labels_tmp;
+  Buf<uint32_t> ls_aux;                                    // label histogram + slot table of label_stats_slots_kernel
+  Buf<uint16_t> sort_list;   // tiles ranked once for a multi-launch label-statistics pass (label_tile_sort_kernel)
+  Buf<uint16_t> sort_start;
+  Buf<double> table_tmp;
+  int bad_counts_K = 0;         // > 0: cnt_d[kCntLabels ..] holds the label counts of the NaN rows of the last label pass
 
   // batched mode (mimo_upload_batched): Z holds the rows of B problems back to back; the single-problem entry points refuse
   bool batched = false;
   int batch_B = 0;
   int batch_G = 0;                                         // workgroups of the work table
   std::vector<int64_t> batch_rows;                         // host copy of row_off [B + 1]
-  int64_t* batch_row_off_d = nullptr;                      // [B + 1]
-  BatchedWork* batch_work_d = nullptr;                     // [G]
-  int32_t* batch_wg_off_d = nullptr;                       // [B + 1]: problem b owns the workgroups [wg_off[b], wg_off[b + 1])
+  Buf<int64_t> batch_row_off_d;                            // [B + 1]
+  Buf<BatchedWork> batch_work_d;                           // [G]
+  Buf<int32_t> batch_wg_off_d;                             // [B + 1]: problem b owns the workgroups [wg_off[b], wg_off[b + 1])
 
   void* comm = nullptr;         // RCCL communicator (mimo_comm_init): every pass then returns statistics summed over the ranks
   int comm_world = 1;
@@ -177,36 +220,16 @@ static int guarded(mimo_ctx* ctx, F&& f) noexcept {
   }
 }
 
-#define HIP_TRY(ctx, expr)                                                                \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return fail(ctx, MIMO_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-  } while (0)
-
-template <typename T>
-static int ensure_dev(mimo_ctx* ctx, T** p, size_t* cap, size_t count) {
-  if (*cap >= count && *p) return MIMO_OK;
-  if (*p) { HIP_TRY(ctx, hipFree(*p)); *p = nullptr; *cap = 0; }
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
-  *cap = count;
-  return MIMO_OK;
-}
-
-template <typename T>
-static int ensure_pinned(mimo_ctx* ctx, T** p, size_t* cap, size_t count) {
-  if (*cap >= count && *p) return MIMO_OK;
-  if (*p) { HIP_TRY(ctx, hipHostFree(*p)); *p = nullptr; *cap = 0; }
-  HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(p), count * sizeof(T), hipHostMallocDefault));
-  *cap = count;
-  return MIMO_OK;
-}
-
 static int bind(mimo_ctx* ctx) {
   if (!ctx) return fail(nullptr, MIMO_E_INVALID, "null context");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return MIMO_OK;
 }
+
+// doubles of a packed statistics block: K x (n, sum z, sum z z^T)
+static size_t packed_len(int K, int D) { return (size_t)K * (1 + D + (size_t)D * D); }
+// doubles of one workgroup's partial block: K16 row blocks of 16 components x F16 features, and the scalars behind them
+static size_t partial_stride(int K16, int F16) { return (size_t)16 * K16 * F16 + 4; }
 
 // feature table for dimension D: pairs (a,b), a <= b <= D over z~ = [z, 1]; padding -> (D+1,D+1)
 static int prepare_features(mimo_ctx* ctx, int D) {
@@ -222,8 +245,9 @@ static int prepare_features(mimo_ctx* ctx, int D) {
       ctx->feat_h[2 * f] = (uint8_t)a;
       ctx->feat_h[2 * f + 1] = (uint8_t)b;
     }
-  if (ctx->feat_d) { HIP_TRY(ctx, hipFree(ctx->feat_d)); ctx->feat_d = nullptr; }
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->feat_d), ctx->feat_h.size()));
+  int rc;
+  HIP_TRY(ctx, ctx->feat_d.release());       // replaced wholesale: the table is as long as its map
+  if ((rc = ctx->feat_d.ensure(ctx, ctx->feat_h.size()))) return rc;
   HIP_TRY(ctx, hipMemcpy(ctx->feat_d, ctx->feat_h.data(), ctx->feat_h.size(), hipMemcpyHostToDevice));
   ctx->feat_D = D;
   ctx->feat_structure = ctx->structure;
@@ -232,7 +256,7 @@ static int prepare_features(mimo_ctx* ctx, int D) {
     memset(full, D + 1, sizeof full);
     for (int aa = 0; aa <= D; ++aa)
       for (int bb = aa; bb <= D; ++bb) { full[2 * feat_index(D, aa, bb)] = (uint8_t)aa; full[2 * feat_index(D, aa, bb) + 1] = (uint8_t)bb; }
-    if (!ctx->feat_full_d) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->feat_full_d), sizeof full));
+    if ((rc = ctx->feat_full_d.ensure(ctx, sizeof full))) return rc;
     HIP_TRY(ctx, hipMemcpy(ctx->feat_full_d, full, sizeof full, hipMemcpyHostToDevice));
     ctx->feat_full_D = D;
   }
@@ -301,8 +325,8 @@ static int stage_theta(mimo_ctx* ctx, const Placement& pl, const double* c, cons
   const size_t D = ctx->D, K = pl.K, per = pl.count(), total = per * B + nextra;
   int rc;
   if (!inline_img) {
-    if ((rc = ensure_dev(ctx, &ctx->theta_d, &ctx->theta_cap, total))) return rc;
-    if ((rc = ensure_pinned(ctx, &ctx->theta_h, &ctx->theta_hcap, total))) return rc;
+    if ((rc = ctx->theta_d.ensure(ctx, total))) return rc;
+    if ((rc = ctx->theta_h.ensure(ctx, total))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));    // the staging buffer may still be in flight from the previous call on this stream
   }
   double* img = inline_img ? inline_img : ctx->theta_h;
@@ -428,25 +452,88 @@ static int prepare_label_presort(mimo_ctx* ctx, KernelArgs& a) {
   if (!label_stats_sorted(a.K, a.D, ctx->structure) && (a.N < 1 || label_stats_launches(a.K, a.D, ctx->structure) < 2)) return MIMO_OK;
   const size_t tiles = a.N < 1 ? 1 : (size_t)((a.N + 255) / 256);
   int rc;
-  if ((rc = ensure_dev(ctx, &ctx->sort_list, &ctx->sort_list_cap, tiles * 256))) return rc;
-  if ((rc = ensure_dev(ctx, &ctx->sort_start, &ctx->sort_start_cap, tiles * 257))) return rc;
+  if ((rc = ctx->sort_list.ensure(ctx, tiles * 256))) return rc;
+  if ((rc = ctx->sort_start.ensure(ctx, tiles * 257))) return rc;
   a.sort_list = ctx->sort_list; a.sort_start = ctx->sort_start;
   return MIMO_OK;
 }
 
-// run the pass (the kernels of route.family) -> reduce -> unpack;
-// deliver S / scalars to host or device pointers
-static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S, double* scalars, const Route& route) {
+// Two-stage path: chunked E-step writes responsibilities / labels, then the statistics kernel
+// runs once per group of <= kMaxNCB feature column blocks, all into the same partial block.
+static int launch_two_stage(mimo_ctx* ctx, KernelArgs& a, int src, int grid) {
   const int K = a.K, D = a.D;
-  const int Kpad = a.K16 * 16;
+  const int ncb_total = a.F16 / 16;
+  int rc;
+  KernelArgs st = a;
+  int stats_src = src;
+  if (src == kSrcEstep) {
+    KernelArgs e = a;
+    e.RS = 16 * kChunkNCB + 1;
+    e.split = (a.split || a.resp || a.logp || a.lse) ? 1 : 0;   // include/mimo_hip.h: scalars[1..2] come with the split or any kept table
+    if (!e.gibbs && e.do_stats && !e.resp) {       // statistics need the table: keep it internally
+      if ((rc = ctx->resp.ensure(ctx, (size_t)K * (size_t)ctx->N))) return rc;
+      e.resp = ctx->resp; ctx->resp_K = K; ctx->resp_valid = true;
+    }
+    if (chunked_lds_bytes(e) > 160 * 1024)
+      return fail(ctx, MIMO_E_UNSUPPORTED, "K=%d, Dz=%d needs more LDS than one CU has", K, D);
+    if (wide_estep_covers(a.K16, D, a.F16, e.gibbs))            // pipelined softmax / label pass (mimo_wide.hip)
+      rc = TIMED_HIP(ctx, "wide_estep_kernel", launch_wide_estep(e, grid, ctx->stream));
+    else
+      rc = TIMED_HIP(ctx, "estep_chunked_kernel", launch_estep_chunked(e, grid, ctx->stream));
+    if (rc) return rc;
+    st.resp = e.resp; st.labels = e.labels; st.write_scalars = 0;
+    stats_src = e.gibbs ? kSrcLabels : kSrcWeights;
+    if (ctx->n_bad > 0 && !e.gibbs && a.do_stats) {     // rows with NaN: their weights are dropped from the statistics
+      if ((rc = ctx->table_tmp.ensure(ctx, (size_t)K * (size_t)ctx->N))) return rc;
+      HIP_TRY(ctx, launch_mask_table(e.resp, ctx->row_mask, ctx->table_tmp, K, ctx->N, ctx->stream));
+      st.resp = ctx->table_tmp;
+    }
+  }
+  if (!a.do_stats) return MIMO_OK;
+  if (stats_src == kSrcLabels && label_stats_covers(K, D, ctx->structure)) {
+    // label-indexed statistics of the labels just drawn: the HBM-bound pass instead of one-hot products per column group
+    KernelArgs g = st;
+    g.gibbs = 0; g.do_stats = 1; g.logp = nullptr; g.lse = nullptr;
+    if ((rc = prepare_label_presort(ctx, g))) return rc;
+    return TIMED_HIP(ctx, "label_stats_kernel", launch_label_stats(g, ctx->structure, grid, ctx->stream));
+  }
+  const bool wide = stats_src == kSrcWeights && wide_stats_covers(a.K16, D);     // 8-wave statistics kernel (mimo_wide.hip)
+  const int gmax = wide ? wide_stats_group_ncb(a.K16, ncb_total) : stats_group_ncb(a.K16);
+  for (int cb0 = 0; cb0 < ncb_total; cb0 += gmax) {
+    KernelArgs g = st;
+    const int ncb = ncb_total - cb0 < gmax ? ncb_total - cb0 : gmax;
+    g.cb0 = cb0; g.F16 = 16 * ncb; g.RS = g.F16 + 1; g.F16_total = a.F16;
+    g.gibbs = 0; g.do_stats = 1; g.logp = nullptr; g.lse = nullptr;
+    if (cb0 > 0) g.write_scalars = 0;
+    if (wide) {
+      rc = TIMED_HIP(ctx, "wide_stats_kernel", launch_wide_stats(g, grid, ctx->stream));
+    } else {
+      rc = timed_launch(ctx, src == kSrcEstep ? "fused_kernel(statistics of a column group)" : "fused_kernel", [&]() -> int {
+        bool unsupported = false;
+        HIP_TRY(ctx, launch_fused(g, stats_src, grid, ctx->stream, &unsupported));
+        if (unsupported) return fail(ctx, MIMO_E_UNSUPPORTED, "no statistics kernel for K=%d, Dz=%d", K, D);
+        return MIMO_OK;
+      });
+    }
+    if (rc) return rc;
+  }
+  return MIMO_OK;
+}
+
+// The partial blocks a pass left behind: how many (the grid of the kernel that wrote them) and how far apart
+struct Launched { int grid; size_t pstride; };
+
+// Launch the kernels of route.family, and behind a label kernel (or alone, Family::LabelStats) the label statistics
+static int launch_route(mimo_ctx* ctx, KernelArgs& a, int src, const Route& route, Launched* out) {
+  const int K = a.K, D = a.D;
   const bool small = route.family == Family::Small;
   if (small) { a.F16_total = 16; a.F16 = 16; }
   const int kgrid = route_grid(route, a, ctx->num_cu, ctx->F, src);
   const bool lstats = route.label_draw() || route.family == Family::LabelStats;     // the label-statistics kernels close the pass
   const int grid = lstats ? label_stats_grid(a, ctx->num_cu) : kgrid;               // partial blocks
-  const size_t pstride = (size_t)Kpad * a.F16 + 4;
+  *out = {grid, partial_stride(a.K16, a.F16)};
   int rc;
-  if ((rc = ensure_dev(ctx, &ctx->partials, &ctx->partials_cap, pstride * (size_t)grid))) return rc;
+  if ((rc = ctx->partials.ensure(ctx, out->pstride * (size_t)grid))) return rc;
   a.partials = ctx->partials;
 
 #ifdef MIMO_STAMPS
@@ -457,7 +544,6 @@ static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S,
     g_stamps = stamps_d; g_stamps_grid = grid;
   }
 #endif
-  const int ncb_total = a.F16 / 16;
   // a resident-Theta label kernel counts its labels for the slot table of the statistics kernel behind it
   // (not with NaN rows: their labels are masked before the statistics; MIMO_FUSE_LABEL_HIST=0: off)
   static const bool fuse_on = [] { const char* e = getenv("MIMO_FUSE_LABEL_HIST"); return !e || atoi(e) != 0; }();
@@ -465,23 +551,17 @@ static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S,
   rc = MIMO_OK;
   switch (route.family) {
   case Family::LabelStats: break;
-  case Family::Rowwave:
-    a.fuse_hist = fuse_hist && gibbs_rowwave_counts_labels(K, a.F16, a.ZS) ? 1 : 0;
-    rc = timed_launch(ctx, "gibbs_rowwave_kernel", [&]() -> int {
+  case Family::Rowwave: case Family::Narrow: {
+    const bool narrow = route.family == Family::Narrow;
+    a.fuse_hist = fuse_hist && (narrow ? route.narrow_mode == 2 : gibbs_rowwave_counts_labels(K, a.F16, a.ZS)) ? 1 : 0;
+    rc = timed_launch(ctx, narrow ? "narrow_kernel" : "gibbs_rowwave_kernel", [&]() -> int {
       if (a.fuse_hist) HIP_TRY(ctx, launch_label_hist_reset(a, ctx->stream));
-      HIP_TRY(ctx, launch_gibbs_rowwave(a, kgrid, ctx->stream));
+      HIP_TRY(ctx, narrow ? launch_narrow(a, ctx->F, route.narrow_mode - 1, kgrid, ctx->stream) : launch_gibbs_rowwave(a, kgrid, ctx->stream));
       return MIMO_OK;
     });
     break;
+  }
   case Family::MidLabels: rc = TIMED_HIP(ctx, "mid_kernel (labels)", launch_mid_labels(a, kgrid, ctx->stream)); break;
-  case Family::Narrow:
-    a.fuse_hist = route.narrow_mode == 2 && fuse_hist ? 1 : 0;
-    rc = timed_launch(ctx, "narrow_kernel", [&]() -> int {
-      if (a.fuse_hist) HIP_TRY(ctx, launch_label_hist_reset(a, ctx->stream));
-      HIP_TRY(ctx, launch_narrow(a, ctx->F, route.narrow_mode - 1, kgrid, ctx->stream));
-      return MIMO_OK;
-    });
-    break;
   case Family::RowwaveVi: rc = TIMED_HIP(ctx, "vi_rowwave_kernel", launch_vi_rowwave(a, grid, ctx->stream)); break;
   case Family::Mid: rc = TIMED_HIP(ctx, "mid_kernel", launch_mid(a, grid, ctx->stream)); break;
   case Family::Small: case Family::Fused:
@@ -493,65 +573,7 @@ static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S,
       return MIMO_OK;
     });
     break;
-  case Family::TwoStage: {
-    // two-stage path: chunked E-step writes responsibilities / labels, then the statistics kernel
-    // runs once per group of <= kMaxNCB feature column blocks, all into the same partial block.
-    KernelArgs st = a;
-    int stats_src = src;
-    if (src == kSrcEstep) {
-      KernelArgs e = a;
-      e.RS = 16 * kChunkNCB + 1;
-      e.split = (a.split || a.resp || a.logp || a.lse) ? 1 : 0;   // include/mimo_hip.h: scalars[1..2] come with the split or any kept table
-      if (!e.gibbs && e.do_stats && !e.resp) {       // statistics need the table: keep it internally
-        const size_t kn = (size_t)K * (size_t)(ctx->N > 0 ? ctx->N : 1);
-        if ((rc = ensure_dev(ctx, &ctx->resp, &ctx->resp_cap, kn))) return rc;
-        e.resp = ctx->resp; ctx->resp_K = K; ctx->resp_valid = true;
-      }
-      if (chunked_lds_bytes(e) > 160 * 1024)
-        return fail(ctx, MIMO_E_UNSUPPORTED, "K=%d, Dz=%d needs more LDS than one CU has", K, D);
-      if (wide_estep_covers(a.K16, D, a.F16, e.gibbs))            // pipelined softmax / label pass (mimo_wide.hip)
-        rc = TIMED_HIP(ctx, "wide_estep_kernel", launch_wide_estep(e, grid, ctx->stream));
-      else
-        rc = TIMED_HIP(ctx, "estep_chunked_kernel", launch_estep_chunked(e, grid, ctx->stream));
-      if (rc) return rc;
-      st.resp = e.resp; st.labels = e.labels; st.write_scalars = 0;
-      stats_src = e.gibbs ? kSrcLabels : kSrcWeights;
-      if (ctx->n_bad > 0 && !e.gibbs && a.do_stats) {     // rows with NaN: their weights are dropped from the statistics
-        const size_t kn = (size_t)K * (size_t)ctx->N;
-        if ((rc = ensure_dev(ctx, &ctx->table_tmp, &ctx->table_tmp_cap, kn))) return rc;
-        HIP_TRY(ctx, launch_mask_table(e.resp, ctx->row_mask, ctx->table_tmp, K, ctx->N, ctx->stream));
-        st.resp = ctx->table_tmp;
-      }
-    }
-    if (a.do_stats && stats_src == kSrcLabels && label_stats_covers(K, D, ctx->structure)) {
-      // label-indexed statistics of the labels just drawn: the HBM-bound pass instead of one-hot products per column group
-      KernelArgs g = st;
-      g.gibbs = 0; g.do_stats = 1; g.logp = nullptr; g.lse = nullptr;
-      if ((rc = prepare_label_presort(ctx, g))) return rc;
-      rc = TIMED_HIP(ctx, "label_stats_kernel", launch_label_stats(g, ctx->structure, grid, ctx->stream));
-    } else if (a.do_stats) {
-      const bool wide = stats_src == kSrcWeights && wide_stats_covers(a.K16, D);     // 8-wave statistics kernel (mimo_wide.hip)
-      const int gmax = wide ? wide_stats_group_ncb(a.K16, ncb_total) : stats_group_ncb(a.K16);
-      for (int cb0 = 0; cb0 < ncb_total; cb0 += gmax) {
-        KernelArgs g = st;
-        const int ncb = ncb_total - cb0 < gmax ? ncb_total - cb0 : gmax;
-        g.cb0 = cb0; g.F16 = 16 * ncb; g.RS = g.F16 + 1; g.F16_total = a.F16;
-        g.gibbs = 0; g.do_stats = 1; g.logp = nullptr; g.lse = nullptr;
-        if (cb0 > 0) g.write_scalars = 0;
-        if (wide) {
-          rc = TIMED_HIP(ctx, "wide_stats_kernel", launch_wide_stats(g, grid, ctx->stream));
-        } else {
-          rc = timed_launch(ctx, src == kSrcEstep ? "fused_kernel(statistics of a column group)" : "fused_kernel", [&]() -> int {
-            bool unsupported = false;
-            HIP_TRY(ctx, launch_fused(g, stats_src, grid, ctx->stream, &unsupported));
-            if (unsupported) return fail(ctx, MIMO_E_UNSUPPORTED, "no statistics kernel for K=%d, Dz=%d", K, D);
-            return MIMO_OK;
-          });
-        }
-        if (rc) return rc;
-      }
-    }
-  }
+  case Family::TwoStage: rc = launch_two_stage(ctx, a, src, grid); break;
   }
   if (rc) return rc;
   if (lstats && a.do_stats) {
@@ -559,19 +581,44 @@ static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S,
     if ((rc = TIMED_HIP(ctx, "label_stats_kernel", launch_label_stats(a, ctx->structure, grid, ctx->stream)))) return rc;
   }
   if (ctx->prof) ctx->prof_n += 1;
+  return MIMO_OK;
+}
+
+// Room for a block of `len` doubles on the device and in its pinned host sibling
+static int ensure_block(mimo_ctx* ctx, size_t len) {
+  const int rc = ctx->S_d.ensure(ctx, len);
+  return rc ? rc : ctx->S_h.ensure(ctx, len);
+}
+
+// The end of every host delivery.  The first `copy_len` doubles of the device block follow the kernels into the pinned buffer
+// (0: they are there already, or on their way); then wait for the stream and hand the caller `nstats` doubles from its front
+// and `nscalars` doubles from `scalars_at` on.  A null destination is skipped.
+static int hand_out(mimo_ctx* ctx, size_t copy_len, double* S, size_t nstats, double* scalars, size_t scalars_at, size_t nscalars) {
+  if (copy_len) HIP_TRY(ctx, hipMemcpyAsync(ctx->S_h, ctx->S_d, copy_len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (S) memcpy(S, ctx->S_h, nstats * sizeof(double));
+  if (scalars) memcpy(scalars, ctx->S_h + scalars_at, nscalars * sizeof(double));
+  return MIMO_OK;
+}
+
+// Reduce the partial blocks of a pass -> unpack; deliver S / scalars to host or device pointers
+static int deliver(mimo_ctx* ctx, const KernelArgs& a, int flags, double* S, double* scalars, const Route& route, const Launched& l) {
+  const int K = a.K, D = a.D;
+  const bool small = route.family == Family::Small;
   const bool async = (flags & MIMO_F_ASYNC) != 0;
   // (a promoted bound pass leaves its statistics in the partial blocks: nothing of them is reduced, all-reduced or copied)
   const bool want_stats = a.do_stats && !route.promoted && (S || async);
   const bool device_out = (flags & MIMO_F_DEVICE_OUT) != 0;
   if (!want_stats && !scalars && !async) return MIMO_OK;
 
-  const size_t slen = (size_t)K * (1 + D + (size_t)D * D);
+  int rc;
+  const size_t slen = packed_len(K, D);
   // the small-shape kernel always accumulates the full feature map: under a structure hint the entries outside
   // the structure are masked to the zeros the hint promises
   const uint8_t* feat = small ? ctx->feat_full_d : ctx->feat_d;
   const int F = small ? feat_count(D) : ctx->F, mask = small ? ctx->structure : 0;
   if (device_out) {
-    HIP_TRY(ctx, launch_reduce_unpack(ctx->partials, grid, (int64_t)pstride, feat, K, D, F, a.F16, want_stats ? S : nullptr, scalars,
+    HIP_TRY(ctx, launch_reduce_unpack(ctx->partials, l.grid, (int64_t)l.pstride, feat, K, D, F, a.F16, want_stats ? S : nullptr, scalars,
                                       ctx->stream, mask));
     if (ctx->comm) {     // sharded through this library: sum over the ranks where the caller wants the block
       char msg[256];
@@ -580,28 +627,57 @@ static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S,
     }
     return MIMO_OK;
   }
-  if ((rc = ensure_dev(ctx, &ctx->S_d, &ctx->S_cap, slen + 4))) return rc;
-  if ((rc = ensure_pinned(ctx, &ctx->S_h, &ctx->S_hcap, slen + 4))) return rc;
+  if ((rc = ensure_block(ctx, slen + 4))) return rc;
   // Without a communicator and on the full feature map the reduction writes the packed block straight into the pinned host
   // buffer (device-visible, hipHostMalloc): no device copy of the block, no D2H transfer behind the kernel.
   static const bool direct_on = [] { const char* e = getenv("MIMO_DIRECT_OUT"); return !e || atoi(e) != 0; }();   // tuning knob
   const bool direct = direct_on && !ctx->comm && F == feat_count(D);
-  double* dst = direct ? ctx->S_h : ctx->S_d;
+  double* dst = direct ? ctx->S_h.p : ctx->S_d.p;
   if (ctx->comm && !want_stats) HIP_TRY(ctx, hipMemsetAsync(ctx->S_d, 0, slen * sizeof(double), ctx->stream));
-  HIP_TRY(ctx, launch_reduce_unpack(ctx->partials, grid, (int64_t)pstride, feat, K, D, F, a.F16, want_stats ? dst : nullptr,
+  HIP_TRY(ctx, launch_reduce_unpack(ctx->partials, l.grid, (int64_t)l.pstride, feat, K, D, F, a.F16, want_stats ? dst : nullptr,
                                     dst + slen, ctx->stream, mask));
   if (ctx->comm) {       // ONE all-reduce(sum, f64) of [K (1 + Dz + Dz^2) + 3] per pass, behind the kernels on the same stream
     char msg[256];
     if ((rc = mimo_comm::allreduce_sum_f64(ctx->comm, ctx->S_d, slen + 3, ctx->stream, msg, sizeof msg))) return fail(ctx, rc, "%s", msg);
   }
   if (!direct) HIP_TRY(ctx, hipMemcpyAsync(ctx->S_h, ctx->S_d, (slen + 4) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (flags & MIMO_F_ASYNC) {
-    ctx->pending_async = true; ctx->pending_slen = slen; ctx->pending_stats = want_stats;
-    return MIMO_OK;
+  if (!async) return hand_out(ctx, 0, want_stats ? S : nullptr, slen, scalars, slen, 3);
+  ctx->pending_async = true; ctx->pending_slen = slen; ctx->pending_stats = want_stats;     // mimo_wait hands the block out
+  return MIMO_OK;
+}
+
+// run the pass (the kernels of route.family) -> reduce -> unpack -> S / scalars at the caller's host or device pointers
+static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S, double* scalars, const Route& route) {
+  Launched l;
+  const int rc = launch_route(ctx, a, src, route, &l);
+  return rc ? rc : deliver(ctx, a, flags, S, scalars, route, l);
+}
+
+// What an entry point reads when the caller passes NULL for an input: the context's own copy `p` if `valid`, else MIMO_E_STATE
+// with the entry point's text `missing` (it may print K).  No `missing`: the input is optional and NULL stays NULL.
+template <typename T>
+struct Resident { const T* p = nullptr; bool valid = false; const char* missing = nullptr; };
+
+// Bring one input of `count` elements to the device and say where to read it (*dev): NULL is the resident copy, under
+// MIMO_F_DEVICE_IN the caller's pointer is the device's already, anything else is host memory and goes through `staging` (*copied
+// becomes true).  The copy is only enqueued: the source is pageable, so the entry point synchronises once all its inputs are
+// queued, and does what else follows from a fresh staging buffer there.
+// (P: const T* or T* — KernelArgs holds its tables and labels as writable pointers for the kernels that produce them)
+template <typename T, typename P>
+static int stage_input(mimo_ctx* ctx, const T* src, size_t count, int flags, Buf<T>& staging, const Resident<T>& res, int K,
+                       P* dev, bool* copied) {
+  if (!src) {
+    if (res.missing && !res.valid) return fail(ctx, MIMO_E_STATE, res.missing, K);
+    *dev = const_cast<P>(res.p);
+  } else if (flags & MIMO_F_DEVICE_IN) {
+    *dev = const_cast<P>(src);
+  } else {
+    const int rc = staging.ensure(ctx, count);
+    if (rc) return rc;
+    if (count) HIP_TRY(ctx, hipMemcpyAsync(staging, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    *dev = staging;
+    *copied = true;
   }
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (want_stats) memcpy(S, ctx->S_h, slen * sizeof(double));
-  if (scalars) memcpy(scalars, ctx->S_h + slen, 3 * sizeof(double));
   return MIMO_OK;
 }
 
@@ -621,7 +697,7 @@ static int run_fused(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S
     if (!a.u) {
       a.u = ctx->row_mask;
     } else {       // caller's row weights x mask (one column of a "table")
-      if ((rc = ensure_dev(ctx, &ctx->table_tmp, &ctx->table_tmp_cap, (size_t)N))) return rc;
+      if ((rc = ctx->table_tmp.ensure(ctx, (size_t)N))) return rc;
       HIP_TRY(ctx, launch_mask_table(a.u, ctx->row_mask, ctx->table_tmp, 1, N, ctx->stream));
       a.u = ctx->table_tmp;
     }
@@ -634,9 +710,9 @@ static int run_fused(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S
       a.do_stats = 0;
       if ((rc = run_pass(ctx, a, kSrcEstep, flags & ~(MIMO_F_DEVICE_OUT), nullptr, nullptr, route))) return rc;
     }
-    if ((rc = ensure_dev(ctx, &ctx->labels_tmp, &ctx->labels_tmp_cap, (size_t)N))) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->cnt_d + 1, 0, 256 * sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(ctx, launch_mask_labels(a.labels, ctx->row_mask, ctx->labels_tmp, N, a.K, ctx->cnt_d + 1, ctx->stream));
+    if ((rc = ctx->labels_tmp.ensure(ctx, (size_t)N))) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->cnt_d + kCntLabels, 0, 256 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, launch_mask_labels(a.labels, ctx->row_mask, ctx->labels_tmp, N, a.K, ctx->cnt_d + kCntLabels, ctx->stream));
     ctx->bad_counts_K = a.K;
     if (!want) return MIMO_OK;
     KernelArgs b = a;
@@ -644,8 +720,7 @@ static int run_fused(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S
     return run_pass(ctx, b, kSrcLabels, flags, S, scalars, route_for(ctx, a.K, {kSrcLabels}));
   }
   // kSrcWeights: statistics of a (K, N) table
-  const size_t kn = (size_t)a.K * (size_t)N;
-  if ((rc = ensure_dev(ctx, &ctx->table_tmp, &ctx->table_tmp_cap, kn))) return rc;
+  if ((rc = ctx->table_tmp.ensure(ctx, (size_t)a.K * (size_t)N))) return rc;
   HIP_TRY(ctx, launch_mask_table(a.resp, ctx->row_mask, ctx->table_tmp, a.K, N, ctx->stream));
   a.resp = ctx->table_tmp;
   return run_pass(ctx, a, src, flags, S, scalars, route);
@@ -677,11 +752,7 @@ int mimo_create(mimo_ctx** out, int device) {
     return fail(nullptr, MIMO_E_HIP, "hipStreamCreate failed");
   }
   ctx->stream = ctx->own_stream;
-  if (hipMalloc(reinterpret_cast<void**>(&ctx->ls_aux), label_stats_aux_words() * sizeof(uint32_t)) != hipSuccess) {
-    (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
-    return fail(nullptr, MIMO_E_HIP, "hipMalloc failed");
-  }
+  if (ctx->ls_aux.ensure(nullptr, label_stats_aux_words())) { delete ctx; return MIMO_E_HIP; }     // (the text is in g_err)
   *out = ctx;
   return MIMO_OK;
   });
@@ -694,14 +765,7 @@ int mimo_destroy(mimo_ctx* ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   drain_profile(ctx);
   if (ctx->comm) { (void)mimo_comm::destroy(ctx->comm); ctx->comm = nullptr; }
-  void* bufs[] = {ctx->sort_list, ctx->sort_start, ctx->ls_aux, ctx->Z_owned, ctx->feat_d, ctx->feat_full_d, ctx->row_mask, ctx->cnt_d, ctx->labels_tmp, ctx->table_tmp, ctx->theta_d, ctx->partials, ctx->reduced, ctx->S_d, ctx->resp,
-                  ctx->logp, ctx->lse, ctx->labels, ctx->u_d, ctx->win, ctx->lin,
-                  ctx->batch_row_off_d, ctx->batch_work_d, ctx->batch_wg_off_d};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if (ctx->theta_h) (void)hipHostFree(ctx->theta_h);
-  if (ctx->S_h) (void)hipHostFree(ctx->S_h);
-  if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-  delete ctx;
+  delete ctx;      // the stream and every buffer go with it
   return MIMO_OK;
   });
 }
@@ -728,6 +792,26 @@ static int set_data(mimo_ctx* ctx, int64_t N, int Dz) {
   return prepare_features(ctx, Dz);
 }
 
+// Replace the resident rows by N x D doubles from `src`: a host block that is copied, the caller's device rows that are borrowed,
+// or (scan_nan_rows) borrowed rows that need a copy the library may write.  ctx->Z is null from before the old copy is freed until
+// the last step has succeeded, so a failure leaves the context without data (MIMO_E_NODATA) and never with freed rows.
+enum class Rows { HostCopy, DeviceBorrow, DeviceCopy };
+static int set_rows(mimo_ctx* ctx, const double* src, Rows how) {
+  const size_t count = (size_t)ctx->N * ctx->D;
+  int rc;
+  ctx->Z = nullptr;
+  if (how != Rows::DeviceCopy) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // kernels of earlier calls may still read the old rows
+  HIP_TRY(ctx, ctx->Z_owned.release());
+  if (how != Rows::DeviceBorrow) {
+    if ((rc = ctx->Z_owned.ensure(ctx, count))) return rc;
+    if (how == Rows::DeviceCopy) HIP_TRY(ctx, hipMemcpyAsync(ctx->Z_owned, src, count * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    else if (count) HIP_TRY(ctx, hipMemcpy(ctx->Z_owned, src, count * sizeof(double), hipMemcpyHostToDevice));
+    src = ctx->Z_owned;
+  }
+  ctx->Z = src;
+  return MIMO_OK;
+}
+
 // Find the rows that hold a NaN.  `owned`: Z is the library's copy — such rows are zeroed in place and the mask written;
 // otherwise (borrowed device buffer) they are only counted, and if there are any the data is copied first.
 static int scan_nan_rows(mimo_ctx* ctx, bool checksum) {
@@ -738,16 +822,16 @@ static int scan_nan_rows(mimo_ctx* ctx, bool checksum) {
     return MIMO_OK;
   }
   int rc;
-  if (!ctx->cnt_d) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->cnt_d), 259 * sizeof(unsigned long long)));
+  if ((rc = ctx->cnt_d.ensure(ctx, kCntWords))) return rc;
   // flat scan first (one coalesced read of Z): data without a NaN — the usual case — is done after it; the same read
   // yields the content checksum of an upload (before any row is zeroed)
   HIP_TRY(ctx, hipMemsetAsync(ctx->cnt_d, 0, sizeof(unsigned long long), ctx->stream));
-  if (checksum) HIP_TRY(ctx, hipMemsetAsync(ctx->cnt_d + 257, 0, 2 * sizeof(unsigned long long), ctx->stream));
-  HIP_TRY(ctx, launch_nan_any(ctx->Z, ctx->N * ctx->D, reinterpret_cast<unsigned int*>(ctx->cnt_d), ctx->hw_num_cu, ctx->stream,
-                              checksum ? ctx->cnt_d + 257 : nullptr));
+  if (checksum) HIP_TRY(ctx, hipMemsetAsync(ctx->cnt_d + kCntChecksum, 0, 2 * sizeof(unsigned long long), ctx->stream));
+  HIP_TRY(ctx, launch_nan_any(ctx->Z, ctx->N * ctx->D, reinterpret_cast<unsigned int*>(ctx->cnt_d.p), ctx->hw_num_cu, ctx->stream,
+                              checksum ? ctx->cnt_d + kCntChecksum : nullptr));
   unsigned long long nb = 0;
   HIP_TRY(ctx, hipMemcpyAsync(&nb, ctx->cnt_d, sizeof nb, hipMemcpyDeviceToHost, ctx->stream));
-  if (checksum) HIP_TRY(ctx, hipMemcpyAsync(ctx->data_sum, ctx->cnt_d + 257, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  if (checksum) HIP_TRY(ctx, hipMemcpyAsync(ctx->data_sum, ctx->cnt_d + kCntChecksum, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->data_sum_valid = checksum;
   if (nb == 0) return MIMO_OK;
@@ -756,13 +840,8 @@ static int scan_nan_rows(mimo_ctx* ctx, bool checksum) {
   HIP_TRY(ctx, hipMemcpyAsync(&nb, ctx->cnt_d, sizeof nb, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (nb == 0) return MIMO_OK;
-  if (ctx->Z != ctx->Z_owned) {        // borrowed buffer: never written — work on a copy
-    const size_t bytes = (size_t)ctx->N * ctx->D * sizeof(double);
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->Z_owned), bytes));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->Z_owned, ctx->Z, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    ctx->Z = ctx->Z_owned;
-  }
-  if ((rc = ensure_dev(ctx, &ctx->row_mask, &ctx->mask_cap, (size_t)ctx->N))) return rc;
+  if (ctx->Z != ctx->Z_owned.p && (rc = set_rows(ctx, ctx->Z, Rows::DeviceCopy))) return rc;   // borrowed buffer: never written — work on a copy
+  if ((rc = ctx->row_mask.ensure(ctx, (size_t)ctx->N))) return rc;
   HIP_TRY(ctx, hipMemsetAsync(ctx->cnt_d, 0, sizeof(unsigned long long), ctx->stream));
   HIP_TRY(ctx, launch_nan_scan(ctx->Z_owned, ctx->N, ctx->D, ctx->row_mask, ctx->cnt_d, true, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -775,12 +854,7 @@ int mimo_upload(mimo_ctx* ctx, const double* Z_host, int64_t N, int Dz) {
   int rc = bind(ctx); if (rc) return rc;
   if (!Z_host && N > 0) return fail(ctx, MIMO_E_INVALID, "mimo_upload: Z is NULL");
   if ((rc = set_data(ctx, N, Dz))) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->Z_owned) { HIP_TRY(ctx, hipFree(ctx->Z_owned)); ctx->Z_owned = nullptr; }
-  const size_t bytes = (size_t)(N > 0 ? N : 1) * Dz * sizeof(double);
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->Z_owned), bytes));
-  if (N > 0) HIP_TRY(ctx, hipMemcpy(ctx->Z_owned, Z_host, (size_t)N * Dz * sizeof(double), hipMemcpyHostToDevice));
-  ctx->Z = ctx->Z_owned;
+  if ((rc = set_rows(ctx, Z_host, Rows::HostCopy))) return rc;
   return scan_nan_rows(ctx, true);
   });
 }
@@ -799,9 +873,7 @@ int mimo_attach(mimo_ctx* ctx, const double* Z_dev, int64_t N, int Dz) {
   int rc = bind(ctx); if (rc) return rc;
   if (!Z_dev) return fail(ctx, MIMO_E_INVALID, "mimo_attach: Z is NULL");
   if ((rc = set_data(ctx, N, Dz))) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->Z_owned) { HIP_TRY(ctx, hipFree(ctx->Z_owned)); ctx->Z_owned = nullptr; }
-  ctx->Z = Z_dev;
+  if ((rc = set_rows(ctx, Z_dev, Rows::DeviceBorrow))) return rc;
   return scan_nan_rows(ctx, false);
   });
 }
@@ -829,17 +901,17 @@ int mimo_set_row_offset(mimo_ctx* ctx, int64_t row0) {
 
 static int keep_tables(mimo_ctx* ctx, int K, int flags, KernelArgs* a) {
   int rc;
-  const size_t kn = (size_t)K * (size_t)(ctx->N > 0 ? ctx->N : 1);
+  const size_t kn = (size_t)K * (size_t)ctx->N;
   if (flags & MIMO_F_KEEP_RESP) {
-    if ((rc = ensure_dev(ctx, &ctx->resp, &ctx->resp_cap, kn))) return rc;
+    if ((rc = ctx->resp.ensure(ctx, kn))) return rc;
     a->resp = ctx->resp; ctx->resp_K = K; ctx->resp_valid = true;
   }
   if (flags & MIMO_F_KEEP_LOGP) {
-    if ((rc = ensure_dev(ctx, &ctx->logp, &ctx->logp_cap, kn))) return rc;
+    if ((rc = ctx->logp.ensure(ctx, kn))) return rc;
     a->logp = ctx->logp; ctx->logp_K = K; ctx->logp_valid = true;
   }
   if (flags & MIMO_F_KEEP_LSE) {
-    if ((rc = ensure_dev(ctx, &ctx->lse, &ctx->lse_cap, (size_t)(ctx->N > 0 ? ctx->N : 1)))) return rc;
+    if ((rc = ctx->lse.ensure(ctx, (size_t)ctx->N))) return rc;
     a->lse = ctx->lse; ctx->lse_valid = true;
   }
   return MIMO_OK;
@@ -890,19 +962,12 @@ int mimo_estep_weighted(mimo_ctx* ctx, const double* c, const double* b, const d
                 "its weights as a table (mimo_estep + mimo_weighted_stats)", K, ctx->D);
   a.split = (flags & MIMO_F_ENTROPY_SPLIT) ? 1 : 0;
   if ((rc = keep_tables(ctx, K, flags, &a))) return rc;
-  if (flags & MIMO_F_WEIGHTS_RESIDENT) {
-    if (!ctx->weights_resident) return fail(ctx, MIMO_E_STATE, "mimo_estep_weighted: no row weights are resident on the device");
-    a.u = ctx->u_d;
-  } else if (flags & MIMO_F_DEVICE_IN) {
-    a.u = row_weights;
-  } else {
-    const size_t n1 = (size_t)(ctx->N > 0 ? ctx->N : 1);
-    if ((rc = ensure_dev(ctx, &ctx->u_d, &ctx->u_cap, n1))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->u_d, row_weights, (size_t)ctx->N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // pageable host memory
-    a.u = ctx->u_d;
-    ctx->weights_resident = true;
-  }
+  bool copied = false;        // MIMO_F_WEIGHTS_RESIDENT: the weights of the last call, whatever row_weights is
+  if ((rc = stage_input<double>(ctx, (flags & MIMO_F_WEIGHTS_RESIDENT) ? nullptr : row_weights, (size_t)ctx->N, flags, ctx->u_d,
+                                {ctx->u_d, ctx->weights_resident, "mimo_estep_weighted: no row weights are resident on the device"}, K,
+                                &a.u, &copied))) return rc;
+  if (copied) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // pageable host memory
+  if (copied) ctx->weights_resident = true;                      // u_d holds this call's weights
   if ((rc = upload_theta_for(ctx, route, c, b, W, K, &a))) return rc;
   return run_fused(ctx, a, kSrcEstep, flags, S, scalars, route);
   });
@@ -912,13 +977,11 @@ int mimo_wait(mimo_ctx* ctx, double* S, double* scalars) {
   return guarded(ctx, [&]() -> int {
   int rc = bind(ctx); if (rc) return rc;
   if (!ctx->pending_async) return fail(ctx, MIMO_E_STATE, "mimo_wait: no asynchronous call is pending");
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const bool no_block = S && !ctx->pending_stats;      // refused once the call has been waited for; nothing is handed out then
+  const size_t slen = ctx->pending_slen;
+  if ((rc = hand_out(ctx, 0, no_block ? nullptr : S, slen, no_block ? nullptr : scalars, slen, 3))) return rc;
   ctx->pending_async = false;
-  if (S) {
-    if (!ctx->pending_stats) return fail(ctx, MIMO_E_STATE, "mimo_wait: the pending call produced no statistics");
-    memcpy(S, ctx->S_h, ctx->pending_slen * sizeof(double));
-  }
-  if (scalars) memcpy(scalars, ctx->S_h + ctx->pending_slen, 3 * sizeof(double));
+  if (no_block) return fail(ctx, MIMO_E_STATE, "mimo_wait: the pending call produced no statistics");
   return MIMO_OK;
   });
 }
@@ -936,21 +999,13 @@ int mimo_gibbs_labels(mimo_ctx* ctx, const double* c, const double* b, const dou
   a.gibbs = 1;
   a.do_stats = no_stats ? 0 : 1;
   a.seed = seed; a.sweep = sweep;
-  const size_t n1 = (size_t)(ctx->N > 0 ? ctx->N : 1);
-  if ((rc = ensure_dev(ctx, &ctx->labels, &ctx->labels_cap, n1))) return rc;
+  if ((rc = ctx->labels.ensure(ctx, (size_t)ctx->N))) return rc;
   a.labels = ctx->labels; ctx->labels_valid = true;
   if ((rc = keep_tables(ctx, K, flags & (MIMO_F_KEEP_LOGP | MIMO_F_KEEP_LSE), &a))) return rc;
-  if (u) {
-    if (flags & MIMO_F_DEVICE_IN) {
-      a.u = u;
-    } else {
-      if ((rc = ensure_dev(ctx, &ctx->u_d, &ctx->u_cap, n1))) return rc;
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->u_d, u, (size_t)ctx->N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // u is pageable host memory
-      a.u = ctx->u_d;
-      ctx->weights_resident = false;
-    }
-  }
+  bool copied = false;        // (u NULL: the kernel draws its own Philox uniforms)
+  if ((rc = stage_input<double>(ctx, u, (size_t)ctx->N, flags, ctx->u_d, {}, K, &a.u, &copied))) return rc;
+  if (copied) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // u is pageable host memory
+  if (copied) ctx->weights_resident = false;                     // u_d holds uniforms now
   RouteRequest q;
   q.gibbs = true;
   q.tables = (flags & (MIMO_F_KEEP_LOGP | MIMO_F_KEEP_LSE)) != 0;
@@ -973,19 +1028,11 @@ int mimo_weighted_stats(mimo_ctx* ctx, const double* resp, int K, int flags, dou
   if (!S) return fail(ctx, MIMO_E_INVALID, "mimo_weighted_stats: S is NULL");
   KernelArgs a;
   fill_args(ctx, K, &a);
-  if (!resp) {
-    if (!ctx->resp_valid || ctx->resp_K != K)
-      return fail(ctx, MIMO_E_STATE, "mimo_weighted_stats: resp is NULL and no (K=%d,N) table is resident", K);
-    a.resp = ctx->resp;
-  } else if (flags & MIMO_F_DEVICE_IN) {
-    a.resp = const_cast<double*>(resp);
-  } else {
-    const size_t kn = (size_t)K * (size_t)(ctx->N > 0 ? ctx->N : 1);
-    if ((rc = ensure_dev(ctx, &ctx->win, &ctx->win_cap, kn))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->win, resp, (size_t)K * ctx->N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    a.resp = ctx->win;
-  }
+  bool copied = false;
+  if ((rc = stage_input<double>(ctx, resp, (size_t)K * (size_t)ctx->N, flags, ctx->win,
+                                {ctx->resp, ctx->resp_valid && ctx->resp_K == K, "mimo_weighted_stats: resp is NULL and no (K=%d,N) table is resident"},
+                                K, &a.resp, &copied))) return rc;
+  if (copied) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // pageable host memory
   return run_fused(ctx, a, kSrcWeights, flags, S, nullptr, route_for(ctx, K, {kSrcWeights}));
   });
 }
@@ -997,18 +1044,10 @@ int mimo_label_stats(mimo_ctx* ctx, const int32_t* labels, int K, int flags, dou
   if (!S) return fail(ctx, MIMO_E_INVALID, "mimo_label_stats: S is NULL");
   KernelArgs a;
   fill_args(ctx, K, &a);
-  if (!labels) {
-    if (!ctx->labels_valid) return fail(ctx, MIMO_E_STATE, "mimo_label_stats: labels is NULL and none are resident");
-    a.labels = ctx->labels;
-  } else if (flags & MIMO_F_DEVICE_IN) {
-    a.labels = const_cast<int32_t*>(labels);
-  } else {
-    const size_t n1 = (size_t)(ctx->N > 0 ? ctx->N : 1);
-    if ((rc = ensure_dev(ctx, &ctx->lin, &ctx->lin_cap, n1))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->lin, labels, (size_t)ctx->N * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    a.labels = ctx->lin;
-  }
+  bool copied = false;
+  if ((rc = stage_input<int32_t>(ctx, labels, (size_t)ctx->N, flags, ctx->lin,
+                                 {ctx->labels, ctx->labels_valid, "mimo_label_stats: labels is NULL and none are resident"}, K, &a.labels, &copied))) return rc;
+  if (copied) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // pageable host memory
   return run_fused(ctx, a, kSrcLabels, flags, S, nullptr, route_for(ctx, K, {kSrcLabels}));
   });
 }
@@ -1019,32 +1058,18 @@ int mimo_sample_from_log(mimo_ctx* ctx, const double* logp, int K, int64_t N, co
   int rc = bind(ctx); if (rc) return rc;
   if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
   if (K < 1 || N < 0 || !labels_out) return fail(ctx, MIMO_E_INVALID, "mimo_sample_from_log: bad arguments");
-  const double* table = logp;
-  const size_t kn = (size_t)K * (size_t)(N > 0 ? N : 1), n1 = (size_t)(N > 0 ? N : 1);
-  if (!logp) {
-    if (!ctx->logp_valid || ctx->logp_K != K || ctx->N != N)
-      return fail(ctx, MIMO_E_STATE, "mimo_sample_from_log: logp is NULL and no (K=%d, N) log-density table is resident", K);
-    table = ctx->logp;
-  } else if (!(flags & MIMO_F_DEVICE_IN)) {
-    if ((rc = ensure_dev(ctx, &ctx->win, &ctx->win_cap, kn))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->win, logp, (size_t)K * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    table = ctx->win;
-  }
-  const double* ud = nullptr;
-  if (u) {
-    if (flags & MIMO_F_DEVICE_IN) ud = u;
-    else {
-      if ((rc = ensure_dev(ctx, &ctx->u_d, &ctx->u_cap, n1))) return rc;
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->u_d, u, (size_t)N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-      ud = ctx->u_d;
-      ctx->weights_resident = false;
-    }
-  }
+  const double *table = nullptr, *ud = nullptr;
+  bool table_copied = false, u_copied = false;
+  if ((rc = stage_input<double>(ctx, logp, (size_t)K * (size_t)N, flags, ctx->win,
+                                {ctx->logp, ctx->logp_valid && ctx->logp_K == K && ctx->N == N,
+                                 "mimo_sample_from_log: logp is NULL and no (K=%d, N) log-density table is resident"}, K, &table, &table_copied))) return rc;
+  if ((rc = stage_input<double>(ctx, u, (size_t)N, flags, ctx->u_d, {}, K, &ud, &u_copied))) return rc;    // (u NULL: Philox uniforms)
+  if (u_copied) ctx->weights_resident = false;         // u_d holds uniforms now
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // pageable host sources
-  if ((rc = ensure_dev(ctx, &ctx->lin, &ctx->lin_cap, n1))) return rc;
+  if ((rc = ctx->lin.ensure(ctx, (size_t)N))) return rc;
   double* ln_d = nullptr;
   if (lognorms_out) {
-    if ((rc = ensure_dev(ctx, &ctx->lse, &ctx->lse_cap, n1 > (size_t)(ctx->N > 0 ? ctx->N : 1) ? n1 : (size_t)(ctx->N > 0 ? ctx->N : 1)))) return rc;
+    if ((rc = ctx->lse.ensure(ctx, (size_t)std::max(N, ctx->N)))) return rc;      // also long enough for the resident rows: it stays their lse buffer
     ctx->lse_valid = false;      // (the buffer is borrowed: whatever log-normaliser it held is gone)
     ln_d = ctx->lse;
   }
@@ -1063,8 +1088,7 @@ int mimo_random_resp_stats(mimo_ctx* ctx, int K, uint64_t seed, int flags, doubl
   int rc = bind(ctx); if (rc) return rc;
   if ((rc = check_shapes(ctx, K))) return rc;
   if (!S) return fail(ctx, MIMO_E_INVALID, "mimo_random_resp_stats: S is NULL");
-  const size_t kn = (size_t)K * (size_t)(ctx->N > 0 ? ctx->N : 1);
-  if ((rc = ensure_dev(ctx, &ctx->resp, &ctx->resp_cap, kn))) return rc;
+  if ((rc = ctx->resp.ensure(ctx, (size_t)K * (size_t)ctx->N))) return rc;
   ctx->resp_K = K; ctx->resp_valid = true;
   HIP_TRY(ctx, launch_random_resp(ctx->resp, K, ctx->N, seed, ctx->row0, ctx->stream));
   KernelArgs a;
@@ -1078,20 +1102,15 @@ int mimo_table_entropy(mimo_ctx* ctx, const double* table, int64_t count, int fl
   return guarded(ctx, [&]() -> int {
   int rc = bind(ctx); if (rc) return rc;
   if (!out || count < 0) return fail(ctx, MIMO_E_INVALID, "mimo_table_entropy: bad arguments");
-  const double* src = table;
-  if (!table) {
-    if (!ctx->resp_valid) return fail(ctx, MIMO_E_STATE, "mimo_table_entropy: table is NULL and no resp table is resident");
-    src = ctx->resp;
-    count = (int64_t)ctx->resp_K * ctx->N;
-  } else if (!(flags & MIMO_F_DEVICE_IN)) {
-    if ((rc = ensure_dev(ctx, &ctx->win, &ctx->win_cap, (size_t)(count > 0 ? count : 1)))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->win, table, (size_t)count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    src = ctx->win;
-  }
+  const double* src = nullptr;
+  bool copied = false;
+  if ((rc = stage_input<double>(ctx, table, (size_t)count, flags, ctx->win,
+                                {ctx->resp, ctx->resp_valid, "mimo_table_entropy: table is NULL and no resp table is resident"}, 0, &src, &copied))) return rc;
+  if (copied) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // pageable host memory
+  if (!table) count = (int64_t)ctx->resp_K * ctx->N;             // the whole resident table
   const int nblocks = 1024;
-  if ((rc = ensure_dev(ctx, &ctx->partials, &ctx->partials_cap, (size_t)nblocks))) return rc;
-  if ((rc = ensure_dev(ctx, &ctx->reduced, &ctx->reduced_cap, 4))) return rc;
+  if ((rc = ctx->partials.ensure(ctx, (size_t)nblocks))) return rc;
+  if ((rc = ctx->reduced.ensure(ctx, 4))) return rc;
   HIP_TRY(ctx, launch_table_entropy(src, count, ctx->partials, nblocks, ctx->reduced, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(out, ctx->reduced, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1122,12 +1141,12 @@ int mimo_predict_flags(mimo_ctx* ctx, const double* c, const double* b, const do
   if (want_nlpd && (!y || !P || !ld)) return fail(ctx, MIMO_E_INVALID, "mimo_predict: nlpd needs y, P and ld");
   const int dx = ctx->D, dc = dx + (affine ? 1 : 0);
   const int64_t N = ctx->N;
-  const size_t ng = (size_t)K * (1 + dx + (size_t)dx * dx), nM = (size_t)K * dy * dc, nQ = (size_t)K * dc * dc,
+  const size_t ng = packed_len(K, dx), nM = (size_t)K * dy * dc, nQ = (size_t)K * dc * dc,
                nC = (size_t)K * dy * dy;
   const size_t nparam = ng + nM + nQ + 2 * nC + K;
   const size_t nout = dev_out ? 0 : (size_t)N * (dy + ncov + 1), nin = (want_nlpd && !dev_in) ? (size_t)N * dy : 0;
   // parameters | outputs | y, all in the staged-weights workspace
-  if ((rc = ensure_dev(ctx, &ctx->win, &ctx->win_cap, nparam + nout + nin + 1))) return rc;
+  if ((rc = ctx->win.ensure(ctx, nparam + nout + nin + 1))) return rc;
   std::vector<double> h(nparam);
   double* q = h.data();
   for (int k = 0; k < K; ++k) {
@@ -1189,12 +1208,24 @@ static int copy_out(mimo_ctx* ctx, void* dst, const void* src, size_t bytes, boo
   return MIMO_OK;
 }
 
-int mimo_get_resp(mimo_ctx* ctx, double* out) {
+// mimo_get_*: one of the tables a pass left on the device
+enum class Kept { Resp, Logp, Lse, Labels };
+static int get_kept(mimo_ctx* ctx, void* out, Kept which, const char* what) {
   return guarded(ctx, [&]() -> int {
   if (!ctx) return fail(nullptr, MIMO_E_INVALID, "null context");
-  return copy_out(ctx, out, ctx->resp, (size_t)ctx->resp_K * ctx->N * sizeof(double), ctx->resp_valid, "mimo_get_resp");
+  const size_t n = (size_t)ctx->N;
+  switch (which) {
+    case Kept::Resp: return copy_out(ctx, out, ctx->resp, ctx->resp_K * n * sizeof(double), ctx->resp_valid, what);
+    case Kept::Logp: return copy_out(ctx, out, ctx->logp, ctx->logp_K * n * sizeof(double), ctx->logp_valid, what);
+    case Kept::Lse: return copy_out(ctx, out, ctx->lse, n * sizeof(double), ctx->lse_valid, what);
+    default: return copy_out(ctx, out, ctx->labels, n * sizeof(int32_t), ctx->labels_valid, what);
+  }
   });
 }
+int mimo_get_resp(mimo_ctx* ctx, double* out) { return get_kept(ctx, out, Kept::Resp, "mimo_get_resp"); }
+int mimo_get_logp(mimo_ctx* ctx, double* out) { return get_kept(ctx, out, Kept::Logp, "mimo_get_logp"); }
+int mimo_get_lse(mimo_ctx* ctx, double* out) { return get_kept(ctx, out, Kept::Lse, "mimo_get_lse"); }
+int mimo_get_labels(mimo_ctx* ctx, int32_t* out) { return get_kept(ctx, out, Kept::Labels, "mimo_get_labels"); }
 int mimo_get_resp_columns(mimo_ctx* ctx, const int64_t* cols, int64_t ncols, double* out) {
   return guarded(ctx, [&]() -> int {
   int rc = bind(ctx); if (rc) return rc;
@@ -1204,8 +1235,8 @@ int mimo_get_resp_columns(mimo_ctx* ctx, const int64_t* cols, int64_t ncols, dou
   for (int64_t j = 0; j < ncols; ++j)
     if (cols[j] < 0 || cols[j] >= ctx->N) return fail(ctx, MIMO_E_INVALID, "mimo_get_resp_columns: column %lld outside [0, N)", (long long)cols[j]);
   const size_t K = (size_t)ctx->resp_K, words = (size_t)ncols + K * (size_t)ncols;      // indices | gathered block, in the staged-labels / weights workspace
-  if ((rc = ensure_dev(ctx, &ctx->table_tmp, &ctx->table_tmp_cap, words))) return rc;
-  int64_t* cols_d = reinterpret_cast<int64_t*>(ctx->table_tmp);
+  if ((rc = ctx->table_tmp.ensure(ctx, words))) return rc;
+  int64_t* cols_d = reinterpret_cast<int64_t*>(ctx->table_tmp.p);
   double* out_d = ctx->table_tmp + ncols;
   HIP_TRY(ctx, hipMemcpyAsync(cols_d, cols, (size_t)ncols * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, launch_gather_columns(ctx->resp, (int)K, ctx->N, cols_d, ncols, out_d, ctx->stream));
@@ -1214,25 +1245,6 @@ int mimo_get_resp_columns(mimo_ctx* ctx, const int64_t* cols, int64_t ncols, dou
   return MIMO_OK;
   });
 }
-int mimo_get_logp(mimo_ctx* ctx, double* out) {
-  return guarded(ctx, [&]() -> int {
-  if (!ctx) return fail(nullptr, MIMO_E_INVALID, "null context");
-  return copy_out(ctx, out, ctx->logp, (size_t)ctx->logp_K * ctx->N * sizeof(double), ctx->logp_valid, "mimo_get_logp");
-  });
-}
-int mimo_get_lse(mimo_ctx* ctx, double* out) {
-  return guarded(ctx, [&]() -> int {
-  if (!ctx) return fail(nullptr, MIMO_E_INVALID, "null context");
-  return copy_out(ctx, out, ctx->lse, (size_t)ctx->N * sizeof(double), ctx->lse_valid, "mimo_get_lse");
-  });
-}
-int mimo_get_labels(mimo_ctx* ctx, int32_t* out) {
-  return guarded(ctx, [&]() -> int {
-  if (!ctx) return fail(nullptr, MIMO_E_INVALID, "null context");
-  return copy_out(ctx, out, ctx->labels, (size_t)ctx->N * sizeof(int32_t), ctx->labels_valid, "mimo_get_labels");
-  });
-}
-
 int mimo_nan_info(mimo_ctx* ctx, int64_t* n_bad, double* row_mask_out, int K, int64_t* label_counts) {
   return guarded(ctx, [&]() -> int {
     int rc = bind(ctx); if (rc) return rc;
@@ -1251,7 +1263,7 @@ int mimo_nan_info(mimo_ctx* ctx, int64_t* n_bad, double* row_mask_out, int K, in
       if (ctx->n_bad > 0) {
         if (ctx->bad_counts_K != K) return fail(ctx, MIMO_E_STATE, "mimo_nan_info: no label pass with K = %d has run on this data", K);
         unsigned long long h[256];
-        HIP_TRY(ctx, hipMemcpyAsync(h, ctx->cnt_d + 1, (size_t)K * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h, ctx->cnt_d + kCntLabels, (size_t)K * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         for (int k = 0; k < K; ++k) label_counts[k] = (int64_t)h[k];
       }
@@ -1265,8 +1277,8 @@ int mimo_shader_clock_mhz(mimo_ctx* ctx, double* mhz) {
     int rc = bind(ctx); if (rc) return rc;
     if (!mhz) return fail(ctx, MIMO_E_INVALID, "mimo_shader_clock_mhz: out is NULL");
     const int grid = ctx->num_cu * 4;
-    if ((rc = ensure_dev(ctx, &ctx->partials, &ctx->partials_cap, (size_t)grid * 2))) return rc;
-    unsigned long long* d = reinterpret_cast<unsigned long long*>(ctx->partials);
+    if ((rc = ctx->partials.ensure(ctx, (size_t)grid * 2))) return rc;
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(ctx->partials.p);
     HIP_TRY(ctx, launch_clock_probe(d, grid, 20000, ctx->stream));      // ~0.3 ms of v_fma_f64 on every SIMD
     std::vector<unsigned long long> h((size_t)grid * 2);
     HIP_TRY(ctx, hipMemcpyAsync(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
@@ -1299,7 +1311,7 @@ int mimo_lane_exchange_selftest(mimo_ctx* ctx, int* mismatches) {
         v[64 * r + l] = r == 0 ? 1.37 * l - 20.5 + 1e-9 * l * l : r == 4 ? (__builtin_popcount(l) & 1 ? -0.0 : 0.0) : special[(l * (2 * r + 5) + 3 * r) % NS];
         iv[64 * r + l] = r == 0 ? l : (int)(2654435761u * (unsigned)(64 * r + l + 1)) >> (r == 1 ? 3 : 8);      // (sums of two stay inside int)
       }
-    if ((rc = ensure_dev(ctx, &ctx->partials, &ctx->partials_cap, (size_t)64 * R + 32 * R + 1))) return rc;
+    if ((rc = ctx->partials.ensure(ctx, (size_t)64 * R + 32 * R + 1))) return rc;
     double* dv = ctx->partials;
     int* div = reinterpret_cast<int*>(dv + 64 * R);
     unsigned int* dout = reinterpret_cast<unsigned int*>(dv + 64 * R + 32 * R);
@@ -1360,35 +1372,20 @@ int mimo_tune(mimo_ctx* ctx, const char* key, int64_t value) {
   return guarded(ctx, [&]() -> int {
     if (!ctx || !key) return fail(ctx, MIMO_E_INVALID, "mimo_tune: null argument");
     if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
-    if (!strcmp(key, "num_cu")) {
-      if (value < 0 || value > 4096) return fail(ctx, MIMO_E_INVALID, "mimo_tune: num_cu = %lld outside [0, 4096]", (long long)value);
-      ctx->num_cu = value == 0 ? ctx->hw_num_cu : (int)value;
-      return MIMO_OK;
-    }
-    if (!strcmp(key, "resp_skip_log2")) {
-      if (value < 0 || value > 1000) return fail(ctx, MIMO_E_INVALID, "mimo_tune: resp_skip_log2 = %lld outside [0, 1000]", (long long)value);
-      ctx->resp_skip_log2 = (int)value;
-      return MIMO_OK;
-    }
-    if (!strcmp(key, "sorted_range")) {
-      if (value < 0 || value > 80) return fail(ctx, MIMO_E_INVALID, "mimo_tune: sorted_range = %lld outside [0, 80]", (long long)value);
-      set_sorted_range_cap((int)value);
-      return MIMO_OK;
-    }
-    if (!strcmp(key, "narrow_big_vi")) {
-      if (value < 0 || value > 256) return fail(ctx, MIMO_E_INVALID, "mimo_tune: narrow_big_vi = %lld outside [0, 256]", (long long)value);
-      set_narrow_big_vi((int)value);
-      return MIMO_OK;
-    }
     RouteTunables& t = g_route_tunables;     // process-wide, as sorted_range and narrow_big_vi (include/mimo_hip.h)
-    const struct { const char* key; int* knob; } mid_keys[] = {{"mid_labels_narrow_k", &t.mid_labels_narrow_k}, {"mid_labels_min_d", &t.mid_labels_min_d},
-                                                              {"mid_narrow_k", &t.mid_narrow_k}, {"mid_min_d", &t.mid_min_d}};
-    for (const auto& m : mid_keys)
-      if (!strcmp(key, m.key)) {
-        if (value < 0 || value > 64) return fail(ctx, MIMO_E_INVALID, "mimo_tune: %s = %lld outside [0, 64]", key, (long long)value);
-        *m.knob = (int)value;
-        return MIMO_OK;
-      }
+    const struct { const char* key; int max; int* knob; } keys[] = {
+        {"num_cu", 4096, nullptr}, {"resp_skip_log2", 1000, &ctx->resp_skip_log2}, {"sorted_range", 80, nullptr}, {"narrow_big_vi", 256, nullptr},
+        {"mid_labels_narrow_k", 64, &t.mid_labels_narrow_k}, {"mid_labels_min_d", 64, &t.mid_labels_min_d},
+        {"mid_narrow_k", 64, &t.mid_narrow_k}, {"mid_min_d", 64, &t.mid_min_d}};
+    for (const auto& m : keys) {
+      if (strcmp(key, m.key)) continue;
+      if (value < 0 || value > m.max) return fail(ctx, MIMO_E_INVALID, "mimo_tune: %s = %lld outside [0, %d]", key, (long long)value, m.max);
+      if (m.knob) *m.knob = (int)value;
+      else if (!strcmp(key, "num_cu")) ctx->num_cu = value == 0 ? ctx->hw_num_cu : (int)value;
+      else if (!strcmp(key, "sorted_range")) set_sorted_range_cap((int)value);
+      else set_narrow_big_vi((int)value);
+      return MIMO_OK;
+    }
     return fail(ctx, MIMO_E_INVALID, "mimo_tune: unknown key '%s'", key);
   });
 }
@@ -1575,18 +1572,15 @@ int mimo_upload_batched(mimo_ctx* ctx, const double* Z_host, const int64_t* row_
     wg_off[(size_t)b + 1] = (int32_t)work.size();
   }
   if ((rc = set_data(ctx, N, Dz))) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->Z_owned) { HIP_TRY(ctx, hipFree(ctx->Z_owned)); ctx->Z_owned = nullptr; }
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->Z_owned), (size_t)(N > 0 ? N : 1) * Dz * sizeof(double)));
-  if (N > 0) HIP_TRY(ctx, hipMemcpy(ctx->Z_owned, Z_host, (size_t)N * Dz * sizeof(double), hipMemcpyHostToDevice));
-  ctx->Z = ctx->Z_owned;
+  if ((rc = set_rows(ctx, Z_host, Rows::HostCopy))) return rc;
   ctx->n_bad = 0; ctx->bad_counts_K = 0; ctx->data_sum_valid = false;
-  void* olds[] = {ctx->batch_row_off_d, ctx->batch_work_d, ctx->batch_wg_off_d};
-  for (void* o : olds) if (o) HIP_TRY(ctx, hipFree(o));
-  ctx->batch_row_off_d = nullptr; ctx->batch_work_d = nullptr; ctx->batch_wg_off_d = nullptr;
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->batch_row_off_d), ((size_t)B + 1) * sizeof(int64_t)));
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->batch_work_d), std::max<size_t>(work.size(), 1) * sizeof(BatchedWork)));
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->batch_wg_off_d), ((size_t)B + 1) * sizeof(int32_t)));
+  // the three tables are replaced wholesale: each is as long as this batch needs
+  HIP_TRY(ctx, ctx->batch_row_off_d.release());
+  HIP_TRY(ctx, ctx->batch_work_d.release());
+  HIP_TRY(ctx, ctx->batch_wg_off_d.release());
+  if ((rc = ctx->batch_row_off_d.ensure(ctx, (size_t)B + 1))) return rc;
+  if ((rc = ctx->batch_work_d.ensure(ctx, work.size()))) return rc;
+  if ((rc = ctx->batch_wg_off_d.ensure(ctx, (size_t)B + 1))) return rc;
   HIP_TRY(ctx, hipMemcpy(ctx->batch_row_off_d, row_off, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
   if (!work.empty()) HIP_TRY(ctx, hipMemcpy(ctx->batch_work_d, work.data(), work.size() * sizeof(BatchedWork), hipMemcpyHostToDevice));
   HIP_TRY(ctx, hipMemcpy(ctx->batch_wg_off_d, wg_off.data(), ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -1649,28 +1643,22 @@ int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const do
   if ((rc = batched_theta(ctx, c, b, W, K, nullptr, 0, "mimo_estep_batched"))) return rc;
 
   const int G = ctx->batch_G;
-  const size_t pstride = (size_t)16 * K16 * F16 + 4;
-  if ((rc = ensure_dev(ctx, &ctx->partials, &ctx->partials_cap, pstride * (size_t)std::max(G, 1)))) return rc;
+  if ((rc = ctx->partials.ensure(ctx, partial_stride(K16, F16) * (size_t)std::max(G, 1)))) return rc;
   const bool keep_lse = (flags & MIMO_F_KEEP_LSE) != 0;
-  if (keep_lse && (rc = ensure_dev(ctx, &ctx->lse, &ctx->lse_cap, (size_t)(ctx->N > 0 ? ctx->N : 1)))) return rc;
+  if (keep_lse && (rc = ctx->lse.ensure(ctx, (size_t)ctx->N))) return rc;
   ctx->lse_valid = keep_lse;
   ctx->resp_valid = ctx->logp_valid = ctx->labels_valid = false;
   BatchedArgs a = batched_args(ctx, K);
   a.lse = keep_lse ? ctx->lse : nullptr;
   a.do_stats = no_stats ? 0 : 1;
   HIP_TRY(ctx, launch_batched(a, G, ctx->stream));
-  const size_t slen = (size_t)K * (1 + D + (size_t)D * D), out = (no_stats ? 0 : slen * B) + 3 * (size_t)B;
-  if ((rc = ensure_dev(ctx, &ctx->S_d, &ctx->S_cap, out))) return rc;
-  if ((rc = ensure_pinned(ctx, &ctx->S_h, &ctx->S_hcap, out))) return rc;
-  double* sc_d = ctx->S_d + (no_stats ? 0 : slen * B);
+  const size_t nstats = no_stats ? 0 : packed_len(K, D) * B, out = nstats + 3 * (size_t)B;
+  if ((rc = ensure_block(ctx, out))) return rc;
+  double* sc_d = ctx->S_d + nstats;
   const int split = (flags & (MIMO_F_ENTROPY_SPLIT | MIMO_F_KEEP_LSE)) ? 1 : 0;
   HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, D, F, F16, split,
                                      no_stats ? nullptr : ctx->S_d, sc_d, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->S_h, ctx->S_d, out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (!no_stats) memcpy(S, ctx->S_h, slen * B * sizeof(double));
-  memcpy(scalars, ctx->S_h + (no_stats ? 0 : slen * B), 3 * (size_t)B * sizeof(double));
-  return MIMO_OK;
+  return hand_out(ctx, out, no_stats ? nullptr : S, nstats, scalars, nstats, 3 * (size_t)B);
   });
 }
 
@@ -1678,16 +1666,12 @@ int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const do
 // just queued are reduced per problem into S (B x K(1+Dz+Dz^2)); the scalars the reduction also writes are not returned.
 static int batched_label_stats_out(mimo_ctx* ctx, int K, double* S) {
   const int D = ctx->D, B = ctx->batch_B;
-  const size_t slen = (size_t)K * (1 + D + (size_t)D * D), out = slen * B + 3 * (size_t)B;
+  const size_t nstats = packed_len(K, D) * B;
   int rc;
-  if ((rc = ensure_dev(ctx, &ctx->S_d, &ctx->S_cap, out))) return rc;
-  if ((rc = ensure_pinned(ctx, &ctx->S_h, &ctx->S_hcap, out))) return rc;
+  if ((rc = ensure_block(ctx, nstats + 3 * (size_t)B))) return rc;
   HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, D, ctx->F, ctx->F16, 0,
-                                     ctx->S_d, ctx->S_d + slen * B, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->S_h, ctx->S_d, slen * B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(S, ctx->S_h, slen * B * sizeof(double));
-  return MIMO_OK;
+                                     ctx->S_d, ctx->S_d + nstats, ctx->stream));
+  return hand_out(ctx, nstats, S, nstats, nullptr, 0, 0);
 }
 
 int mimo_gibbs_labels_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K,
@@ -1706,23 +1690,20 @@ int mimo_gibbs_labels_batched(mimo_ctx* ctx, const double* c, const double* b, c
                 "seed per problem)");
   const int B = ctx->batch_B, G = ctx->batch_G;
   const int64_t N = ctx->N;
-  const size_t n1 = (size_t)(N > 0 ? N : 1);
   // the seeds travel behind the operand image, in its transfer
   if ((rc = batched_theta(ctx, c, b, W, K, u ? nullptr : seeds, u ? 0 : (size_t)B, "mimo_gibbs_labels_batched"))) return rc;
   const size_t count = (size_t)((K + 15) / 16) * (ctx->F16 / 4) * 64 * B;
-  if ((rc = ensure_dev(ctx, &ctx->labels, &ctx->labels_cap, n1))) return rc;
-  if (u) {
-    if ((rc = ensure_dev(ctx, &ctx->u_d, &ctx->u_cap, n1))) return rc;
-    if (N > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->u_d, u, (size_t)N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // u is pageable host memory
-    ctx->weights_resident = false;
-  }
-  const size_t pstride = (size_t)16 * ((K + 15) / 16) * ctx->F16 + 4;
-  if ((rc = ensure_dev(ctx, &ctx->partials, &ctx->partials_cap, pstride * (size_t)std::max(G, 1)))) return rc;
+  if ((rc = ctx->labels.ensure(ctx, (size_t)N))) return rc;
+  const double* ud = nullptr;
+  bool copied = false;        // (u NULL: Philox uniforms from the seeds; the flags admit no MIMO_F_DEVICE_IN)
+  if ((rc = stage_input<double>(ctx, u, (size_t)N, flags, ctx->u_d, {}, K, &ud, &copied))) return rc;
+  if (copied) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // u is pageable host memory
+  if (copied) ctx->weights_resident = false;                     // u_d holds uniforms now
+  if ((rc = ctx->partials.ensure(ctx, partial_stride((K + 15) / 16, ctx->F16) * (size_t)std::max(G, 1)))) return rc;
   ctx->resp_valid = ctx->logp_valid = ctx->lse_valid = false;
   BatchedArgs a = batched_args(ctx, K);
   a.do_stats = no_stats ? 0 : 1;
-  a.u = u ? ctx->u_d : nullptr;
+  a.u = ud;
   a.seeds = u ? nullptr : reinterpret_cast<const uint64_t*>(ctx->theta_d + count);
   a.labels = ctx->labels;
   a.sweep = sweep;
@@ -1745,23 +1726,18 @@ int mimo_label_stats_batched(mimo_ctx* ctx, const int32_t* labels, int K, int fl
   if (!S) return fail(ctx, MIMO_E_INVALID, "mimo_label_stats_batched: S is NULL");
   const int64_t N = ctx->N;
   const int G = ctx->batch_G;
-  const int32_t* lab = ctx->labels;
-  if (!labels) {
-    if (!ctx->labels_valid || !ctx->labels)
-      return fail(ctx, MIMO_E_STATE, "mimo_label_stats_batched: labels is NULL and no batched draw is resident");
-  } else {
-    for (int64_t n = 0; n < N; ++n)
-      if (labels[n] < 0 || labels[n] >= K)
-        return fail(ctx, MIMO_E_INVALID, "mimo_label_stats_batched: label %d of row %lld outside [0, %d)", labels[n],
-                    (long long)n, K);
-    const size_t n1 = (size_t)(N > 0 ? N : 1);
-    if ((rc = ensure_dev(ctx, &ctx->lin, &ctx->lin_cap, n1))) return rc;
-    if (N > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->lin, labels, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // labels is pageable host memory
-    lab = ctx->lin;
-  }
-  const size_t pstride = (size_t)16 * ((K + 15) / 16) * ctx->F16 + 4;
-  if ((rc = ensure_dev(ctx, &ctx->partials, &ctx->partials_cap, pstride * (size_t)std::max(G, 1)))) return rc;
+  // the kernel indexes its accumulators by label: the caller's labels are checked on the host, before anything is staged
+  for (int64_t n = 0; labels && n < N; ++n)
+    if (labels[n] < 0 || labels[n] >= K)
+      return fail(ctx, MIMO_E_INVALID, "mimo_label_stats_batched: label %d of row %lld outside [0, %d)", labels[n],
+                  (long long)n, K);
+  const int32_t* lab = nullptr;
+  bool copied = false;        // (flags is 0: the labels are the resident draw or host memory)
+  if ((rc = stage_input<int32_t>(ctx, labels, (size_t)N, flags, ctx->lin,
+                                 {ctx->labels, ctx->labels_valid && ctx->labels, "mimo_label_stats_batched: labels is NULL and no batched draw is resident"},
+                                 K, &lab, &copied))) return rc;
+  if (copied) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // labels is pageable host memory
+  if ((rc = ctx->partials.ensure(ctx, partial_stride((K + 15) / 16, ctx->F16) * (size_t)std::max(G, 1)))) return rc;
   BatchedArgs a = batched_args(ctx, K);
   a.labels = const_cast<int32_t*>(lab);
   HIP_TRY(ctx, launch_batched_labels(a, kBatchedGiven, G, ctx->stream));

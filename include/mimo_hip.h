@@ -331,6 +331,32 @@ int mimo_gibbs_labels_batched(mimo_ctx* ctx, const double* c, const double* b, c
  * Coverage, the batch, the communicator and the determinism rule: those of mimo_estep_batched. */
 int mimo_label_stats_batched(mimo_ctx* ctx, const int32_t* labels, int K, int flags, double* S);
 
+/* Statistics of arbitrary weights of all B problems of a batched context: S (B, K(1+Dz+Dz²)), per problem b what
+ * mimo_weighted_stats returns for its rows alone.
+ * Replaces: per problem, weighted_statistics(data, weights) (gaussian.py:491-502, lingauss.py:306-322,
+ *   categorical.py:41-43) of weights that do not come from a softmax pass — the drivers' randomize=True start with the
+ *   host draw (mimo/mixtures/gmm.py:265-267, ilr.py:200-202: resp = rand(K, N); resp /= resp.sum(0)) of B reference jobs.
+ * resp: K N_total doubles on the host, the problems' K-major tables back to back: problem b's (K, N_b) block starts at
+ *   element K row_off[b], its entry (k, n) at K row_off[b] + k N_b + n.  The values are taken as they are (they need not
+ *   be normalised or positive).  NULL: the table the last mimo_random_resp_stats_batched left on the device, which must
+ *   have this K (MIMO_E_STATE if there is none).  flags: 0.  S NULL: MIMO_E_INVALID.
+ * Coverage, the batch, the communicator and the determinism rule (a problem's block does not depend on the rest of the
+ * batch, bit for bit): those of mimo_estep_batched. */
+int mimo_weighted_stats_batched(mimo_ctx* ctx, const double* resp, int K, int flags, double* S);
+
+/* Statistics of RANDOM initial responsibilities of all B problems, generated on the device in one launch: per problem b
+ * what mimo_random_resp_stats(seed = seeds[b]) returns for its rows alone at row offset 0.
+ * Replaces: per problem, the drivers' randomize=True start (mimo/mixtures/gmm.py:265-267, ilr.py:200-202:
+ *   resp = rand(K, N); resp /= resp.sum(0); weighted_statistics — gaussian.py:491-502, lingauss.py:306-322,
+ *   categorical.py:41-43) without K N_total host uniforms going over PCIe.
+ * r[k, n] = v_kn / sum_j v_jn with v_kn the Philox4x32-10 uniform of key seeds[b], counter (local row n, k), plus 2^-53;
+ *   the sum runs over k ascending, then one reciprocal: the bits of mimo_random_resp_stats' table.  seeds: B keys (host).
+ * The table stays resident in the layout of mimo_weighted_stats_batched (mimo_get_resp returns its K N_total doubles;
+ *   mimo_weighted_stats_batched with resp = NULL its statistics) until the next softmax pass, label pass or upload.
+ * flags: 0.  S or seeds NULL: MIMO_E_INVALID.  Coverage, the batch, the communicator and the determinism rule: those of
+ * mimo_estep_batched. */
+int mimo_random_resp_stats_batched(mimo_ctx* ctx, int K, const uint64_t* seeds, int flags, double* S);
+
 /* ---- copy-outs of device-resident tables ----------------------------------------------- */
 int mimo_get_resp(mimo_ctx* ctx, double* resp_host /* K×N */);
 /* The columns `cols[0 .. ncols)` (row indices of the data) of the resident responsibility table: out (K, ncols) row-major.  What a

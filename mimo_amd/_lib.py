@@ -37,6 +37,8 @@ SIGNATURES = {
     "mimo_estep_batched": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "mimo_gibbs_labels_batched": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_uint64, _vp, C.c_int, _vp, _vp]),
     "mimo_label_stats_batched": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
+    "mimo_weighted_stats_batched": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
+    "mimo_random_resp_stats_batched": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
     "mimo_estep_weighted": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "mimo_wait": (C.c_int, [_vp, _vp, _vp]),
     "mimo_gibbs_labels": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_uint64, C.c_uint64, _vp,

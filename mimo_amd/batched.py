@@ -1,5 +1,6 @@
-"""BatchedHipEngine — one softmax pass or one Gibbs label pass over B independent problems (mimo_upload_batched /
-mimo_estep_batched / mimo_gibbs_labels_batched / mimo_label_stats_batched).
+"""BatchedHipEngine — one softmax pass, one Gibbs label pass or one table pass over B independent problems
+(mimo_upload_batched / mimo_estep_batched / mimo_gibbs_labels_batched / mimo_label_stats_batched /
+mimo_weighted_stats_batched / mimo_random_resp_stats_batched).
 
 B problems share Dz and K; each has its own rows and its own (c, b, W).  Where the reference fits many models with
 joblib (examples/ilr/evaluate_sinc_parallel.py: one ILR fit per train split) or random restarts, every pass of every
@@ -145,6 +146,65 @@ class BatchedHipEngine:
         S = np.empty((self.B, K, 1 + D + D * D))
         self._check(self._lib.mimo_label_stats_batched(self._ctx, p, K, 0, _ptr(S)))
         return [SuffStats.from_packed(S[i], K, D) for i in range(self.B)]
+
+    def _tables(self, tables):
+        """B (K, N_b) weight tables -> (the concatenated K-major blocks, K); raises ValueError before any library call."""
+        tables = list(tables)
+        if len(tables) != self.B:
+            raise ValueError(f"tables for {len(tables)} problems, {self.B} uploaded")
+        if not tables:
+            raise ValueError("no batch is uploaded")
+        tables = [_f64(t) for t in tables]
+        if any(t.ndim != 2 for t in tables):
+            raise ValueError("every problem's weights must be (K, N_b)")
+        K = tables[0].shape[0]
+        if any(t.shape[0] != K for t in tables):
+            raise ValueError(f"the problems' tables differ in K: {[t.shape[0] for t in tables]}")
+        for i, t in enumerate(tables):
+            if t.shape[1] != self.row_off[i + 1] - self.row_off[i]:
+                raise ValueError("weights must be (K, N_b): one column per datum")
+        flat = np.concatenate([t.reshape(-1) for t in tables])
+        return (np.ascontiguousarray(flat) if flat.size else np.zeros(1)), int(K)
+
+    def weighted_stats(self, tables=None, K=None):
+        """Statistics of arbitrary weights: a list of B arrays (K, N_b), one K for all problems (taken as they are), or
+        None for the table the last random_resp_stats left on the device (K: its K).  Returns a list of B SuffStats —
+        per problem what HipEngine.weighted_stats returns for its rows alone."""
+        if tables is None:
+            if K is None:
+                raise ValueError("weighted_stats of the resident table needs its K")
+            p, K = None, int(K)
+        else:
+            flat, K = self._tables(tables)
+            p = _ptr(flat)
+        D = self.D
+        S = np.empty((self.B, K, 1 + D + D * D))
+        self._check(self._lib.mimo_weighted_stats_batched(self._ctx, p, K, 0, _ptr(S)))
+        return [SuffStats.from_packed(S[i], K, D) for i in range(self.B)]
+
+    def random_resp_stats(self, K, seeds):
+        """Statistics of random initial responsibilities drawn on the device, all problems in one launch: per problem what
+        HipEngine.random_resp_stats(K, seeds[i]) returns for its rows alone (the same table, bit for bit).  seeds: B Philox
+        keys.  The table stays resident (get_resp, weighted_stats(None, K)).  Returns a list of B SuffStats."""
+        K = int(K)
+        sd = np.ascontiguousarray(np.asarray(seeds).reshape(-1).astype(np.uint64))
+        if sd.shape[0] != self.B:
+            raise ValueError(f"{sd.shape[0]} seeds for {self.B} problems")
+        D = self.D
+        S = np.empty((self.B, K, 1 + D + D * D))
+        self._check(self._lib.mimo_random_resp_stats_batched(self._ctx, K, _ptr(sd), 0, _ptr(S)))
+        self._K = K
+        return [SuffStats.from_packed(S[i], K, D) for i in range(self.B)]
+
+    def get_resp(self, K=None):
+        """The table of the last random_resp_stats, resident on the device: a list of B arrays (K, N_b)."""
+        K = int(K if K is not None else getattr(self, '_K', 0))
+        if K < 1:
+            raise ValueError("get_resp needs the K of the resident table")
+        out = np.empty(max(K * int(self.row_off[-1]), 1))
+        self._check(self._lib.mimo_get_resp(self._ctx, _ptr(out)))
+        ro = self.row_off
+        return [out[K * ro[i]:K * ro[i + 1]].reshape(K, int(ro[i + 1] - ro[i])).copy() for i in range(self.B)]
 
     def get_labels(self):
         """The labels of the last gibbs_labels, resident on the device: a list of B int32 arrays (N_b,)."""

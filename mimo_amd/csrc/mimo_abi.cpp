@@ -1625,6 +1625,7 @@ static BatchedArgs batched_args(mimo_ctx* ctx, int K) {
   a.ZS = (ctx->D + 2) | 1;
   a.do_stats = 1;
   a.u = nullptr; a.seeds = nullptr; a.labels = nullptr; a.sweep = 0;
+  a.resp = nullptr;
   return a;
 }
 
@@ -1742,6 +1743,59 @@ int mimo_label_stats_batched(mimo_ctx* ctx, const int32_t* labels, int K, int fl
   a.labels = const_cast<int32_t*>(lab);
   HIP_TRY(ctx, launch_batched_labels(a, kBatchedGiven, G, ctx->stream));
   return batched_label_stats_out(ctx, K, S);
+  });
+}
+
+// The table pass of a batch (launch_batched_weights over the device table `table`, the problems' K-major (K, N_b) blocks back
+// to back) and its statistics: S (B x K(1+Dz+Dz^2)), reduced like the label passes' (the scalars of the reduction are zeros
+// and are not returned).
+static int batched_table_stats(mimo_ctx* ctx, const double* table, int K, double* S) {
+  const int G = ctx->batch_G;
+  int rc;
+  if ((rc = ctx->partials.ensure(ctx, partial_stride((K + 15) / 16, ctx->F16) * (size_t)std::max(G, 1)))) return rc;
+  BatchedArgs a = batched_args(ctx, K);
+  a.resp = table;
+  HIP_TRY(ctx, launch_batched_weights(a, G, ctx->stream));
+  return batched_label_stats_out(ctx, K, S);
+}
+
+int mimo_weighted_stats_batched(mimo_ctx* ctx, const double* resp, int K, int flags, double* S) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, "mimo_weighted_stats_batched"))) return rc;
+  if (flags != 0) return fail(ctx, MIMO_E_INVALID, "mimo_weighted_stats_batched: flags 0x%x: none are defined", flags);
+  if (!S) return fail(ctx, MIMO_E_INVALID, "mimo_weighted_stats_batched: S is NULL");
+  const double* table = nullptr;
+  bool copied = false;        // (flags is 0: the table is the resident one or host memory; its values are taken as they are)
+  if ((rc = stage_input<double>(ctx, resp, (size_t)K * (size_t)ctx->N, flags, ctx->win,
+                                {ctx->resp, ctx->resp_valid && ctx->resp_K == K && ctx->resp,
+                                 "mimo_weighted_stats_batched: resp is NULL and no (K=%d, N_total) table is resident"},
+                                K, &table, &copied))) return rc;
+  if (copied) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // resp is pageable host memory
+  return batched_table_stats(ctx, table, K, S);
+  });
+}
+
+int mimo_random_resp_stats_batched(mimo_ctx* ctx, int K, const uint64_t* seeds, int flags, double* S) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, "mimo_random_resp_stats_batched"))) return rc;
+  if (flags != 0) return fail(ctx, MIMO_E_INVALID, "mimo_random_resp_stats_batched: flags 0x%x: none are defined", flags);
+  if (!S || !seeds) return fail(ctx, MIMO_E_INVALID, "mimo_random_resp_stats_batched: S and seeds must be non-NULL");
+  const int B = ctx->batch_B;
+  const int64_t N = ctx->N;
+  ctx->resp_valid = false;
+  if ((rc = ctx->resp.ensure(ctx, (size_t)K * (size_t)N))) return rc;
+  // the seeds go the way the label pass sends them: through the operand image's pinned buffer (there is no image here)
+  if ((rc = ctx->theta_d.ensure(ctx, (size_t)B))) return rc;
+  if ((rc = ctx->theta_h.ensure(ctx, (size_t)B))) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));    // the staging buffer may still be in flight from the previous call on this stream
+  memcpy(ctx->theta_h, seeds, (size_t)B * sizeof(uint64_t));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, ctx->theta_h, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, launch_batched_random_resp(ctx->resp, ctx->batch_row_off_d, reinterpret_cast<const uint64_t*>(ctx->theta_d.p), B, K, N,
+                                          ctx->stream));
+  ctx->resp_K = K; ctx->resp_valid = true;
+  return batched_table_stats(ctx, ctx->resp, K, S);
   });
 }
 

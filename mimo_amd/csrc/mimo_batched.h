@@ -1,4 +1,4 @@
-// Internal interface of the batched softmax and Gibbs label passes (mimo_batched.hip): B independent problems that share Dz and K, each with
+// Internal interface of the batched softmax, Gibbs label and table passes (mimo_batched.hip): B independent problems that share Dz and K, each with
 // its own rows and its own (c, b, W), in one launch.  Not installed; the public surface is include/mimo_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -40,11 +40,14 @@ struct BatchedArgs {
   const uint64_t* seeds;      // [B] (Philox draw)
   int32_t* labels;            // (N_total,): the labels drawn (kBatchedDraw) or given (kBatchedGiven)
   uint64_t sweep;
+  // table mode (launch_batched_weights) only
+  const double* resp;         // the problems' K-major (K, N_b) weight tables back to back: problem b's starts at element K row_off[b]
 };
 
 // Label modes of the batched kernel family: the inverse-CDF draw of a Gibbs sweep (with the statistics of the labels
 // drawn), or the statistics of labels given on the device (no L product, no draw).
-enum BatchedLabelMode : int { kBatchedSoftmax = 0, kBatchedDraw = 1, kBatchedGiven = 2 };
+// Table mode: the statistics of a weight table given on the device (no L product, no normalise phase; weights as they are).
+enum BatchedLabelMode : int { kBatchedSoftmax = 0, kBatchedDraw = 1, kBatchedGiven = 2, kBatchedWeights = 3 };
 
 // Tiles per workgroup for a problem of `nrows` rows: a function of the row count alone (the determinism rule: a problem's
 // result does not depend on what else is in the batch).
@@ -55,6 +58,13 @@ hipError_t launch_batched(const BatchedArgs& a, int grid, hipStream_t stream);
 // The label modes (kBatchedDraw / kBatchedGiven) on the same work table; the partial blocks hold the statistics of the labels
 // (one-hot operand, exact counts) and zero scalars.
 hipError_t launch_batched_labels(const BatchedArgs& a, int mode, int grid, hipStream_t stream);
+// The table mode (kBatchedWeights) on the same work table: the partial blocks hold the statistics of a.resp and zero scalars.
+hipError_t launch_batched_weights(const BatchedArgs& a, int grid, hipStream_t stream);
+// Random responsibilities of every problem in one launch, in the layout of BatchedArgs::resp: column n of problem b is
+// random_resp_column (mimo_device.h) with key seeds[b] and the LOCAL row n — the table launch_random_resp writes for the
+// problem's rows alone at row offset 0, bit for bit.  row_off and seeds are device pointers.
+hipError_t launch_batched_random_resp(double* resp, const int64_t* row_off, const uint64_t* seeds, int B, int K, int64_t N_total,
+                                      hipStream_t stream);
 // Per problem: the fixed-order sum of its workgroups' partial blocks [wg_off[b], wg_off[b + 1]), unpacked into
 // S[b] = K x (1 + Dz + Dz^2) (or nothing when S is null) and scalars[b] = {sum lse, sum r l, sum lse - sum r l}
 // (the last two NaN unless `split`).

@@ -23,6 +23,13 @@
 //                  A operand built from the LDS label array (exact integer counts).
 //   kBatchedGiven: labels read from the device (the initial labels of a chain): no L product, no draw, phase 5 as above.
 // No scalars are returned in the label modes (their partial blocks carry zeros there).
+//
+// Table mode (LM = kBatchedWeights, the statistics of a weight table: the drivers' random start, caller-supplied weights),
+// on the same work table, the same LDS plan and the same reduction: phases 1-2 as above; then the weight tile
+// Lt[row][k] is filled from the problem's slice of a device table (a.resp: the problems' K-major (K, N_b) tables back to
+// back, problem b's at element K row_off[b]; exactly 0.0 for rows past the problem's end and for padding components);
+// no L product, no normalise phase; phase 5 is the softmax mode's, its A operand read from Lt.  Zero scalars.
+// batched_random_resp_kernel writes such a table for the whole batch in one launch (random_resp_column of mimo_device.h).
 #include "mimo_batched.h"
 #include "mimo_tile.h"
 
@@ -65,7 +72,9 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
   double* red = Lt + T * LS;                      // [16]     scalar reduction scratch
   double* etab = red + 16;                        // [64]     2^(j/64) for exp_nonpos
   uint8_t* fe = reinterpret_cast<uint8_t*>(etab + 64);   // [F16][2]
-  int* labs = reinterpret_cast<int*>(red);        // [T] labels of the tile (label modes; unused by the softmax)
+  int* labs = reinterpret_cast<int*>(red);        // [T] labels of the tile (label modes; unused by the softmax and the table mode)
+  constexpr bool HAS_L = LM == kBatchedSoftmax || LM == kBatchedDraw;        // L product + normalise phase
+  constexpr bool A_FROM_LT = LM == kBatchedSoftmax || LM == kBatchedWeights;   // phase 5 reads its A operand from Lt
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -129,6 +138,30 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
   store_z(tile0);
   load_z(tile0 + 1);
 
+  // Weight tile staging (table mode): thread (row wrow, component group wgrp) holds the components wgrp + 8 i of its row: a
+  // wave reads 32 consecutive doubles of each of two components per step.  Like the z~ rows, the next tile's weights are
+  // read into registers before the current tile's statistics MFMAs are issued.
+  constexpr int NW = LM == kBatchedWeights ? 2 * K16MAX : 1;
+  const int wrow = tid & (T - 1), wgrp = tid >> 5;
+  double wr[NW];
+  auto load_w = [&](int t) {
+    const int64_t n = (int64_t)t * T + wrow;
+    const double* tb = a.resp + (int64_t)K * rbeg + n;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+      const int k = wgrp + 8 * i;
+      wr[i] = (n < Nb && k < K) ? tb[(int64_t)k * Nb] : 0.0;
+    }
+  };
+  auto store_w = [&]() {
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+      const int k = wgrp + 8 * i;
+      if (k < Kpad) Lt[wrow * LS + k] = wr[i];
+    }
+  };
+  if constexpr (LM == kBatchedWeights) load_w(tile0);
+
   const int frow = tid & (T - 1), fgrp = tid >> 5;
   wg_sync();   // feature and exp tables are in LDS
   uint32_t w[NCB];
@@ -177,9 +210,13 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
     if constexpr (LM == kBatchedGiven) {   // rows past the problem's end get no label: their one-hot row is zero
       if (tid < T) labs[tid] = (n0 + tid) < Nb ? a.labels[rbeg + n0 + tid] : -1;
     }
+    if constexpr (LM == kBatchedWeights) store_w();   // (Lt was last read before the barrier at the top of this step)
     wg_sync();
+    if constexpr (LM == kBatchedWeights) {
+      if (t + 1 < tile0 + ntl) load_w(t + 1);
+    }
 
-    if constexpr (LM != kBatchedGiven) {
+    if constexpr (HAS_L) {
     // ---- L tile = Theta_b Phi': row block rb = wave + 4 h, both 16-row column groups -------------------
     // A lane (i = j, kk = q) = Theta[16 rb + j][4 s + q]; B lane (kk = q, col = j) = Phi[16 g + j][4 s + q];
     // C/D: reg r of lane (q, j) = component 16 rb + q + 4 r, row 16 g + j
@@ -251,11 +288,11 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
       double avq[2][SP], bvq[2][SP];
       auto fetch = [&](int s, int slot) {
         int lab = -1;
-        if constexpr (LM != kBatchedSoftmax) lab = labs[8 * q + s];
+        if constexpr (!A_FROM_LT) lab = labs[8 * q + s];
 #pragma unroll
         for (int i = 0; i < SP; ++i) {
           if (i < npw) {
-            if constexpr (LM == kBatchedSoftmax) avq[slot][i] = Lt[lot[i] + s * LS];
+            if constexpr (A_FROM_LT) avq[slot][i] = Lt[lot[i] + s * LS];
             else avq[slot][i] = lab == lk[i] ? 1.0 : 0.0;
             bvq[slot][i] = Ph[pot[i] + s * RS];
           }
@@ -294,7 +331,7 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
     }
   }
   if constexpr (LM != kBatchedSoftmax) {
-    // no scalars in the label modes (and red, which holds the labels, is left alone)
+    // no scalars in the label and table modes (and red, which holds the labels, is left alone)
     if (tid < 4) Pb[(size_t)Kpad * F16 + tid] = 0.0;
     return;
   }
@@ -403,6 +440,34 @@ hipError_t launch_batched_labels(const BatchedArgs& a, int mode, int grid, hipSt
     return launch_mode<kBatchedGiven>(a, grid, stream);
   }
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_batched_weights(const BatchedArgs& a, int grid, hipStream_t stream) {
+  if (!a.resp) return hipErrorInvalidValue;
+  return launch_mode<kBatchedWeights>(a, grid, stream);
+}
+
+// One thread per row of the concatenated batch: its problem is the last one that starts at or before it (empty problems own no
+// row and are stepped over), its Philox counter the row's index WITHIN the problem.
+__global__ __launch_bounds__(kWG) void batched_random_resp_kernel(double* __restrict__ resp, const int64_t* __restrict__ row_off,
+                                                                  const uint64_t* __restrict__ seeds, int B, int K, int64_t N_total) {
+  const int64_t g = (int64_t)blockIdx.x * kWG + threadIdx.x;
+  if (g >= N_total) return;
+  int lo = 0, hi = B;                       // row_off[lo] <= g < row_off[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (row_off[mid] <= g) lo = mid; else hi = mid;
+  }
+  const int64_t rbeg = row_off[lo], Nb = row_off[lo + 1] - rbeg, n = g - rbeg;
+  random_resp_column(resp + (int64_t)K * rbeg + n, Nb, K, seeds[lo], (uint64_t)n);
+}
+
+hipError_t launch_batched_random_resp(double* resp, const int64_t* row_off, const uint64_t* seeds, int B, int K, int64_t N_total,
+                                      hipStream_t stream) {
+  if (B <= 0 || N_total <= 0) return hipSuccess;
+  hipLaunchKernelGGL(batched_random_resp_kernel, dim3((unsigned)((N_total + kWG - 1) / kWG)), dim3(kWG), 0, stream, resp, row_off,
+                     seeds, B, K, N_total);
+  return hipGetLastError();
 }
 
 hipError_t launch_batched_reduce(const double* partials, const int32_t* wg_off, int B, const uint8_t* feat, int K, int D,

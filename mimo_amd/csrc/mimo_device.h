@@ -51,6 +51,21 @@ __host__ __device__ inline double philox_uniform(uint64_t seed, uint64_t row, ui
   return ((double)(c0 >> 5) * 67108864.0 + (double)(c1 >> 6)) * (1.0 / 9007199254740992.0);
 }
 
+// One column of the random initial responsibilities (random_resp_kernel of mimo_small.hip, batched_random_resp_kernel of
+// mimo_batched.hip): out[k stride] = v_k / sum_j v_j, v_k = the Philox uniform of key `seed`, counter (row, k), moved to
+// (0, 1] (a column of zeros cannot happen).  The sum runs over k ascending, then ONE reciprocal, then v inv: both kernels
+// go through here, so a problem's table is the same bits solo and in a batch.
+__device__ __forceinline__ void random_resp_column(double* __restrict__ out, int64_t stride, int K, uint64_t seed, uint64_t row) {
+  double tot = 0.0;
+  for (int k = 0; k < K; ++k) {
+    const double v = philox_uniform(seed, row, (uint64_t)k) + 1.1102230246251565e-16;
+    out[(int64_t)k * stride] = v;
+    tot += v;
+  }
+  const double inv = 1.0 / tot;
+  for (int k = 0; k < K; ++k) out[(int64_t)k * stride] *= inv;
+}
+
 // ------------------------------------------------------------------------------------------
 // Lane exchanges with a compile-time XOR mask, in registers.  __shfl_xor(v, MASK) is ds_bpermute_b32 per 32-bit word:
 // a per-lane address (v_xor, v_cmp, v_cndmask, v_lshlrev) and a round trip through the LDS pipe, queued behind the

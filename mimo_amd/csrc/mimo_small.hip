@@ -412,15 +412,7 @@ __global__ __launch_bounds__(kWG) void random_resp_kernel(double* __restrict__ r
                                                           int64_t row0) {
   const int64_t n = (int64_t)blockIdx.x * kWG + threadIdx.x;
   if (n >= N) return;
-  double tot = 0.0;
-  for (int k = 0; k < K; ++k) {
-    // (0, 1]: a column of zeros cannot happen
-    const double v = philox_uniform(seed, (uint64_t)(row0 + n), (uint64_t)k) + 1.1102230246251565e-16;
-    resp[(int64_t)k * N + n] = v;
-    tot += v;
-  }
-  const double inv = 1.0 / tot;
-  for (int k = 0; k < K; ++k) resp[(int64_t)k * N + n] *= inv;
+  random_resp_column(resp + n, N, K, seed, (uint64_t)(row0 + n));
 }
 
 hipError_t launch_random_resp(double* resp, int K, int64_t N, uint64_t seed, int64_t row0, hipStream_t stream) {

@@ -17,7 +17,7 @@ import numpy.random as npr
 from mimo_amd.batched import BatchedHipEngine
 from mimo_amd.distributions import native_sweep as _native_sweep
 from mimo_amd.distributions.lingauss import joint_rows
-from mimo_amd.mixtures.gmm import BayesianMixtureOfGaussians, _component_stats, random_start
+from mimo_amd.mixtures.gmm import BayesianMixtureOfGaussians, _component_stats
 from mimo_amd.mixtures.ilr import BayesianMixtureOfLinearGaussians
 
 
@@ -29,12 +29,6 @@ def _rows(model, d):
         return np.ascontiguousarray(np.asarray(d, dtype=float).reshape(-1, model.dim))
     x, y = d
     return np.ascontiguousarray(joint_rows(*model._scaled(x, y)))
-
-
-def _bind(model, d):
-    if isinstance(model, BayesianMixtureOfGaussians):
-        return model._bind(d)
-    return model._bind(*model._scaled(*d))
 
 
 def _begin(model, S):
@@ -75,11 +69,28 @@ def _per_model(values, B, default, what):
     return values
 
 
+def _random_start(engine, K, init_rng, seeds):
+    """random_start (mixtures/gmm.py) of every model in one batched pass over the data the engine holds.
+    init_rng='host'  : numpy.random.rand(K, N_b) per model, in model order — what B solo runs draw one after another;
+    init_rng='philox': drawn on the device, model i from the Philox stream keyed by seeds[i] (counter (row, k))."""
+    if init_rng == 'philox':
+        return engine.random_resp_stats(K, seeds)
+    if init_rng != 'host':
+        raise ValueError(init_rng)
+    tables = []
+    for n in np.diff(engine.row_off):
+        resp = npr.rand(K, int(n))
+        resp /= np.sum(resp, axis=0)
+        tables.append(resp)
+    return engine.weighted_stats(tables)
+
+
 def meanfield_coordinate_descent_batched(models, data, randomize=True, maxiter=250, tol=1e-8, init_rng='host', seeds=None,
                                          sample_likelihood=True, engine=None):
     """models: B BayesianMixtureOfGaussians with data a list of B `obs`, or B BayesianMixtureOfLinearGaussians with data a
     list of B `(x, y)`; one class, one size and one set of dimensions for all.  randomize / init_rng / seeds[i] /
-    sample_likelihood as in the solo drivers (the random start runs on each model's own engine).  engine: a
+    sample_likelihood as in the solo drivers (the random start is one batched table pass: the host draws are made in
+    model order).  engine: a
     BatchedHipEngine (default: a new one on the device of the first model's engine).  Returns the B ELBO traces."""
     models, data, cls = _check_models(models, data)
     B = len(models)
@@ -89,7 +100,7 @@ def meanfield_coordinate_descent_batched(models, data, randomize=True, maxiter=2
     engine.upload([_rows(m, d) for m, d in zip(models, data)])
 
     if randomize:
-        S = [random_start(_bind(m, d), m.size, init_rng, s) for m, d, s in zip(models, data, seeds)]
+        S = _random_start(engine, models[0].size, init_rng, seeds)
     else:
         canons = [m.canonical_expected() for m in models]
         S, _ = engine.estep(*_stack(canons))

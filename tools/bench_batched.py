@@ -2,7 +2,7 @@
 data resident), on the same inputs, after warm-up; wall time per pass (each call returns synchronised host results) and the
 largest relative difference of the outputs.  Writes <out>/bench_batched.json.
 
-    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3]
+    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3] [--start-only | --no-start]
 
 Also times one iteration of meanfield_coordinate_descent_batched against B solo meanfield_iteration calls at shape 1
 (24 ILR models, K = 100, dx = dy = 1), split into host time and pass time.
@@ -10,6 +10,11 @@ Also times one iteration of meanfield_coordinate_descent_batched against B solo 
 Gibbs leg (unless --no-gibbs): per shape, one batched label pass (BatchedHipEngine.gibbs_labels, Philox, statistics on)
 against the B solo HipEngine.gibbs_labels calls; and one resample_batched sweep over the 24 ILR models of shape 1 (host
 uniforms) against 24 solo sweeps, with the largest difference of the sampled parameters after two seeded sweeps.
+
+Start leg (unless --no-start): per shape, the random start of a variational fit — one BatchedHipEngine.random_resp_stats
+and one BatchedHipEngine.weighted_stats (host tables) against the B solo HipEngine calls, batched and solo alternated in the
+same run.  --trace-start SHAPE only runs the two batched start passes a few times (for a kernel trace of the fill kernel
+and the weights mode from outside) and writes nothing.
 
 Shapes: 1. B = 24, N_b = 1600, Dz = 2, K = 100 (the reference's parallel ILR example); 2. B = 64, N_b = 1e4, Dz = 2, K = 4
 (restarts of the toy GMM); 3. B = 8, N_b = 2.5e5, Dz = 12, K = 64 (C4 per model)."""
@@ -126,6 +131,89 @@ def run_gibbs_shape(sid, reps):
     beng.close()
     return {"gibbs_shape": sid, "B": B, "N_b": N, "Dz": D, "K": K, "batched_ms": tb, "solo_sum_ms": ts, "speedup": ts / tb,
             "max_rel_diff": err, "labels_mismatched": mismatched, "solo_profile": prof, "reps": reps}
+
+
+def timed_alternating(fa, fb, reps):
+    """Medians (ms) of fa and fb, called in turn."""
+    for _ in range(2):
+        fa()
+        fb()
+    ta, tb = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fa()
+        t1 = time.perf_counter()
+        fb()
+        t2 = time.perf_counter()
+        ta.append(t1 - t0)
+        tb.append(t2 - t1)
+    return float(np.median(ta)) * 1e3, float(np.median(tb)) * 1e3
+
+
+def start_tables(B, N, K, seed):
+    rng = np.random.default_rng(seed)
+    tables = []
+    for _ in range(B):
+        r = rng.random((K, N))
+        r /= r.sum(axis=0)
+        tables.append(r)
+    return tables
+
+
+def run_start_shape(sid, reps):
+    """The random start: one batched random_resp_stats / weighted_stats (host tables) against the B solo calls."""
+    B, N, D, K = SHAPES[sid]
+    Zs = inputs(B, N, D, K, seed=sid)[0]
+    tables = start_tables(B, N, K, sid)
+    seeds = [1000 + i for i in range(B)]
+    beng = BatchedHipEngine(0)
+    beng.upload(Zs)
+    solos = []
+    for Z in Zs:
+        e = HipEngine(0)
+        e.upload(Z)
+        solos.append(e)
+    out = {}
+
+    def diff(Sb, Ss):
+        err = 0.
+        for x, y in zip(Sb, Ss):
+            for u, v in ((x.n, y.n), (x.sx, y.sx), (x.sxx, y.sxx)):
+                err = max(err, float(np.abs(u - v).max() / max(np.abs(v).max(), 1.)))
+        return err
+
+    def philox_b():
+        out["pb"] = beng.random_resp_stats(K, seeds)
+
+    def philox_s():
+        out["ps"] = [e.random_resp_stats(K, seeds[i]) for i, e in enumerate(solos)]
+
+    def host_b():
+        out["hb"] = beng.weighted_stats(tables)
+
+    def host_s():
+        out["hs"] = [e.weighted_stats(tables[i]) for i, e in enumerate(solos)]
+
+    pb, ps = timed_alternating(philox_b, philox_s, reps)
+    hb, hs = timed_alternating(host_b, host_s, reps)
+    res = {"start_shape": sid, "B": B, "N_b": N, "Dz": D, "K": K,
+           "random_resp_stats": {"batched_ms": pb, "solo_sum_ms": ps, "speedup": ps / pb, "max_rel_diff": diff(out["pb"], out["ps"])},
+           "weighted_stats": {"batched_ms": hb, "solo_sum_ms": hs, "speedup": hs / hb, "max_rel_diff": diff(out["hb"], out["hs"])},
+           "reps": reps}
+    for e in solos:
+        e.close()
+    beng.close()
+    return res
+
+
+def trace_start(sid, reps=5):
+    B, N, D, K = SHAPES[sid]
+    beng = BatchedHipEngine(0)
+    beng.upload(inputs(B, N, D, K, seed=sid)[0])
+    for _ in range(reps):
+        beng.random_resp_stats(K, [1000 + i for i in range(B)])
+        beng.weighted_stats(None, K)
+    beng.close()
 
 
 class _SweepClock:
@@ -271,9 +359,24 @@ def main():
     ap.add_argument("--shapes", default="1,2,3")
     ap.add_argument("--no-driver", action="store_true", help="skip the driver timings (VI iteration, Gibbs sweep)")
     ap.add_argument("--no-gibbs", action="store_true", help="skip the Gibbs leg")
+    ap.add_argument("--no-start", action="store_true", help="skip the start leg")
+    ap.add_argument("--start-only", action="store_true", help="only the start leg")
+    ap.add_argument("--trace-start", type=int, default=0, metavar="SHAPE", help="only run the batched start passes of SHAPE")
     args = ap.parse_args()
+    if args.trace_start:
+        trace_start(args.trace_start)
+        return
     os.makedirs(args.out, exist_ok=True)
+    if args.start_only:
+        res = [run_start_shape(int(s), args.reps) for s in args.shapes.split(",")]
+        for r in res:
+            print(json.dumps(r))
+        with open(os.path.join(args.out, "bench_batched_start.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     res = [run_shape(int(s), args.reps) for s in args.shapes.split(",")]
+    if not args.no_start:
+        res += [run_start_shape(int(s), args.reps) for s in args.shapes.split(",")]
     if not args.no_driver:
         res.append(driver_iteration(min(args.reps, 10)))
     if not args.no_gibbs:

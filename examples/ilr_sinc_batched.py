@@ -5,7 +5,14 @@ by meanfield_coordinate_descent_batched — one batched softmax pass per iterati
 
 --gibbs-iters G > 0 runs the reference job's full flow: a Gibbs warm-up of G sweeps from random labels, each model on its
 own numpy stream seeded like its joblib worker (resample_batched, numpy_seeds = 0 .. fits - 1; one batched label pass per
-sweep), then mean-field VI from the sampled parameters (randomize=False)."""
+sweep), then mean-field VI from the sampled parameters (randomize=False).
+
+--svi-iters N > 0 runs the reference job's DEFAULT inference instead of coordinate descent (its --stochastic flow): after
+the Gibbs warm-up, if one is asked for, N outer iterations of stochastic VI with minibatches of --svi-batch rows
+(meanfield_stochastic_descent_batched, randomize=False, step size 0.5): per iteration one batched pass over the rows
+every model drew — gathered on the device from the resident data — and one over all rows for the bounds.  Each model's numpy
+stream is seeded like its joblib worker (0 .. fits - 1); the workers leave Python's `random`, which draws the minibatches,
+unseeded, and here each model gets a stream of its own seeded the same way, so a run is reproducible."""
 import argparse
 import os
 import sys
@@ -20,7 +27,8 @@ from mimo_amd.distributions import (TruncatedStickBreaking, CategoricalWithStick
                                     StackedLinearGaussiansWithMatrixNormalWisharts)
 from mimo_amd.engine import HipEngine
 from mimo_amd.mixtures import BayesianMixtureOfLinearGaussians
-from mimo_amd.mixtures.batched import meanfield_coordinate_descent_batched, resample_batched
+from mimo_amd.mixtures.batched import (meanfield_coordinate_descent_batched, meanfield_stochastic_descent_batched,
+                                        resample_batched)
 
 
 def make_model(K, engine):
@@ -44,6 +52,8 @@ def main():
     ap.add_argument("--experts", type=int, default=100)
     ap.add_argument("--iters", type=int, default=250)
     ap.add_argument("--gibbs-iters", type=int, default=0, help="Gibbs warm-up sweeps before VI (0: random VI start)")
+    ap.add_argument("--svi-iters", type=int, default=0, help="outer iterations of stochastic VI (0: coordinate-descent VI)")
+    ap.add_argument("--svi-batch", type=int, default=256, help="rows per minibatch of stochastic VI")
     args = ap.parse_args()
     rng = np.random.default_rng(1337)
     x = rng.uniform(-10., 10., size=(args.rows, 1))
@@ -62,6 +72,11 @@ def main():
         resample_batched(models, data, init_labels='random', maxiter=args.gibbs_iters, numpy_seeds=range(args.fits))
         gibbs = time.perf_counter() - t0
         print(f"Gibbs warm-up: {args.gibbs_iters} sweeps of {args.fits} models in {gibbs:.2f} s")
+    if args.svi_iters > 0:
+        vlbs = meanfield_stochastic_descent_batched(models, data, randomize=False, maxiter=args.svi_iters, step_size=0.5,
+                                                    batch_size=args.svi_batch, numpy_seeds=range(args.fits),
+                                                    python_seeds=range(args.fits))
+    elif args.gibbs_iters > 0:
         vlbs = meanfield_coordinate_descent_batched(models, data, randomize=False, maxiter=args.iters, tol=1e-6)
     else:
         vlbs = meanfield_coordinate_descent_batched(models, data, randomize=True, init_rng='philox', seeds=range(args.fits),

@@ -306,6 +306,28 @@ int mimo_upload_batched(mimo_ctx* ctx, const double* Z_host, const int64_t* row_
 int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, int flags,
                        double* S, double* scalars);
 
+/* One softmax pass over a SELECTION of every problem's resident rows (the minibatch pass of batched SVI): problem b gets
+ * exactly what mimo_estep_batched returns for a batch whose problem b holds the rows Z_b[rows_b] in that order, bit for bit.
+ * Replaces: per problem, the minibatch statistics of one outer SVI iteration — random.sample of batch_size row indices
+ *   (mimo/utils/data.py:9-12), the slicing of the data set, expected_log_likelihood + softmax + the statistics that
+ *   meanfield_sgd consumes (mimo/mixtures/ilr.py:245-277, gmm.py:300-326) — that B reference jobs (the joblib.Parallel
+ *   workers of examples/ilr/evaluate_sinc_parallel.py, --stochastic) run one after another; here without a fresh upload
+ *   per minibatch: the rows are gathered from the resident batch.  Bootstrap refits and held-out scoring of row subsets
+ *   are the same call.
+ * rows: sel_off[B] indices on the host, the problems' selections concatenated: problem b's are rows[sel_off[b] ..
+ *   sel_off[b+1]), each LOCAL to problem b, in [0, N_b); any order, duplicates allowed, more than N_b of them allowed.
+ *   sel_off: B + 1 entries, sel_off[0] = 0, non-decreasing; an empty selection is allowed (zero statistics and scalars),
+ *   and an empty problem admits no other.  Every index is checked before anything is launched: an index outside
+ *   [0, N_b), a malformed sel_off, rows or sel_off NULL are MIMO_E_INVALID (the message names the problem and the index).
+ * c, b, W, S, scalars: as mimo_estep_batched.  flags: MIMO_F_NO_STATS, MIMO_F_ENTROPY_SPLIT; MIMO_F_KEEP_LSE (the
+ *   normalisers of a selection have no place in the resident lse) and MIMO_F_DEVICE_IN are MIMO_E_INVALID.
+ * The upload's own tile split is untouched: a later mimo_estep_batched returns the bits it returned before.  Like
+ * mimo_estep_batched the call ends the residency of a random table, of labels and of lse.
+ * Coverage, the batch, the communicator and the determinism rule (problem b's block depends on its own selection and
+ * parameters alone): those of mimo_estep_batched. */
+int mimo_estep_batched_rows(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K,
+                            const int64_t* rows, const int64_t* sel_off, int flags, double* S, double* scalars);
+
 /* One Gibbs label pass over all B problems of a batched context: per problem b what mimo_gibbs_labels returns for its
  * rows alone under its parameters (c + b K, b + b K Dz, W + b K Dz Dz) — the inverse-CDF draw and the statistics of
  * the labels drawn.

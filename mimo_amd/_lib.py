@@ -35,6 +35,7 @@ SIGNATURES = {
     "mimo_estep": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "mimo_upload_batched": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int]),
     "mimo_estep_batched": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "mimo_estep_batched_rows": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
     "mimo_gibbs_labels_batched": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_uint64, _vp, C.c_int, _vp, _vp]),
     "mimo_label_stats_batched": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     "mimo_weighted_stats_batched": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),

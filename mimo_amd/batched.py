@@ -1,6 +1,7 @@
 """BatchedHipEngine — one softmax pass, one Gibbs label pass or one table pass over B independent problems
 (mimo_upload_batched / mimo_estep_batched / mimo_gibbs_labels_batched / mimo_label_stats_batched /
-mimo_weighted_stats_batched / mimo_random_resp_stats_batched).
+mimo_weighted_stats_batched / mimo_random_resp_stats_batched), or one softmax pass over chosen rows of every problem
+(mimo_estep_batched_rows: the minibatch pass of batched SVI).
 
 B problems share Dz and K; each has its own rows and its own (c, b, W).  Where the reference fits many models with
 joblib (examples/ilr/evaluate_sinc_parallel.py: one ILR fit per train split) or random restarts, every pass of every
@@ -75,18 +76,49 @@ class BatchedHipEngine:
             raise ValueError(f"parameter shapes {c.shape}, {b.shape}, {W.shape} do not match B={B}, K={K}, Dz={self.D}")
         return c, b, W, K
 
-    def estep(self, c, b, W, stats=True, keep_lse=False, entropy_split=False):
+    def _selection(self, rows):
+        """B integer index arrays -> (the concatenated int64 indices, sel_off); raises ValueError before any library call."""
+        rows = list(rows)
+        if len(rows) != self.B:
+            raise ValueError(f"row selections for {len(rows)} problems, {self.B} uploaded")
+        rows = [np.asarray(r) for r in rows]
+        for i, r in enumerate(rows):
+            if r.ndim != 1:
+                raise ValueError(f"the row selection of problem {i} must be one-dimensional, got shape {r.shape}")
+            if r.dtype.kind not in 'iu':
+                raise ValueError(f"the row selection of problem {i} must hold integers, got dtype {r.dtype}")
+            n = int(self.row_off[i + 1] - self.row_off[i])
+            if r.size and (int(r.min()) < 0 or int(r.max()) >= n):
+                raise ValueError(f"the row selection of problem {i} holds an index outside [0, {n})")
+        sel_off = np.zeros(self.B + 1, dtype=np.int64)
+        sel_off[1:] = np.cumsum([r.size for r in rows])
+        flat = np.concatenate(rows).astype(np.int64, copy=False) if sel_off[-1] > 0 else np.zeros(1, dtype=np.int64)
+        return np.ascontiguousarray(flat), sel_off
+
+    def estep(self, c, b, W, stats=True, keep_lse=False, entropy_split=False, rows=None):
         """One pass over all problems.  c (B, K), b (B, K, Dz), W (B, K, Dz, Dz).  Returns (list of B SuffStats, or None
         without stats; scalars (B, 3)) — per problem what HipEngine.estep returns; scalars[:, 1:] are NaN unless
-        entropy_split or keep_lse is set."""
+        entropy_split or keep_lse is set.
+        rows: a list of B integer arrays, problem b's a selection of its local rows in [0, N_b) — any order, duplicates
+        allowed, empty allowed.  The pass then runs over the selected rows only, gathered on the device from the resident
+        batch (mimo_estep_batched_rows): per problem, bit for bit, what a plain pass returns on a batch that holds
+        Z_b[rows_b].  No keep_lse with rows."""
+        if rows is not None:
+            if keep_lse:
+                raise ValueError("keep_lse with rows: the normalisers of a selection have no place in the resident lse")
+            sel, sel_off = self._selection(rows)
         c, b, W, K = self._params(c, b, W)
         flags = ((0 if stats else _lib.F_NO_STATS) | (_lib.F_KEEP_LSE if keep_lse else 0)
                  | (_lib.F_ENTROPY_SPLIT if entropy_split else 0))
         D = self.D
         S = np.empty((self.B, K, 1 + D + D * D)) if stats else None
         sc = np.empty((self.B, 3))
-        self._check(self._lib.mimo_estep_batched(self._ctx, _ptr(c), _ptr(b), _ptr(W), K, flags,
-                                                 _ptr(S) if stats else None, _ptr(sc)))
+        if rows is not None:
+            self._check(self._lib.mimo_estep_batched_rows(self._ctx, _ptr(c), _ptr(b), _ptr(W), K, _ptr(sel), _ptr(sel_off),
+                                                          flags, _ptr(S) if stats else None, _ptr(sc)))
+        else:
+            self._check(self._lib.mimo_estep_batched(self._ctx, _ptr(c), _ptr(b), _ptr(W), K, flags,
+                                                     _ptr(S) if stats else None, _ptr(sc)))
         return ([SuffStats.from_packed(S[i], K, D) for i in range(self.B)] if stats else None), sc
 
     def _split(self, a):

@@ -316,13 +316,14 @@ static int theta_fail(mimo_ctx* ctx, const ThetaFail& f, const char* what, int p
   }
 }
 
-// The images of B problems' (c, b, W) back to back in the placement `pl`, followed by `nextra` uint64 words (copied in the same
-// transfer), on the device at ctx->theta_d.  `what`: the batched entry point (its name leads the error texts), null for a single
+// The images of B problems' (c, b, W) back to back in the placement `pl`, followed by `nextra` uint64 words and then `nextra2` more
+// (copied in the same transfer), on the device at ctx->theta_d.  `what`: the batched entry point (its name leads the error texts), null for a single
 // problem.  inline_img: the image goes there and nowhere else — no staging buffer to wait for, no transfer to enqueue.
 template <typename Placement>
 static int stage_theta(mimo_ctx* ctx, const Placement& pl, const double* c, const double* b, const double* W, int B,
-                       const uint64_t* extra, size_t nextra, const char* what, double* inline_img = nullptr) {
-  const size_t D = ctx->D, K = pl.K, per = pl.count(), total = per * B + nextra;
+                       const uint64_t* extra, size_t nextra, const char* what, double* inline_img = nullptr,
+                       const uint64_t* extra2 = nullptr, size_t nextra2 = 0) {
+  const size_t D = ctx->D, K = pl.K, per = pl.count(), total = per * B + nextra + nextra2;
   int rc;
   if (!inline_img) {
     if ((rc = ctx->theta_d.ensure(ctx, total))) return rc;
@@ -335,6 +336,7 @@ static int stage_theta(mimo_ctx* ctx, const Placement& pl, const double* c, cons
     if (f.kind) return theta_fail(ctx, f, what, p);
   }
   if (nextra) memcpy(img + per * B, extra, nextra * sizeof(uint64_t));
+  if (nextra2) memcpy(img + per * B + nextra, extra2, nextra2 * sizeof(uint64_t));
   if (!inline_img) HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   return MIMO_OK;
 }
@@ -1612,9 +1614,9 @@ static int batched_ready(mimo_ctx* ctx, int K, const char* what) {
 // Stacked operand image [B][K16][NS][64] of the B problems' (c, b, W) (problem p's slice is the single-problem image of the fused
 // kernels, K16 row blocks of it), followed by `extra` uint64 words; on the device at ctx->theta_d.
 static int batched_theta(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, const uint64_t* extra,
-                         size_t nextra, const char* what) {
+                         size_t nextra, const char* what, const uint64_t* extra2 = nullptr, size_t nextra2 = 0) {
   const ThetaGeneric pl = {ctx->D, K, ctx->structure, (K + 15) / 16, ctx->F16 / 4};
-  return stage_theta(ctx, pl, c, b, W, ctx->batch_B, extra, nextra, what);
+  return stage_theta(ctx, pl, c, b, W, ctx->batch_B, extra, nextra, what, nullptr, extra2, nextra2);
 }
 
 static BatchedArgs batched_args(mimo_ctx* ctx, int K) {
@@ -1626,6 +1628,7 @@ static BatchedArgs batched_args(mimo_ctx* ctx, int K) {
   a.do_stats = 1;
   a.u = nullptr; a.seeds = nullptr; a.labels = nullptr; a.sweep = 0;
   a.resp = nullptr;
+  a.sel = nullptr; a.sel_off = nullptr;
   return a;
 }
 
@@ -1659,6 +1662,78 @@ int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const do
   const int split = (flags & (MIMO_F_ENTROPY_SPLIT | MIMO_F_KEEP_LSE)) ? 1 : 0;
   HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, D, F, F16, split,
                                      no_stats ? nullptr : ctx->S_d, sc_d, ctx->stream));
+  return hand_out(ctx, out, no_stats ? nullptr : S, nstats, scalars, nstats, 3 * (size_t)B);
+  });
+}
+
+// The minibatch pass (launch_batched_rows): the softmax pass over a selection of every problem's resident rows.  The call's own
+// work table — the selection sizes through batched_tiles_per_wg, as mimo_upload_batched builds its table from the row counts —
+// travels with the indices behind the operand image; the upload's tables are left alone.
+int mimo_estep_batched_rows(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, const int64_t* rows,
+                            const int64_t* sel_off, int flags, double* S, double* scalars) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, "mimo_estep_batched_rows"))) return rc;
+  if (flags & ~(MIMO_F_NO_STATS | MIMO_F_ENTROPY_SPLIT))
+    return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: flags 0x%x: only MIMO_F_NO_STATS, MIMO_F_ENTROPY_SPLIT (a selection's "
+                "normalisers have no place in the resident lse: no MIMO_F_KEEP_LSE; the indices are host memory: no MIMO_F_DEVICE_IN)", flags);
+  const bool no_stats = (flags & MIMO_F_NO_STATS) != 0;
+  if (!c || !b || !W || !scalars || (!no_stats && !S))
+    return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: c, b, W, scalars (and S without MIMO_F_NO_STATS) must be non-NULL");
+  if (!rows || !sel_off) return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: rows and sel_off must be non-NULL");
+  const int D = ctx->D, B = ctx->batch_B;
+  const int F = ctx->F, F16 = ctx->F16, K16 = (K + 15) / 16;
+  // the kernel gathers through these indices unchecked: every one is checked here, before anything is staged or launched
+  if (sel_off[0] != 0) return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: sel_off[0] = %lld, must be 0", (long long)sel_off[0]);
+  for (int p = 0; p < B; ++p) {
+    if (sel_off[p + 1] < sel_off[p]) return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: sel_off decreases at problem %d", p);
+    const int64_t nb = ctx->batch_rows[(size_t)p + 1] - ctx->batch_rows[(size_t)p];
+    for (int64_t i = sel_off[p]; i < sel_off[p + 1]; ++i)
+      if (rows[i] < 0 || rows[i] >= nb)
+        return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: problem %d: index %lld (entry %lld of its selection) outside [0, %lld)",
+                    p, (long long)rows[i], (long long)(i - sel_off[p]), (long long)nb);
+  }
+  const size_t M = (size_t)sel_off[B];
+  // behind the operand image, in its transfer: [rows (M), straight from the caller's array | sel_off (B + 1) | work table (2 words
+  // per workgroup) | wg_off (int32, B + 1)]
+  std::vector<uint64_t> extra((size_t)B + 1);
+  memcpy(extra.data(), sel_off, ((size_t)B + 1) * sizeof(int64_t));
+  std::vector<BatchedWork> work;
+  std::vector<int32_t> wg_off((size_t)B + 2, 0);     // (an even count of int32: whole words)
+  for (int p = 0; p < B; ++p) {
+    const int64_t mb = sel_off[p + 1] - sel_off[p];
+    const int64_t tiles = (mb + kTile - 1) / kTile;
+    const int tpw = batched_tiles_per_wg(mb);
+    for (int64_t t = 0; t < tiles; t += tpw)
+      work.push_back(BatchedWork{p, (int32_t)t, (int32_t)std::min<int64_t>(tpw, tiles - t), 0});
+    if (work.size() > (size_t)INT32_MAX) return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: too many rows");
+    wg_off[(size_t)p + 1] = (int32_t)work.size();
+  }
+  static_assert(sizeof(BatchedWork) == 2 * sizeof(uint64_t), "a work table entry is two words of the staged block");
+  const size_t G = work.size(), at_work = extra.size(), at_wg = at_work + 2 * G, nwg = ((size_t)B + 2) / 2;
+  extra.resize(at_wg + nwg);
+  if (G) memcpy(extra.data() + at_work, work.data(), G * sizeof(BatchedWork));
+  memcpy(extra.data() + at_wg, wg_off.data(), nwg * sizeof(uint64_t));
+  if ((rc = batched_theta(ctx, c, b, W, K, reinterpret_cast<const uint64_t*>(rows), M, "mimo_estep_batched_rows", extra.data(),
+                          extra.size()))) return rc;
+  const uint64_t* sel_d = reinterpret_cast<const uint64_t*>(ctx->theta_d.p) + (size_t)K16 * (F16 / 4) * 64 * B;
+  const uint64_t* ex = sel_d + M;      // the small tables
+
+  if ((rc = ctx->partials.ensure(ctx, partial_stride(K16, F16) * std::max<size_t>(G, 1)))) return rc;
+  // a softmax pass for the residency rule, as mimo_estep_batched without MIMO_F_KEEP_LSE
+  ctx->lse_valid = false;
+  ctx->resp_valid = ctx->logp_valid = ctx->labels_valid = false;
+  BatchedArgs a = batched_args(ctx, K);
+  a.work = reinterpret_cast<const BatchedWork*>(ex + at_work);
+  a.sel = reinterpret_cast<const int64_t*>(sel_d);
+  a.sel_off = reinterpret_cast<const int64_t*>(ex);
+  a.do_stats = no_stats ? 0 : 1;
+  HIP_TRY(ctx, launch_batched_rows(a, (int)G, ctx->stream));
+  const size_t nstats = no_stats ? 0 : packed_len(K, D) * B, out = nstats + 3 * (size_t)B;
+  if ((rc = ensure_block(ctx, out))) return rc;
+  const int split = (flags & MIMO_F_ENTROPY_SPLIT) ? 1 : 0;
+  HIP_TRY(ctx, launch_batched_reduce(ctx->partials, reinterpret_cast<const int32_t*>(ex + at_wg), B, ctx->feat_d, K, D, F, F16, split,
+                                     no_stats ? nullptr : ctx->S_d, ctx->S_d + nstats, ctx->stream));
   return hand_out(ctx, out, no_stats ? nullptr : S, nstats, scalars, nstats, 3 * (size_t)B);
   });
 }

@@ -42,12 +42,16 @@ struct BatchedArgs {
   uint64_t sweep;
   // table mode (launch_batched_weights) only
   const double* resp;         // the problems' K-major (K, N_b) weight tables back to back: problem b's starts at element K row_off[b]
+  // row-selection mode (launch_batched_rows) only
+  const int64_t* sel;         // local row indices in [0, N_b), the problems' selections concatenated (checked by the caller)
+  const int64_t* sel_off;     // [B + 1]: problem b's selection is sel[sel_off[b] .. sel_off[b + 1])
 };
 
 // Label modes of the batched kernel family: the inverse-CDF draw of a Gibbs sweep (with the statistics of the labels
 // drawn), or the statistics of labels given on the device (no L product, no draw).
 // Table mode: the statistics of a weight table given on the device (no L product, no normalise phase; weights as they are).
-enum BatchedLabelMode : int { kBatchedSoftmax = 0, kBatchedDraw = 1, kBatchedGiven = 2, kBatchedWeights = 3 };
+// Row-selection mode: the softmax pass over rows gathered through an index list (the minibatch pass of batched SVI).
+enum BatchedLabelMode : int { kBatchedSoftmax = 0, kBatchedDraw = 1, kBatchedGiven = 2, kBatchedWeights = 3, kBatchedSoftmaxRows = 4 };
 
 // Tiles per workgroup for a problem of `nrows` rows: a function of the row count alone (the determinism rule: a problem's
 // result does not depend on what else is in the batch).
@@ -60,6 +64,11 @@ hipError_t launch_batched(const BatchedArgs& a, int grid, hipStream_t stream);
 hipError_t launch_batched_labels(const BatchedArgs& a, int mode, int grid, hipStream_t stream);
 // The table mode (kBatchedWeights) on the same work table: the partial blocks hold the statistics of a.resp and zero scalars.
 hipError_t launch_batched_weights(const BatchedArgs& a, int grid, hipStream_t stream);
+// The row-selection mode (kBatchedSoftmaxRows): a.work is a work table built for the SELECTION sizes
+// sel_off[b + 1] - sel_off[b] (batched_tiles_per_wg of them), a.partials has room for its grid.  Problem b's partial blocks are
+// those launch_batched writes for a batch whose problem b holds the rows Z_b[sel_b] in that order, bit for bit.  Every index
+// must lie in [0, N_b): the kernel does not check.
+hipError_t launch_batched_rows(const BatchedArgs& a, int grid, hipStream_t stream);
 // Random responsibilities of every problem in one launch, in the layout of BatchedArgs::resp: column n of problem b is
 // random_resp_column (mimo_device.h) with key seeds[b] and the LOCAL row n — the table launch_random_resp writes for the
 // problem's rows alone at row offset 0, bit for bit.  row_off and seeds are device pointers.

@@ -30,6 +30,13 @@
 // back, problem b's at element K row_off[b]; exactly 0.0 for rows past the problem's end and for padding components);
 // no L product, no normalise phase; phase 5 is the softmax mode's, its A operand read from Lt.  Zero scalars.
 // batched_random_resp_kernel writes such a table for the whole batch in one launch (random_resp_column of mimo_device.h).
+//
+// Row-selection mode (LM = kBatchedSoftmaxRows, the minibatch pass of batched SVI): the softmax mode over a.sel, a list of
+// local row indices per problem (problem b's are sel[sel_off[b] .. sel_off[b + 1]), any order, duplicates allowed).  Phase 1
+// gathers the z~ tile through the list: tile row r of local tile t is row sel[sel_off[b] + 32 t + r] of the problem; the
+// problem's "row count" is its selection's length, and a.work is a table built for those lengths.  Every phase after the tile
+// store is the softmax mode's, so the result is that of a plain pass over the gathered rows, bit for bit.  The indices are
+// read one tile ahead of the rows they address (three tiles ahead of their use), so the dependent load is never waited for.
 #include "mimo_batched.h"
 #include "mimo_tile.h"
 
@@ -73,8 +80,9 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
   double* etab = red + 16;                        // [64]     2^(j/64) for exp_nonpos
   uint8_t* fe = reinterpret_cast<uint8_t*>(etab + 64);   // [F16][2]
   int* labs = reinterpret_cast<int*>(red);        // [T] labels of the tile (label modes; unused by the softmax and the table mode)
-  constexpr bool HAS_L = LM == kBatchedSoftmax || LM == kBatchedDraw;        // L product + normalise phase
-  constexpr bool A_FROM_LT = LM == kBatchedSoftmax || LM == kBatchedWeights;   // phase 5 reads its A operand from Lt
+  constexpr bool ROWS = LM == kBatchedSoftmaxRows;                           // the softmax mode over a row selection
+  constexpr bool HAS_L = LM == kBatchedSoftmax || ROWS || LM == kBatchedDraw;  // L product + normalise phase
+  constexpr bool A_FROM_LT = LM == kBatchedSoftmax || ROWS || LM == kBatchedWeights;   // phase 5 reads its A operand from Lt
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -86,9 +94,16 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
   const BatchedWork wk = a.work[blockIdx.x];
   const int prob = __builtin_amdgcn_readfirstlane(wk.prob);
   const int tile0 = __builtin_amdgcn_readfirstlane(wk.tile0), ntl = __builtin_amdgcn_readfirstlane(wk.ntiles);
-  const int64_t rbeg = a.row_off[prob], Nb = a.row_off[prob + 1] - rbeg;
+  const int64_t rbeg = a.row_off[prob];
+  int64_t nrows = a.row_off[prob + 1] - rbeg;
+  const int64_t* selb = nullptr;            // selection mode: the problem's index list; its length is the pass's row count
+  if constexpr (ROWS) {
+    selb = a.sel + a.sel_off[prob];
+    nrows = a.sel_off[prob + 1] - a.sel_off[prob];
+  }
+  const int64_t Nb = nrows;
   const double* Zb = a.Z + rbeg * D;
-  double* const out_lse = a.lse ? a.lse + rbeg : nullptr;
+  double* const out_lse = !ROWS && a.lse ? a.lse + rbeg : nullptr;    // (a selection's normalisers have no place in lse)
   const gptr_t th = (gptr_t)(a.theta + (size_t)prob * K16 * NSI * 64);
 
   for (int e = tid; e < F16 * 2; e += kWG) fe[e] = a.feat[e];
@@ -117,7 +132,35 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
     zoff[i] = e < T * D ? pt * ZS + (e - pt * D) : -1;
   }
   double zr[2];
+  // selection mode: element i of this thread lies in tile row zrow[i] and column zcol[i] of every tile, so a tile costs it
+  // two index loads; zi[i] is the element offset (index * D + column) of the NEXT load_z's row, -1 past the selection's end.
+  // load_z(t) reads the rows through the offsets fetched by load_z(t - 1) and fetches those of tile t + 1 (the calls come
+  // in tile order), so no load waits for the index it depends on.
+  int zrow[2], zcol[2];
+  int64_t zi[2];
+  auto load_idx = [&](int t) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int64_t n = (int64_t)t * T + zrow[i];
+      zi[i] = (zoff[i] >= 0 && n < Nb) ? selb[n] * D + zcol[i] : -1;
+    }
+  };
+  if constexpr (ROWS) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int e = tid + kWG * i;
+      zrow[i] = e / D;
+      zcol[i] = e - zrow[i] * D;
+    }
+    load_idx(tile0);
+  }
   auto load_z = [&](int t) {
+    if constexpr (ROWS) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) zr[i] = zi[i] >= 0 ? Zb[zi[i]] : 0.0;
+      load_idx(t + 1);
+      return;
+    }
     const int64_t base = (int64_t)t * T * D, total = Nb * D;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -330,7 +373,7 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
       }
     }
   }
-  if constexpr (LM != kBatchedSoftmax) {
+  if constexpr (!(LM == kBatchedSoftmax || ROWS)) {
     // no scalars in the label and table modes (and red, which holds the labels, is left alone)
     if (tid < 4) Pb[(size_t)Kpad * F16 + tid] = 0.0;
     return;
@@ -440,6 +483,11 @@ hipError_t launch_batched_labels(const BatchedArgs& a, int mode, int grid, hipSt
     return launch_mode<kBatchedGiven>(a, grid, stream);
   }
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_batched_rows(const BatchedArgs& a, int grid, hipStream_t stream) {
+  if (!a.sel || !a.sel_off) return hipErrorInvalidValue;
+  return launch_mode<kBatchedSoftmaxRows>(a, grid, stream);
 }
 
 hipError_t launch_batched_weights(const BatchedArgs& a, int grid, hipStream_t stream) {

@@ -8,7 +8,13 @@ likelihood draws, the prior terms of the bound and the bound itself.  A model st
 run would stop; after that it is neither updated nor appended to (its last parameters stay in the batch).
 
 Gibbs: per sweep each model runs the host half of its solo resample sweep, in model order (parameter and gating draws,
-canonical form, host uniforms), then one batched label pass draws every model's labels and their statistics."""
+canonical form, host uniforms), then one batched label pass draws every model's labels and their statistics.
+
+SVI: per outer iteration each model draws its minibatch indices, in model order; one batched pass over the chosen rows
+of every model's resident data (BatchedHipEngine.estep(rows=...): the rows are gathered on the device, nothing but the
+indices is uploaded) gives the minibatch statistics; each model takes its natural-gradient step (_svi_step, the step of
+its solo meanfield_stochastic_descent); one batched pass over all rows gives the bounds."""
+import random
 from contextlib import contextmanager
 
 import numpy as np
@@ -19,6 +25,7 @@ from mimo_amd.distributions import native_sweep as _native_sweep
 from mimo_amd.distributions.lingauss import joint_rows
 from mimo_amd.mixtures.gmm import BayesianMixtureOfGaussians, _component_stats
 from mimo_amd.mixtures.ilr import BayesianMixtureOfLinearGaussians
+from mimo_amd.utils.data import sample_indices
 
 
 def _rows(model, d):
@@ -228,3 +235,103 @@ def resample_batched(models, data, init_labels='prior', maxiter=1, label_rng='ho
             m.labels_ = z
     finally:
         streams.restore()
+
+
+class _PythonStreams:
+    """_NumpyStreams for Python's global `random` generator (the minibatch indices): model i's stream starts as
+    random.seed(python_seeds[i]) and is swapped in (setstate) and out (getstate) around each of its index draws.  Without
+    python_seeds the global stream is used as it stands, in model order."""
+
+    def __init__(self, python_seeds, B):
+        self.states = None
+        if python_seeds is not None:
+            python_seeds = _per_model(python_seeds, B, 0, "python seeds")
+            self.caller = random.getstate()
+            self.states = []
+            for sd in python_seeds:
+                random.seed(sd)
+                self.states.append(random.getstate())
+            random.setstate(self.caller)
+
+    @contextmanager
+    def of(self, i):
+        if self.states is None:
+            yield
+            return
+        random.setstate(self.states[i])
+        try:
+            yield
+        finally:
+            self.states[i] = random.getstate()
+
+    def restore(self):
+        if self.states is not None:
+            random.setstate(self.caller)
+
+
+def meanfield_stochastic_descent_batched(models, data, randomize=True, maxiter=500, step_size=1e-3, batch_size=128,
+                                         sample_likelihood=True, numpy_seeds=None, python_seeds=None, engine=None):
+    """Stochastic variational inference of B models with two batched passes per outer iteration: per model what its solo
+    meanfield_stochastic_descent(data, randomize, maxiter, step_size, batch_size, sample_likelihood=sample_likelihood)
+    does in the plain form of the shared outer loop (mixtures/_svi.py).  models / data / engine as in
+    meanfield_coordinate_descent_batched; every model's full rows are uploaded once.
+
+    Per iteration: each model draws its minibatch, sample_indices(N_b, batch_size), in model order; ONE pass over the
+    chosen rows of all models (engine.estep(..., rows=batches)); each model's natural-gradient step with
+    scale = batch_size / N_b; ONE pass over all rows without statistics; each model appends prior terms + bound.  SVI has
+    no stopping rule: every model runs maxiter iterations.  Returns the B traces.
+
+    randomize=True: the first step's statistics are those of numpy.random.rand(K, batch_size), normalised over k, on the
+    minibatch's rows (the solo start), drawn in model order and passed as a (K, N_b) table that is 0.0 off the minibatch:
+    one engine.weighted_stats call that moves K N_b doubles per model to the device, once.
+
+    numpy_seeds[i] / python_seeds[i]: model i's numpy work (the start, the likelihood draws of the steps) and its index
+    draws run on streams of their own, started as numpy.random.seed(numpy_seeds[i]) and random.seed(python_seeds[i]), so
+    with both lists the batch reproduces B solo runs each preceded by those two calls; the caller's states of both
+    generators are restored at the end, also on an exception.  Without a list that generator's global stream is consumed
+    in model order (at B = 1: the solo plain form's order)."""
+    models, data, cls = _check_models(models, data)
+    B = len(models)
+    maxiter, batch_size = int(maxiter), int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"batch_size = {batch_size} < 1")
+    for name, sd in (("numpy seeds", numpy_seeds), ("python seeds", python_seeds)):
+        _per_model(sd, B, 0, name)
+    rows = [_rows(m, d) for m, d in zip(models, data)]       # (validates the structure before any draw)
+    nstreams, pstreams = _NumpyStreams(numpy_seeds, B), _PythonStreams(python_seeds, B)
+    vlbs = [[] for _ in range(B)]
+    if maxiter <= 0:
+        return vlbs
+    if engine is None:
+        engine = BatchedHipEngine(getattr(models[0].engine, 'device', 0))
+    try:
+        engine.upload(rows)
+        K = models[0].size
+        nrows = [int(n) for n in np.diff(engine.row_off)]
+        for it in range(maxiter):
+            batches = []
+            for i in range(B):
+                with pstreams.of(i):
+                    batches.append(sample_indices(nrows[i], batch_size, as_array=True))
+            if it == 0 and randomize is True:
+                tables = []
+                for i in range(B):
+                    with nstreams.of(i):
+                        resp = npr.rand(K, len(batches[i]))
+                    resp /= np.sum(resp, axis=0)
+                    table = np.zeros((K, nrows[i]))
+                    table[:, batches[i]] = resp
+                    tables.append(table)
+                Sb = engine.weighted_stats(tables)
+            else:
+                Sb, _ = engine.estep(*_stack([m.canonical_expected() for m in models]), rows=batches)
+            for i, m in enumerate(models):
+                with nstreams.of(i):
+                    m._svi_step(Sb[i], batch_size / float(nrows[i]), step_size, sample_likelihood)
+            _, sc = engine.estep(*_stack([m.canonical_expected() for m in models]), stats=False)
+            for i, m in enumerate(models):
+                vlbs[i].append(m._vlb_prior_terms() + sc[i, 0])
+        return vlbs
+    finally:
+        nstreams.restore()
+        pstreams.restore()

@@ -417,6 +417,12 @@ class BayesianMixtureOfGaussians:
         self.components.meanfield_update(None, stats=_component_stats(eng.weighted_stats(resp), self.components))
 
     # ---- SVI -----------------------------------------------------------------------------------
+    def _svi_step(self, Sb, scale, step_size, sample_likelihood):
+        """The natural-gradient step of one minibatch from its statistics (gmm.py:312-318): components, gating."""
+        self.components.meanfield_sgd(None, None, scale, step_size, stats=_component_stats(Sb, self.components),
+                                      sample=sample_likelihood)
+        self.gating.meanfield_sgd(None, Sb.gating_counts, scale, step_size, sample=sample_likelihood)
+
     def meanfield_stochastic_descent(self, obs, randomize=True, maxiter=500, step_size=1e-2, batch_size=128,
                                      progress_bar=True, procces_id=0, sample_likelihood=True):
         """gmm.py:300-326: one minibatch natural-gradient step + one full-data E-step / ELBO per
@@ -436,9 +442,7 @@ class BayesianMixtureOfGaussians:
             beng.upload(obs[batch, :])
 
         def step(Sb):
-            self.components.meanfield_sgd(None, None, scale, step_size, stats=_component_stats(Sb, self.components),
-                                          sample=sample_likelihood)
-            self.gating.meanfield_sgd(None, Sb.gating_counts, scale, step_size, sample=sample_likelihood)
+            self._svi_step(Sb, scale, step_size, sample_likelihood)
 
         with tqdm(total=maxiter, desc=f'SVI #{procces_id + 1}', position=procces_id,
                   disable=not progress_bar) as pbar:

@@ -367,6 +367,13 @@ class BayesianMixtureOfLinearGaussians:
         self.models.meanfield_update(x, y, resp)
 
     # ---- SVI ---------------------------------------------------------------------------------------
+    def _svi_step(self, Sb, scale, step_size, sample_likelihood):
+        """The natural-gradient step of one minibatch from its statistics (ilr.py:259-268): basis, models, gating."""
+        bstats, mstats = self._block_stats(Sb)
+        self.basis.meanfield_sgd(None, None, scale, step_size, stats=bstats, sample=sample_likelihood)
+        self.models.meanfield_sgd(None, None, None, scale, step_size, stats=mstats, sample=sample_likelihood)
+        self.gating.meanfield_sgd(None, Sb.gating_counts, scale, step_size, sample=sample_likelihood)
+
     def meanfield_stochastic_descent(self, x, y, randomize=True, maxiter=500, step_size=1e-3, batch_size=128,
                                      progress_bar=True, procces_id=0, sample_likelihood=True):
         """ilr.py:245-277."""
@@ -381,10 +388,7 @@ class BayesianMixtureOfLinearGaussians:
         scale = eng.global_rows(batch_size) / float(eng.global_rows(len(xx)))
 
         def step(Sb):
-            bstats, mstats = self._block_stats(Sb)
-            self.basis.meanfield_sgd(None, None, scale, step_size, stats=bstats, sample=sample_likelihood)
-            self.models.meanfield_sgd(None, None, None, scale, step_size, stats=mstats, sample=sample_likelihood)
-            self.gating.meanfield_sgd(None, Sb.gating_counts, scale, step_size, sample=sample_likelihood)
+            self._svi_step(Sb, scale, step_size, sample_likelihood)
 
         with tqdm(total=maxiter, desc=f'SVI #{procces_id + 1}', position=procces_id,
                   disable=not progress_bar) as pbar:

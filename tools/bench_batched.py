@@ -2,7 +2,7 @@
 data resident), on the same inputs, after warm-up; wall time per pass (each call returns synchronised host results) and the
 largest relative difference of the outputs.  Writes <out>/bench_batched.json.
 
-    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3] [--start-only | --no-start]
+    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3] [--start-only | --no-start | --svi]
 
 Also times one iteration of meanfield_coordinate_descent_batched against B solo meanfield_iteration calls at shape 1
 (24 ILR models, K = 100, dx = dy = 1), split into host time and pass time.
@@ -15,6 +15,14 @@ Start leg (unless --no-start): per shape, the random start of a variational fit 
 and one BatchedHipEngine.weighted_stats (host tables) against the B solo HipEngine calls, batched and solo alternated in the
 same run.  --trace-start SHAPE only runs the two batched start passes a few times (for a kernel trace of the fill kernel
 and the weights mode from outside) and writes nothing.
+
+SVI leg (--svi, on its own; writes <out>/bench_batched_svi.json): per shape, one selection pass (BatchedHipEngine.estep(rows=...):
+256 random rows per problem at shapes 1 and 2, 1e5 random rows per problem at shape 3) against a plain pass on a second
+engine that uploaded the selected rows contiguously — identical work, so the difference is the gather —, alternated in the
+same run, outputs compared bit for bit; and one outer iteration of meanfield_stochastic_descent_batched over the 24 ILR
+models of shape 1 (minibatches of 256) against 24 solo meanfield_stochastic_descent iterations.  --trace-svi SHAPE only runs
+the two passes a few times (for a kernel trace from outside: the selection pass is batched_kernel<.., 4>, the plain pass
+batched_kernel<.., 0>) and writes nothing.
 
 Shapes: 1. B = 24, N_b = 1600, Dz = 2, K = 100 (the reference's parallel ILR example); 2. B = 64, N_b = 1e4, Dz = 2, K = 4
 (restarts of the toy GMM); 3. B = 8, N_b = 2.5e5, Dz = 12, K = 64 (C4 per model)."""
@@ -352,6 +360,84 @@ def driver_iteration(reps):
     return {"driver_shape": 1, "B": B, "batched": batched, "solo": solo, "reps": reps}
 
 
+SVI_ROWS = {1: 256, 2: 256, 3: 100000}
+
+
+def svi_engines(sid):
+    """(engine with the full batch, engine with the selected rows uploaded contiguously, c, b, W, selections)."""
+    B, N, D, K = SHAPES[sid]
+    Zs, c, b, W = inputs(B, N, D, K, seed=sid)
+    rng = np.random.default_rng(100 + sid)
+    sel = [rng.integers(0, N, size=SVI_ROWS[sid]).astype(np.int64) for _ in range(B)]
+    beng, geng = BatchedHipEngine(0), BatchedHipEngine(0)
+    beng.upload(Zs)
+    geng.upload([Z[r] for Z, r in zip(Zs, sel)])
+    return beng, geng, c, b, W, sel
+
+
+def run_svi_shape(sid, reps):
+    """The selection pass against a plain pass over the same rows uploaded contiguously."""
+    B, N, D, K = SHAPES[sid]
+    beng, geng, c, b, W, sel = svi_engines(sid)
+    out = {}
+
+    def rows_pass():
+        out["r"] = beng.estep(c, b, W, rows=sel)
+
+    def plain_pass():
+        out["p"] = geng.estep(c, b, W)
+
+    tr, tp = timed_alternating(rows_pass, plain_pass, reps)
+    same = bool(np.array_equal(out["r"][1], out["p"][1], equal_nan=True)
+                and all(np.array_equal(x.packed(), y.packed()) for x, y in zip(out["r"][0], out["p"][0])))
+    beng.close()
+    geng.close()
+    return {"svi_shape": sid, "B": B, "N_b": N, "Dz": D, "K": K, "rows_per_problem": SVI_ROWS[sid], "rows_pass_ms": tr,
+            "plain_pass_ms": tp, "ratio": tr / tp, "bit_identical": same, "reps": reps}
+
+
+def trace_svi(sid, reps=5):
+    beng, geng, c, b, W, sel = svi_engines(sid)
+    for _ in range(reps):
+        beng.estep(c, b, W, rows=sel)
+        geng.estep(c, b, W)
+    beng.close()
+    geng.close()
+
+
+class _TimedSviEngine(_TimedEngine):
+    row_off = property(lambda self: self.eng.row_off)
+
+    def weighted_stats(self, *a, **k):
+        return self.eng.weighted_stats(*a, **k)
+
+
+def svi_driver_iteration(reps, batch=256):
+    """One outer iteration of batched SVI (shape 1: 24 ILR models, minibatches of 256) against 24 solo iterations."""
+    from mimo_amd.mixtures.batched import meanfield_stochastic_descent_batched
+    B, N, _, K = SHAPES[1]
+    engines = [HipEngine(0) for _ in range(B)]          # solo: every model on its own engine (and its own minibatch engine)
+    models, data = ilr_models(B, N, K, engines)
+    kw = dict(randomize=False, step_size=0.5, batch_size=batch)
+    teng = _TimedSviEngine(BatchedHipEngine(0))
+    meanfield_stochastic_descent_batched(models, data, maxiter=3, engine=teng, **kw)
+    teng.upload_s, teng.pass_s = 0., []
+    t0 = time.perf_counter()
+    meanfield_stochastic_descent_batched(models, data, maxiter=reps, engine=teng, **kw)
+    total = (time.perf_counter() - t0 - teng.upload_s) / reps * 1e3
+    pass_ms = float(np.sum(teng.pass_s)) / reps * 1e3
+    batched = {"iteration_ms": total, "pass_ms": pass_ms, "rows_pass_ms": float(np.median(teng.pass_s[0::2])) * 1e3,
+               "bound_pass_ms": float(np.median(teng.pass_s[1::2])) * 1e3, "host_ms": total - pass_ms}
+    for m, (x, y) in zip(models, data):                  # warm-up: data resident, minibatch engines created
+        m.meanfield_stochastic_descent(x, y, maxiter=3, progress_bar=False, **kw)
+    t0 = time.perf_counter()
+    for m, (x, y) in zip(models, data):
+        m.meanfield_stochastic_descent(x, y, maxiter=reps, progress_bar=False, **kw)
+    solo = (time.perf_counter() - t0) / reps * 1e3
+    return {"svi_driver_shape": 1, "B": B, "batch_size": batch, "batched": batched, "solo_iterations_ms": solo,
+            "speedup": solo / total, "reps": reps}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
@@ -362,7 +448,22 @@ def main():
     ap.add_argument("--no-start", action="store_true", help="skip the start leg")
     ap.add_argument("--start-only", action="store_true", help="only the start leg")
     ap.add_argument("--trace-start", type=int, default=0, metavar="SHAPE", help="only run the batched start passes of SHAPE")
+    ap.add_argument("--svi", action="store_true", help="only the SVI leg (selection pass, SVI iteration)")
+    ap.add_argument("--trace-svi", type=int, default=0, metavar="SHAPE", help="only run the selection pass and the plain pass of SHAPE")
     args = ap.parse_args()
+    if args.trace_svi:
+        trace_svi(args.trace_svi)
+        return
+    if args.svi:
+        os.makedirs(args.out, exist_ok=True)
+        res = [run_svi_shape(int(s), args.reps) for s in args.shapes.split(",")]
+        if not args.no_driver:
+            res.append(svi_driver_iteration(args.reps))
+        for r in res:
+            print(json.dumps(r))
+        with open(os.path.join(args.out, "bench_batched_svi.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if args.trace_start:
         trace_start(args.trace_start)
         return

@@ -120,6 +120,26 @@ int mimo_attach(mimo_ctx* ctx, const double* Z_dev, int64_t N, int Dz);
 #define MIMO_STRUCT_LINEAR 2
 int mimo_set_structure(mimo_ctx* ctx, int structure);
 
+/* Slot order of the components inside the fused mean-field pass: order[s] (a permutation of 0 .. K-1) is the component whose
+ * Theta sits in slot s, i.e. in position s % 16 of row block s / 16.  The responsibility skip ("resp_skip_log2") contracts a
+ * datum in every row block where one of the 16 components has a weight above the threshold, so an order that puts the
+ * components of one cluster into one block (mimo_host_block_order) saves the contractions of the others.
+ *   - order = NULL restores the identity.  The order stays until it is replaced; a pass with another K, a new data set
+ *     (mimo_upload, mimo_attach, mimo_upload_batched) or another structure drops it.
+ *   - everything the caller hands in or gets back stays in the caller's numbering: the statistics of slot s are delivered as
+ *     row order[s] of the packed block (host, device or all-reduced), the scalars are sums over rows.
+ *   - honoured by the single-pass softmax + statistics request on the fused tile kernel at K <= 64 (mimo_plan: MIMO_PLAN_FUSED
+ *     with MIMO_PLAN_ORDERED set), dense and skipping instantiations alike.  EVERY OTHER ROUTE IGNORES IT: requests with tables,
+ *     the entropy split or row weights, data with NaN rows, label passes, the two-stage, mid, narrow, small, row-owner and
+ *     batched kernels.
+ *   - results: the softmax sums run over the components in slot order and other sub-threshold weights are contracted, so a
+ *     statistic moves by at most tau * sum_n |phi_nf| and the scalars by an ulp of the sum of the weights against the
+ *     identity; for one order they are bit-identical between repeats, the asynchronous call and every shard count.
+ *   - "block_order" = 0 (mimo_tune) makes this call a no-op that returns MIMO_OK.
+ * MIMO_E_INVALID (state unchanged) when order is not a permutation of 0 .. K-1 or K is outside [1, 256]; MIMO_E_STATE while
+ * an asynchronous call is pending.  No reference counterpart. */
+int mimo_set_component_order(mimo_ctx* ctx, const int32_t* order, int K);
+
 /* Global index of local row 0; only enters the Philox counter so that labels drawn by a sharded
  * run do not depend on the number of shards.  Default 0. */
 int mimo_set_row_offset(mimo_ctx* ctx, int64_t row0);
@@ -448,6 +468,19 @@ int mimo_host_gmm_vi_bound(int K, int D, int tied, const double* alpha0, const d
                            const double* mus, const double* nus, const double* half_logdet_psi, const double* nat_c,
                            const double* bb, const double* E2, const double* W, const double* E4, double* vlb);
 
+/* Slot order for mimo_set_component_order from a posterior: order[s] = the component that sits in slot s, chosen so that
+ * components which answer the same rows share a row block of `block` = 16 slots and the blocks carry about equal mass.
+ *   in : means (K, D) the components' posterior means, mass (K) their expected counts (sum_n r_kn)
+ *   how: components with mass < 1 are fillers; the others are clustered by single linkage: the edges of the minimum spanning
+ *        tree of their means (squared Euclidean distance; ties to the lower index), shortest first, each merging its two clusters
+ *        while the result keeps at most 16 members and at most 1 / (4 ceil(K / 16)) of the total mass; the clusters go, heaviest
+ *        first, into the lightest block with room (member by member when none has); the fillers take the free slots in index
+ *        order.  About 5 us at K = 64, D = 16 on one core.
+ * A pure function of its arguments (no state, no threads, no random numbers): every rank of a sharded run computes the same
+ * order from the same posterior.  MIMO_E_INVALID for K < 1, D < 1, block != 16, a NULL pointer, a NaN or an infinity in means
+ * or mass; MIMO_E_UNSUPPORTED for K > 256.  No reference counterpart (the order of the components is ours to choose). */
+int mimo_host_block_order(int K, int D, const double* means, const double* mass, int block, int32_t* order);
+
 /* K blocks of variates from numpy.random's LEGACY stream (RandomState over MT19937), bit for bit what the reference's
  * per-component calls consume and return: per block k, n_before x normal(), then standard_gamma(shapes[k][i]) for i < n_gamma
  * (chisquare(df) = 2 standard_gamma(df / 2), gamma(a, scale) = scale standard_gamma(a): the caller scales), then n_after x
@@ -556,6 +589,8 @@ int mimo_profile_kernels(mimo_ctx* ctx, char* buf, int len);
  *   out8[2] 1 if the (K, N) responsibility table goes through HBM, out8[3] how many times it is read back,
  *   out8[4] reads of the data Z per pass, out8[5] writes + reads of the (N,) labels per pass,
  *   out8[6] workgroups of the dominant kernel, out8[7] compute units of the device.
+ * mimo_plan (not mimo_plan_shape) adds MIMO_PLAN_ORDERED to out8[0] when a component order (mimo_set_component_order) is in
+ * force for this K and the plain softmax pass honours it.
  * bench.py prices its HBM roofline block from this instead of assuming a single fused pass. */
 #define MIMO_PLAN_FUSED      1   /* one fused tile kernel (MFMA): log-densities, softmax / draw, statistics        */
 #define MIMO_PLAN_TWO_STAGE  2   /* chunked E-step + statistics launches per feature column group (Dz > 16, ...)    */
@@ -563,6 +598,7 @@ int mimo_profile_kernels(mimo_ctx* ctx, char* buf, int len);
 #define MIMO_PLAN_ROWWAVE    4   /* label pass: row-owner label kernel + label-indexed statistics kernel            */
 #define MIMO_PLAN_ROWWAVE_VI 5   /* softmax pass at K <= 64, Dz <= 9: row-owner kernel for both matrix products     */
 #define MIMO_PLAN_NARROW     6   /* Dz <= 4 with 32 < K <= 128: 4x4x4 matrix-instruction kernels (+ label statistics) */
+#define MIMO_PLAN_ORDERED    0x100 /* flag on top of the kind: the pass runs under the context's component order               */
 #define MIMO_PLAN_MID        7   /* softmax pass of the mid shapes (K <= 128; mimo_mid.hip): row-owner E-step + column-owner statistics waves */
 int mimo_plan(mimo_ctx* ctx, int K, int gibbs, int64_t* out8);
 
@@ -586,6 +622,10 @@ int mimo_data_checksum(mimo_ctx* ctx, uint64_t out[2]);
  *   "resp_skip_log2" (per context, default 60) the mean-field pass on the fused kernel at Dz >= 14 leaves out of the statistics of a
  *                  16-component row block every datum whose 16 responsibilities there are all below tau = 2^-value; each
  *                  statistic moves by at most tau * sum_n |phi_nf|, the ELBO scalars not at all.  0: every weight enters.
+ *   "block_order"  (per context; default 1, or the value of the environment variable MIMO_BLOCK_ORDER when the context is
+ *                  created, so that a program which never calls mimo_tune can be run both ways) 0: mimo_set_component_order
+ *                  becomes a no-op and an order in force is dropped, so one library runs a driver that sets orders with
+ *                  and without them.
  *   "sorted_range" (process-wide) cap on the 256-row tiles per range of label_stats_gram_kernel (default and maximum 80;
  *                  0 restores it): with a low cap a workgroup takes several ranges ("first range writes, later ranges add").
  *   "mid_min_d", "mid_narrow_k" (process-wide) 0 / 0: the mid kernels (mimo_mid.hip) run where they measured fastest.  Otherwise

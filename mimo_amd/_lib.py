@@ -32,6 +32,7 @@ SIGNATURES = {
     "mimo_attach": (C.c_int, [_vp, _vp, C.c_int64, C.c_int]),
     "mimo_set_row_offset": (C.c_int, [_vp, C.c_int64]),
     "mimo_set_structure": (C.c_int, [_vp, C.c_int]),
+    "mimo_set_component_order": (C.c_int, [_vp, _vp, C.c_int]),
     "mimo_estep": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "mimo_upload_batched": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int]),
     "mimo_estep_batched": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
@@ -60,6 +61,7 @@ SIGNATURES = {
                                          C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "mimo_host_gmm_vi_sweep": (C.c_int, [C.c_int, C.c_int, C.c_int] + [_vp] * 26),
     "mimo_host_gmm_vi_bound": (C.c_int, [C.c_int, C.c_int, C.c_int] + [_vp] * 21),
+    "mimo_host_block_order": (C.c_int, [C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
     "mimo_host_mnw_vi": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 15),
     "mimo_host_nw_gibbs": (C.c_int, [C.c_int, C.c_int] + [_vp] * 10),
     "mimo_host_digamma": (C.c_double, [C.c_double]),

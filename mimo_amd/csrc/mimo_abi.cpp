@@ -103,6 +103,12 @@ struct mimo_ctx {
   Buf<double> theta_d;
   Buf<double, true> theta_h;  // pinned staging
 
+  // slot order of the components in the fused mean-field pass (mimo_set_component_order); order_K = 0: the identity
+  int block_order_on = [] { const char* e = getenv("MIMO_BLOCK_ORDER"); return !e || atoi(e) != 0; }();   // mimo_tune "block_order"
+  int order_K = 0;
+  alignas(8) int32_t order[256] = {0};                    // order[s] = the component in slot s
+  const int32_t* pass_order = nullptr;                    // the pass being launched runs under the order: its device copy (behind the Theta image)
+
   // workspaces
   Buf<double> partials;
   Buf<double> reduced;
@@ -277,7 +283,16 @@ static int check_shapes(mimo_ctx* ctx, int K) {
   if (!ctx->Z) return fail(ctx, MIMO_E_NODATA, "no data uploaded or attached");
   if (K < 1) return fail(ctx, MIMO_E_INVALID, "K must be >= 1 (got %d)", K);
   if (K > 256) return fail(ctx, MIMO_E_UNSUPPORTED, "K = %d > 256 is not covered by the fused kernels", K);
+  ctx->pass_order = nullptr;
+  if (ctx->order_K != K) ctx->order_K = 0;       // a component order belongs to its K
   return MIMO_OK;
+}
+
+// Does this pass run under the context's component order?  The single-pass softmax + statistics request on the fused tile
+// kernel at K <= 64 (resolve_fused: the kFastVI instantiations) and nothing else (include/mimo_hip.h).
+static bool order_applies(const mimo_ctx* ctx, const Route& route, const KernelArgs& a) {
+  return ctx->order_K == a.K && a.K16 <= 4 && route.family == Family::Fused && route.image == Image::Generic && !route.promoted &&
+         a.do_stats && !a.gibbs && !a.split && !a.resp && !a.logp && !a.lse && !a.u && ctx->n_bad == 0;
 }
 
 static void fill_args(mimo_ctx* ctx, int K, KernelArgs* a) {
@@ -373,7 +388,17 @@ static int upload_theta_for(mimo_ctx* ctx, const Route& route, const double* c, 
   // every wave streams 1 (K <= 64) or up to 4 row blocks, unused ones are zero; the fused kernels step through F16 / 4 slices
   // per row block, the chunked E-step through whole chunks
   const int K16 = (K + 15) / 16;
-  return stage(ThetaGeneric{D, K, st, K16 <= 4 ? 4 : 16, fused_covers(K16, F16 / 16, kSrcEstep) ? F16 / 4 : chunked_ns_pad(F16)});
+  ThetaGeneric pl = {D, K, st, K16 <= 4 ? 4 : 16, fused_covers(K16, F16 / 16, kSrcEstep) ? F16 / 4 : chunked_ns_pad(F16)};
+  if (!order_applies(ctx, route, *a)) return stage(pl);
+  // under a component order: component order[s] goes to slot s, and the order itself rides behind the image (same transfer)
+  // for the unpack step, which writes slot s back to row order[s]
+  int32_t slot_of[64];
+  for (int s = 0; s < K; ++s) slot_of[ctx->order[s]] = s;
+  pl.slot_of = slot_of;
+  const int rc = stage_theta(ctx, pl, c, b, W, 1, reinterpret_cast<const uint64_t*>(ctx->order), (size_t)(K + 1) / 2, nullptr);
+  a->theta = ctx->theta_d;
+  ctx->pass_order = reinterpret_cast<const int32_t*>(ctx->theta_d + pl.count());
+  return rc;
 }
 
 // What the router reads of the context
@@ -621,7 +646,7 @@ static int deliver(mimo_ctx* ctx, const KernelArgs& a, int flags, double* S, dou
   const int F = small ? feat_count(D) : ctx->F, mask = small ? ctx->structure : 0;
   if (device_out) {
     HIP_TRY(ctx, launch_reduce_unpack(ctx->partials, l.grid, (int64_t)l.pstride, feat, K, D, F, a.F16, want_stats ? S : nullptr, scalars,
-                                      ctx->stream, mask));
+                                      ctx->stream, mask, ctx->pass_order));
     if (ctx->comm) {     // sharded through this library: sum over the ranks where the caller wants the block
       char msg[256];
       if (want_stats && (rc = mimo_comm::allreduce_sum_f64(ctx->comm, S, slen, ctx->stream, msg, sizeof msg))) return fail(ctx, rc, "%s", msg);
@@ -637,7 +662,7 @@ static int deliver(mimo_ctx* ctx, const KernelArgs& a, int flags, double* S, dou
   double* dst = direct ? ctx->S_h.p : ctx->S_d.p;
   if (ctx->comm && !want_stats) HIP_TRY(ctx, hipMemsetAsync(ctx->S_d, 0, slen * sizeof(double), ctx->stream));
   HIP_TRY(ctx, launch_reduce_unpack(ctx->partials, l.grid, (int64_t)l.pstride, feat, K, D, F, a.F16, want_stats ? dst : nullptr,
-                                    dst + slen, ctx->stream, mask));
+                                    dst + slen, ctx->stream, mask, ctx->pass_order));
   if (ctx->comm) {       // ONE all-reduce(sum, f64) of [K (1 + Dz + Dz^2) + 3] per pass, behind the kernels on the same stream
     char msg[256];
     if ((rc = mimo_comm::allreduce_sum_f64(ctx->comm, ctx->S_d, slen + 3, ctx->stream, msg, sizeof msg))) return fail(ctx, rc, "%s", msg);
@@ -788,6 +813,7 @@ static int set_data(mimo_ctx* ctx, int64_t N, int Dz) {
   if (Dz < 1 || Dz > kMaxD)
     return fail(ctx, MIMO_E_UNSUPPORTED, "Dz = %d outside [1, %d]", Dz, kMaxD);
   ctx->N = N; ctx->D = Dz;
+  ctx->order_K = 0;
   ctx->batched = false;
   ctx->resp_valid = ctx->logp_valid = ctx->lse_valid = ctx->labels_valid = false;
   ctx->weights_resident = false;
@@ -889,7 +915,28 @@ int mimo_set_structure(mimo_ctx* ctx, int structure) {
   if (ctx->structure == structure) return MIMO_OK;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));    // the feature table may be in use
   ctx->structure = structure;
+  ctx->order_K = 0;
   return ctx->D > 0 ? prepare_features(ctx, ctx->D) : MIMO_OK;
+  });
+}
+
+int mimo_set_component_order(mimo_ctx* ctx, const int32_t* order, int K) {
+  return guarded(ctx, [&]() -> int {
+  if (!ctx) return fail(nullptr, MIMO_E_INVALID, "null context");
+  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
+  if (K < 1 || K > 256) return fail(ctx, MIMO_E_INVALID, "mimo_set_component_order: K = %d outside [1, 256]", K);
+  if (!order || !ctx->block_order_on) { ctx->order_K = 0; return MIMO_OK; }
+  bool seen[256] = {false};
+  for (int s = 0; s < K; ++s) {
+    if (order[s] < 0 || order[s] >= K)
+      return fail(ctx, MIMO_E_INVALID, "mimo_set_component_order: order[%d] = %d is no component of 0 .. %d", s, (int)order[s], K - 1);
+    if (seen[order[s]])
+      return fail(ctx, MIMO_E_INVALID, "mimo_set_component_order: component %d sits in two slots (the second: %d)", (int)order[s], s);
+    seen[order[s]] = true;
+  }
+  memcpy(ctx->order, order, sizeof(int32_t) * (size_t)K);
+  ctx->order_K = K;
+  return MIMO_OK;
   });
 }
 
@@ -1376,13 +1423,16 @@ int mimo_tune(mimo_ctx* ctx, const char* key, int64_t value) {
     if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
     RouteTunables& t = g_route_tunables;     // process-wide, as sorted_range and narrow_big_vi (include/mimo_hip.h)
     const struct { const char* key; int max; int* knob; } keys[] = {
-        {"num_cu", 4096, nullptr}, {"resp_skip_log2", 1000, &ctx->resp_skip_log2}, {"sorted_range", 80, nullptr}, {"narrow_big_vi", 256, nullptr},
+        {"num_cu", 4096, nullptr}, {"resp_skip_log2", 1000, &ctx->resp_skip_log2}, {"block_order", 1, &ctx->block_order_on}, {"sorted_range", 80, nullptr}, {"narrow_big_vi", 256, nullptr},
         {"mid_labels_narrow_k", 64, &t.mid_labels_narrow_k}, {"mid_labels_min_d", 64, &t.mid_labels_min_d},
         {"mid_narrow_k", 64, &t.mid_narrow_k}, {"mid_min_d", 64, &t.mid_min_d}};
     for (const auto& m : keys) {
       if (strcmp(key, m.key)) continue;
       if (value < 0 || value > m.max) return fail(ctx, MIMO_E_INVALID, "mimo_tune: %s = %lld outside [0, %d]", key, (long long)value, m.max);
-      if (m.knob) *m.knob = (int)value;
+      if (m.knob) {
+        *m.knob = (int)value;
+        if (m.knob == &ctx->block_order_on && !value) ctx->order_K = 0;     // switched off: an order in force goes with it
+      }
       else if (!strcmp(key, "num_cu")) ctx->num_cu = value == 0 ? ctx->hw_num_cu : (int)value;
       else if (!strcmp(key, "sorted_range")) set_sorted_range_cap((int)value);
       else set_narrow_big_vi((int)value);
@@ -1516,6 +1566,7 @@ int mimo_plan(mimo_ctx* ctx, int K, int gibbs, int64_t* out8) {
   a.gibbs = gibbs ? 1 : 0;
   const Route route = route_for(ctx, K, {kSrcEstep, gibbs != 0});
   plan_route(ctx, route, a, K, gibbs, out8, nullptr, 0);
+  if (order_applies(ctx, route, a)) out8[0] |= MIMO_PLAN_ORDERED;
   out8[6] = route_grid(route, a, ctx->num_cu, ctx->F, kSrcEstep);
   out8[7] = ctx->num_cu;
   return MIMO_OK;

@@ -7,6 +7,7 @@
 //
 // Reference semantics: mimo/distributions/composite.py:50-72,106-118 (Normal-Wishart),
 // :577-599,635-647 (Matrix-Normal-Wishart), wishart.py:139-143, bayesian.py:287-301,933-947.
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <functional>
@@ -954,6 +955,140 @@ int mimo_host_checksum(const void* data, size_t nbytes, uint64_t out[2]) {
   }
   out[0] = A;
   out[1] = B;
+  return MIMO_OK;
+  });
+}
+
+// Slot order of the K components for the fused mean-field pass (mimo_set_component_order): components that answer the same
+// rows share a row block of 16, the blocks' masses as equal as that allows.  The responsibility skip contracts a row in every
+// row block that holds ONE component with a weight above the threshold, so two components on one cluster in two blocks cost
+// every row of the cluster twice.
+//   1. mass < 1: a filler (answers no row); it takes whatever slot is left.
+//   2. single linkage over the others: the edges of the minimum spanning tree of their means (squared distance), ascending;
+//      an edge merges its two clusters while the result has at most 16 members and at most 1 / (4 nblocks) of the total mass.
+//   3. the clusters, heaviest first, into the lightest block that has room; member by member only when none has.
+//   4. fillers in index order into the free slots; the padding slots (K % 16 != 0) stay behind the last block.
+// Pure: no state, no threads, every tie to the lower index.
+int mimo_host_block_order(int K, int D, const double* means, const double* mass, int block, int32_t* order) {
+  return guarded_host([&]() -> int {
+  if (K < 1 || D < 1 || block != 16 || !means || !mass || !order) return MIMO_E_INVALID;
+  if (K > 256) return MIMO_E_UNSUPPORTED;       // (as every pass of the library)
+  for (size_t i = 0; i < (size_t)K * D; ++i) if (!std::isfinite(means[i])) return MIMO_E_INVALID;
+  double total = 0.0;
+  for (int k = 0; k < K; ++k) { if (!std::isfinite(mass[k])) return MIMO_E_INVALID; total += mass[k]; }
+  const int nb = (K + 15) / 16;
+  std::vector<int32_t> act;                     // the components that answer rows, in index order
+  act.reserve((size_t)K);
+  for (int k = 0; k < K; ++k) if (mass[k] >= 1.0) act.push_back(k);
+  const int A = (int)act.size();
+  // Single linkage merges along the edges of the minimum spanning tree of the active components, and a tree has A - 1 edges
+  // where the graph has A (A - 1) / 2 pairs (2 016 at K = 64: sorting them alone took 20 us).  Prim's algorithm: every step
+  // takes the squared distances from the node that just joined to the nodes still outside, which are kept packed (the last
+  // one moves into the gap) with their means transposed, so a step is a unit-stride loop over them, 16 at a time in four
+  // independent sums over the dimensions in index order.  Ties: the outside node of the lower index joins first; between two
+  // tree nodes at the same distance from it the one that joined first keeps the edge.
+  struct Edge { double d; int32_t lo, hi; };
+  std::vector<Edge> edge;
+  edge.reserve((size_t)(A > 0 ? A - 1 : 0));
+  if (A > 1) {
+    const int Ap = (A + 15) / 16 * 16;
+    // position p < n: an outside node, id[p] its position in act; best = -1 marks the unused lanes (no distance is below it)
+    std::vector<double> mt((size_t)D * Ap, 0.0), best((size_t)Ap, -1.0), from((size_t)Ap, 0.0);
+    std::vector<int32_t> id((size_t)Ap, 0);
+    int n = A - 1;                                         // node 0 starts the tree
+    for (int p = 0; p < n; ++p) {
+      id[p] = p + 1; best[p] = HUGE_VAL;
+      for (int a = 0; a < D; ++a) mt[(size_t)a * Ap + p] = means[(size_t)act[p + 1] * D + a];
+    }
+    auto ld = [](const double* q) { v4d v; memcpy(&v, q, sizeof v); return v; };
+    auto st = [](double* q, v4d v) { memcpy(q, &v, sizeof v); };
+    const v4d inf = {HUGE_VAL, HUGE_VAL, HUGE_VAL, HUGE_VAL}, zero = {0.0, 0.0, 0.0, 0.0};
+    int u = 0;
+    while (n > 0) {
+      const double* mu = means + (size_t)act[u] * D;
+      const v4d ud = zero + (double)u;
+      v4d low = inf;
+      for (int j = 0; j < n; j += 16) {
+        v4d acc[4] = {zero, zero, zero, zero};
+        const double* ma = mt.data() + j;
+        for (int a = 0; a < D; ++a, ma += Ap) {
+          const double m = mu[a];
+          for (int c = 0; c < 4; ++c) { const v4d e = ld(ma + 4 * c) - m; acc[c] += e * e; }
+        }
+        for (int c = 0; c < 4; ++c) {
+          double* bp = best.data() + j + 4 * c;
+          double* fp = from.data() + j + 4 * c;
+          const v4d b = ld(bp), f = ld(fp);
+          const auto take = acc[c] < b;
+          const v4d nearest = take ? acc[c] : b;
+          st(bp, nearest);
+          st(fp, take ? ud : f);
+          const v4d key = nearest < zero ? inf : nearest;
+          low = key < low ? key : low;
+        }
+      }
+      double lowest = low[0] < low[1] ? low[0] : low[1];
+      const double l23 = low[2] < low[3] ? low[2] : low[3];
+      lowest = l23 < lowest ? l23 : lowest;
+      int v = -1;
+      for (int p = 0; p < n; ++p) if (best[p] == lowest && (v < 0 || id[p] < id[v])) v = p;
+      const int32_t x = (int32_t)from[v], y = id[v];
+      edge.push_back({lowest, x < y ? x : y, x < y ? y : x});
+      u = y;
+      --n;                                                 // the last outside node moves into the gap
+      id[v] = id[n]; best[v] = best[n]; from[v] = from[n];
+      for (int a = 0; a < D; ++a) mt[(size_t)a * Ap + v] = mt[(size_t)a * Ap + n];
+      best[n] = -1.0;
+    }
+    std::sort(edge.begin(), edge.end(), [](const Edge& x, const Edge& y) {
+      return x.d != y.d ? x.d < y.d : x.lo != y.lo ? x.lo < y.lo : x.hi < y.hi;
+    });
+  }
+  // the tree's edges, ascending, under the two caps
+  std::vector<int32_t> root((size_t)A), members((size_t)A, 1);
+  std::vector<double> cm((size_t)A);
+  for (int i = 0; i < A; ++i) { root[i] = i; cm[i] = mass[act[i]]; }
+  auto find = [&root](int i) { while (root[i] != i) { root[i] = root[root[i]]; i = root[i]; } return i; };
+  const double cap = total / (4.0 * nb);
+  for (const Edge& e : edge) {
+    int a = find(e.lo), b = find(e.hi);
+    if (a == b || members[a] + members[b] > 16 || !(cm[a] + cm[b] <= cap)) continue;
+    if (b < a) { const int t = a; a = b; b = t; }          // the root is the cluster's lowest position
+    root[b] = a; members[a] += members[b]; cm[a] += cm[b];
+  }
+  // clusters by mass, heaviest first (ties: the lower root), each into the lightest block with room
+  std::vector<int32_t> cl;
+  for (int i = 0; i < A; ++i) if (find(i) == i) cl.push_back(i);
+  for (size_t x = 1; x < cl.size(); ++x) {                  // insertion sort: a few dozen clusters
+    const int32_t c = cl[x];
+    size_t y = x;
+    for (; y > 0 && cm[cl[y - 1]] < cm[c]; --y) cl[y] = cl[y - 1];
+    cl[y] = c;
+  }
+  std::vector<int32_t> used((size_t)nb, 0), room((size_t)nb, 16);
+  std::vector<double> bm((size_t)nb, 0.0);
+  room[nb - 1] = K - 16 * (nb - 1);
+  for (int k = 0; k < K; ++k) order[k] = -1;
+  auto lightest = [&](int need) {
+    int best = -1;
+    for (int b = 0; b < nb; ++b)
+      if (room[b] - used[b] >= need && (best < 0 || bm[b] < bm[best])) best = b;
+    return best;
+  };
+  auto put = [&](int b, int pos) { order[16 * b + used[b]++] = act[pos]; bm[b] += mass[act[pos]]; };
+  for (const int32_t c : cl) {
+    const int b = lightest(members[c]);
+    for (int i = c; i < A; ++i) {
+      if (find(i) != c) continue;
+      put(b >= 0 ? b : lightest(1), i);                    // (the actives number at most K: a block with one free slot exists)
+    }
+  }
+  int s = 0;
+  for (int k = 0; k < K; ++k) {
+    if (mass[k] >= 1.0) continue;
+    while (order[s] >= 0) ++s;
+    order[s] = k;
+  }
   return MIMO_OK;
   });
 }

@@ -92,7 +92,8 @@ hipError_t launch_reduce(const double* partials, int G, int64_t stride, double* 
 // only the entries of that structure are real (small-shape kernel): the others come back as zeros
 // both in one launch (mimo_small.hip)
 hipError_t launch_reduce_unpack(const double* partials, int G, int64_t stride, const uint8_t* feat, int K, int D, int F, int F16,
-                                double* S_packed, double* scalars3, hipStream_t stream, int mask_structure = 0);
+                                double* S_packed, double* scalars3, hipStream_t stream, int mask_structure = 0,
+                                const int32_t* order = nullptr);       // order (device, K entries): row k of the block is delivered as row order[k]
 hipError_t launch_unpack(const double* reduced, const uint8_t* feat, int K, int D, int F, int F16,
                          double* S_packed, double* scalars3, hipStream_t stream, int mask_structure = 0);
 

@@ -564,7 +564,8 @@ hipError_t launch_mask_table(const double* table, const double* mask, double* ou
 constexpr int kRuWG = 1024, kRuSlices = kRuWG / 64;
 __global__ __launch_bounds__(kRuWG) void reduce_unpack_kernel(const double* __restrict__ partials, int G, int64_t stride,
                                                              const uint8_t* __restrict__ feat, int K, int D, int F, int F16,
-                                                             double* __restrict__ S, double* __restrict__ scalars, int mask_structure) {
+                                                             double* __restrict__ S, double* __restrict__ scalars, int mask_structure,
+                                                             const int32_t* __restrict__ order) {
   __shared__ double part[kRuSlices][64];
   __shared__ double fin[64];
   const int ex = threadIdx.x & 63, gs = threadIdx.x >> 6;
@@ -604,7 +605,8 @@ __global__ __launch_bounds__(kRuWG) void reduce_unpack_kernel(const double* __re
       const int aa = feat[2 * f], bb = feat[2 * f + 1];
       if (mask_structure == 1 && aa != bb && bb != D) v = 0.0;     // (small-shape kernel under a structure hint: see unpack_stats)
       if (mask_structure == 2 && bb != D) v = 0.0;
-      double* Sk = S + (int64_t)k * (1 + D + D * D);
+      // (a pass under a component order, mimo_set_component_order: slot k of the kernels holds the caller's component order[k])
+      double* Sk = S + (int64_t)(order ? order[k] : k) * (1 + D + D * D);
       if (aa == D) Sk[0] = v;
       else if (bb == D) Sk[1 + aa] = v;
       else { Sk[1 + D + aa * D + bb] = v; Sk[1 + D + bb * D + aa] = v; }
@@ -622,13 +624,13 @@ __global__ __launch_bounds__(kRuWG) void reduce_unpack_kernel(const double* __re
 }
 
 hipError_t launch_reduce_unpack(const double* partials, int G, int64_t stride, const uint8_t* feat, int K, int D, int F, int F16,
-                                double* S_packed, double* scalars3, hipStream_t stream, int mask_structure) {
+                                double* S_packed, double* scalars3, hipStream_t stream, int mask_structure, const int32_t* order) {
   if (S_packed && F < feat_count(D)) {   // reduced feature map: the entries outside it are zeros
     hipError_t e = hipMemsetAsync(S_packed, 0, sizeof(double) * (size_t)K * (1 + D + (size_t)D * D), stream);
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(reduce_unpack_kernel, dim3((unsigned)((stride + 63) / 64)), dim3(kRuWG), 0, stream, partials, G, stride, feat,
-                     K, D, F, F16, S_packed, scalars3, mask_structure);
+                     K, D, F, F16, S_packed, scalars3, mask_structure, order);
   return hipGetLastError();
 }
 

@@ -70,13 +70,17 @@ inline ThetaFail theta_entries(int D, int K, int structure, const double* c, con
 // tile kernels (mimo_kernels.h, KernelArgs::theta): [RB][NS][64], component k in slot k % 16 of row block k / 16, feature f in
 // lane quarter f % 4 of step f / 4.  RB row blocks are streamed (the rest stay zero); NS = F16 / 4 for the single-pass kernels
 // and the per-problem slice of the batched ones, chunked_ns_pad(F16) for the two-stage path.
+// slot_of (mimo_set_component_order; null: the identity): component k < K sits in slot slot_of[k], a permutation of 0 .. K-1; the
+// padding slots stay where they are.
 struct ThetaGeneric {
   int D, K, structure, RB, NS;
+  const int32_t* slot_of = nullptr;
   size_t count() const { return (size_t)RB * NS * 64; }
   int slots() const { return (K + 15) / 16 * 16; }
   size_t at(int k, int a, int b) const {
     const int f = struct_feat_index(structure, D, a, b);
-    return ((size_t)(k / 16) * NS + f / 4) * 64 + (f % 4) * 16 + k % 16;
+    const int s = slot_of && k < K ? slot_of[k] : k;
+    return ((size_t)(s / 16) * NS + f / 4) * 64 + (f % 4) * 16 + s % 16;
   }
 };
 

@@ -19,7 +19,8 @@ def _prior_block(prior):
 
 def gmm_vi_sweep(gating, components, stats, counts):
     """-> ((c, b, W), prior_terms) with prior_terms() -> float to be called after the pass is launched, or None when the
-    models are not the ones the native calls cover.
+    models are not the ones the native calls cover.  prior_terms.block_order is the slot order mimo_host_block_order chooses
+    from the posterior means and the counts just written (int32 (K,), for engine.set_component_order), or None (K <= 16).
 
     gating: CategoricalWithDirichlet; components: Stacked/TiedGaussiansWithNormalWisharts whose prior / posterior are exactly
     Stacked/TiedNormalWisharts; stats = Stats([sum r x, n, sum r xx', n]); counts = what the gating update consumes."""
@@ -63,6 +64,12 @@ def gmm_vi_sweep(gating, components, stats, counts):
     nat = Stats([qb[:, None] * mus, qb, nat_c.reshape(K, D, D), nus - D]) if tied else Stats([qa, qb, qc, qd])
     post._set_memo(nat=nat, hld=hld, estats=(bb, E2, - 0.5 * W, E4), canon=(cc, bb, W), native=True)
 
+    order = None               # (K <= 16: one row block, nothing to order)
+    if K > 16:
+        order = np.empty(K, dtype=np.int32)
+        if lib.mimo_host_block_order(K, D, p_mus, _p(cnt), 16, _p(order)) != 0:
+            order = None       # (K beyond the library's range, a count that is not finite: the pass runs in the identity)
+
     def prior_terms():
         rc = lib.mimo_host_gmm_vi_bound(K, D, int(tied), _p(alpha0), p_alpha, p_elp, _p(pa), _p(pb), _p(pc), _p(pd), _p(plz),
                                         p_qa, p_qb, p_qc, p_qd, p_mus, p_nus, p_hld, p_natc, p_bb, p_E2, p_W, p_E4, p_vlb)
@@ -70,4 +77,5 @@ def gmm_vi_sweep(gating, components, stats, counts):
             raise RuntimeError("mimo_host_gmm_vi_bound failed (%d)" % rc)
         return float(vlb[0] + vlb[1])       # (blk stays alive through the views captured here)
 
+    prior_terms.block_order = order
     return (c_total, bb, W), prior_terms

@@ -194,6 +194,16 @@ class HipEngine(BoundDataGuard):
             self._check(self._lib.mimo_set_structure(self._ctx, code))
             self._structure = code
 
+    def set_component_order(self, order):
+        """Slot order of the components inside the fused mean-field pass (mimo_set_component_order): order[s] is the
+        component in slot s, None the identity.  Results stay in the caller's numbering; routes outside the single-pass
+        fused kernel ignore it.  It holds until replaced, or until K, the data or the structure change."""
+        if order is None:
+            self._check(self._lib.mimo_set_component_order(self._ctx, None, 1))
+            return
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        self._check(self._lib.mimo_set_component_order(self._ctx, _ptr(order), int(order.shape[0])))
+
     # -- 'linear' structure: what the shared quadratic term -1/2 z'W z adds back -------------------
     class _AsFull:
         def __init__(self, eng):
@@ -246,7 +256,8 @@ class HipEngine(BoundDataGuard):
 
     def tune(self, key, value):
         """Launch-geometry override for tests and experiments (mimo_tune): 'num_cu' (0: the device's own), 'sorted_range',
-        'resp_skip_log2' (statistics skip weights below 2^-value, default 60; 0: dense)."""
+        'resp_skip_log2' (statistics skip weights below 2^-value, default 60; 0: dense), 'block_order' (0: set_component_order
+        becomes a no-op, default 1)."""
         self._check(self._lib.mimo_tune(self._ctx, key.encode(), int(value)))
 
     def profile(self, enable=True):
@@ -283,6 +294,7 @@ class HipEngine(BoundDataGuard):
         """How a pass with K components runs on the resident data (mimo_plan): kind, kernels, HBM passes."""
         o = (C.c_int64 * 8)()
         self._check(self._lib.mimo_plan(self._ctx, int(K), 1 if gibbs else 0, o))
+        ordered, o[0] = bool(o[0] & 0x100), o[0] & 0xff          # MIMO_PLAN_ORDERED: a component order is in force for this K
         kind = {1: "fused", 2: "two-stage", 3: "small", 4: "rowwave", 5: "rowwave-vi", 6: "narrow", 7: "mid"}.get(o[0], "?")
         kernel = {1: "mimo::fused_kernel", 2: "E-step (mimo::wide_estep_kernel / estep_chunked_kernel) + statistics per column group (mimo::wide_stats_kernel / fused_kernel)",
                   3: "mimo::small_kernel", 4: "mimo::gibbs_rowwave_kernel + mimo::label_stats_kernel",
@@ -291,7 +303,7 @@ class HipEngine(BoundDataGuard):
                   7: "mimo::mid_kernel"}.get(o[0], "?")
         return {"kind": kind, "kernel": kernel, "kernels_per_pass": int(o[1]), "table_in_hbm": bool(o[2]),
                 "table_reads": int(o[3]), "data_passes": int(o[4]), "label_passes": int(o[5]),
-                "workgroups": int(o[6]), "compute_units": int(o[7])}
+                "workgroups": int(o[6]), "compute_units": int(o[7]), "component_order": ordered}
 
     # -- data -----------------------------------------------------------------------------
     def upload(self, Z):

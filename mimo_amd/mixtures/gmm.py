@@ -189,6 +189,8 @@ class MixtureOfGaussians:
 class BayesianMixtureOfGaussians:
     """reference: mimo/mixtures/gmm.py:147-371 (plotting omitted)."""
 
+    _ordered = False           # the last mean-field pass ran under a component order (meanfield_iteration)
+
     def __init__(self, gating, components, engine=None):
         self.gating = gating
         self.components = components
@@ -382,6 +384,10 @@ class BayesianMixtureOfGaussians:
             self._update_from_stats(S, sample=False)
             canon = self.canonical_expected()
         if hasattr(eng, "estep_async"):
+            order = None if fused is None else bound.block_order
+            if hasattr(eng, "set_component_order") and (order is not None or self._ordered):
+                eng.set_component_order(order)            # components of one cluster into one row block of the fused pass
+                self._ordered = order is not None
             eng.estep_async(*canon)
             if sample_likelihood:
                 self._refresh_likelihoods()

@@ -283,6 +283,12 @@ class ShardedEngine:
         if hasattr(self.inner, 'set_structure'):
             self.inner.set_structure(structure)        # (native route: the inner engine's pooled moment is already global)
 
+    def set_component_order(self, order):
+        """Forwarded to this rank's engine (HipEngine.set_component_order).  Every rank has to set the same order: the
+        statistics are summed in the caller's numbering, but the bits of a rank's block depend on its slot order."""
+        if hasattr(self.inner, 'set_component_order'):
+            self.inner.set_component_order(order)
+
     def estep(self, c, b, W, stats=True, keep_resp=False, keep_logp=False, keep_lse=False, entropy_split=False,
               row_weights=None):
         """`row_weights` are the weights of THIS rank's rows (hierarchical drivers)."""

@@ -12,7 +12,12 @@ the Gibbs warm-up, if one is asked for, N outer iterations of stochastic VI with
 (meanfield_stochastic_descent_batched, randomize=False, step size 0.5): per iteration one batched pass over the rows
 every model drew — gathered on the device from the resident data — and one over all rows for the bounds.  Each model's numpy
 stream is seeded like its joblib worker (0 .. fits - 1); the workers leave Python's `random`, which draws the minibatches,
-unseeded, and here each model gets a stream of its own seeded the same way, so a run is reproducible."""
+unseeded, and here each model gets a stream of its own seeded the same way, so a run is reproducible.
+
+--predict adds what the reference job is run for (its lines 196-201): ONE batched prediction of all fitted models over the
+full input grid (meanfield_prediction_batched: the grid goes to the device once, each model's standardisation is applied in
+the kernel), then the four curves of the reference's figure — the mean and the standard deviation across models of mu and
+of std — and one summary line: the RMSE of the ensemble mean against sinc and the mean ensemble spread."""
 import argparse
 import os
 import sys
@@ -27,8 +32,8 @@ from mimo_amd.distributions import (TruncatedStickBreaking, CategoricalWithStick
                                     StackedLinearGaussiansWithMatrixNormalWisharts)
 from mimo_amd.engine import HipEngine
 from mimo_amd.mixtures import BayesianMixtureOfLinearGaussians
-from mimo_amd.mixtures.batched import (meanfield_coordinate_descent_batched, meanfield_stochastic_descent_batched,
-                                        resample_batched)
+from mimo_amd.mixtures.batched import (meanfield_coordinate_descent_batched, meanfield_prediction_batched,
+                                        meanfield_stochastic_descent_batched, resample_batched)
 
 
 def make_model(K, engine):
@@ -54,6 +59,7 @@ def main():
     ap.add_argument("--gibbs-iters", type=int, default=0, help="Gibbs warm-up sweeps before VI (0: random VI start)")
     ap.add_argument("--svi-iters", type=int, default=0, help="outer iterations of stochastic VI (0: coordinate-descent VI)")
     ap.add_argument("--svi-batch", type=int, default=256, help="rows per minibatch of stochastic VI")
+    ap.add_argument("--predict", action="store_true", help="one batched prediction of all models on the full input grid")
     args = ap.parse_args()
     rng = np.random.default_rng(1337)
     x = rng.uniform(-10., 10., size=(args.rows, 1))
@@ -85,6 +91,18 @@ def main():
     final = np.array([v[-1] for v in vlbs])
     print(f"{args.fits} fits of {ntrain} rows, K = {args.experts}: best ELBO {final.max():.2f}, median {np.median(final):.2f}, "
           f"iterations {min(map(len, vlbs))} - {max(map(len, vlbs))}, wall time {wall:.2f} s")
+    if args.predict:
+        t0 = time.perf_counter()
+        preds = meanfield_prediction_batched(models, x, prediction='average')
+        wall = time.perf_counter() - t0
+        mus = np.stack([p[0] for p in preds])                   # (fits, rows, 1)
+        stds = np.stack([p[2] for p in preds])
+        mu_mean, mu_std = mus.mean(axis=0), mus.std(axis=0)     # the reference's four curves (evaluate_sinc_parallel.py:203-208)
+        std_mean, std_std = stds.mean(axis=0), stds.std(axis=0)
+        rmse = float(np.sqrt(np.mean((mu_mean - np.sinc(x / np.pi)) ** 2)))
+        print(f"ensemble prediction of {args.fits} models on {args.rows} inputs in one launch ({wall * 1e3:.1f} ms): "
+              f"RMSE of the ensemble mean against sinc {rmse:.4f}, mean ensemble spread {float(mu_std.mean()):.4f} "
+              f"(mean predictive std {float(std_mean.mean()):.4f}, its spread {float(std_std.mean()):.4f})")
 
 
 if __name__ == "__main__":

@@ -399,6 +399,34 @@ int mimo_weighted_stats_batched(mimo_ctx* ctx, const double* resp, int K, int fl
  * mimo_estep_batched. */
 int mimo_random_resp_stats_batched(mimo_ctx* ctx, int K, const uint64_t* seeds, int flags, double* S);
 
+/* Posterior-predictive mixture moments of B ILR models in one launch: per problem b what mimo_predict_flags returns on a
+ * context whose resident rows are (X_b - shift_b) / scale_b, bit for bit, and the same bits whatever else is in the batch.
+ * Replaces: the loop `for ilr in ilrs: ilr.meanfield_prediction(input)` of examples/ilr/evaluate_sinc_parallel.py:196-201 over
+ *   mimo/mixtures/ilr.py:374-430 (one upload, one parameter staging, one launch and three copies per model).
+ * The rows are an ARGUMENT, not state: the call needs no uploaded data and no batch (a fresh context will do), and it leaves
+ *   everything resident as it was — single data or a batch with its work tables, the kept lse / resp / logp / labels and their
+ *   validity.  (It overwrites the staging workspaces, like mimo_predict_flags: nothing resident lives there.)
+ * Rows.  Ragged form: row_off [B + 1] (host; row_off[0] = 0, non-decreasing), X (row_off[B], dx) the problems' query rows
+ *   concatenated, N_shared = 0; problem b's outputs start at row row_off[b], in the layouts of mimo_predict_flags with N = N_b
+ *   (with MIMO_F_DIAG_VAR its block [var (N_b, dy) | std (N_b, dy)] starts at element 2 dy row_off[b]).  Shared form:
+ *   row_off = NULL, X (N_shared, dx) read by every problem (uploaded once); problem b's outputs start at row b N_shared.
+ *   y (for nlpd) takes the form of X with dy columns.
+ * Standardisation.  x_tf (B, 2, dx) and y_tf (B, 2, dy): per problem a row of shifts and a row of scales; the kernel reads
+ *   x_i = (X[n, i] - shift_i) / scale_i — one IEEE subtraction, one IEEE division: the bits of NumPy's (X - shift) / scale.
+ *   NULL: the rows are taken as they are.  A scale that is zero or not finite: MIMO_E_INVALID.
+ * Parameter blocks carry a leading B: c (B, K), b (B, K, dx), W (B, K, dx, dx), M (B, K, dy, dx + 1), Q (B, K, dx + 1, dx + 1),
+ *   Cc / P (B, K, dy, dy), ld (B, K); their meaning and mode (0 mixture moments, 1 arg-max component) are mimo_predict's.
+ *   nlpd non-NULL needs y, P and ld; y_tf needs y.
+ * Coverage: affine experts (dc = dx + 1), 1 <= dx <= 8, 1 <= dy <= 8, any K >= 1, 1 <= B <= 65535; MIMO_E_UNSUPPORTED otherwise
+ *   (no fallback to the generic prediction kernel).  flags: MIMO_F_DIAG_VAR only (host pointers throughout).
+ * MIMO_E_STATE while an asynchronous call is pending; MIMO_E_UNSUPPORTED with a communicator attached.  An all-empty batch
+ *   returns MIMO_OK without a launch. */
+int mimo_predict_batched(mimo_ctx* ctx, int B, const double* X, const int64_t* row_off, int64_t N_shared, int dx,
+                         const double* x_tf, const double* c, const double* b, const double* W, int K,
+                         const double* M, const double* Q, const double* Cc, int dy, int mode,
+                         const double* y, const double* y_tf, const double* P, const double* ld,
+                         double* mu, double* covar, double* nlpd, int flags);
+
 /* ---- copy-outs of device-resident tables ----------------------------------------------- */
 int mimo_get_resp(mimo_ctx* ctx, double* resp_host /* K×N */);
 /* The columns `cols[0 .. ncols)` (row indices of the data) of the resident responsibility table: out (K, ncols) row-major.  What a

@@ -70,6 +70,8 @@ SIGNATURES = {
                                _vp, _vp, _vp, _vp, _vp, _vp]),
     "mimo_predict_flags": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
                                      _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "mimo_predict_batched": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, C.c_int,
+                                       _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
     "mimo_get_resp": (C.c_int, [_vp, _vp]),
     "mimo_get_resp_columns": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
     "mimo_get_logp": (C.c_int, [_vp, _vp]),

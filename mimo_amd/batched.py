@@ -228,6 +228,113 @@ class BatchedHipEngine:
         self._K = K
         return [SuffStats.from_packed(S[i], K, D) for i in range(self.B)]
 
+    @staticmethod
+    def _rows_form(a, B, d, what):
+        """One (N, d) array (shared form) or a list of B arrays (ragged form) -> (rows (N_in, d), row_off | None, counts)."""
+        if isinstance(a, (list, tuple)):
+            if len(a) != B:
+                raise ValueError(f"{what}: rows for {len(a)} problems, parameters for {B}")
+            parts = [_f64(p) for p in a]
+            parts = [p.reshape(-1, d) if p.ndim == 1 and d == 1 else p for p in parts]
+            for i, p in enumerate(parts):
+                if p.ndim != 2 or p.shape[1] != d:
+                    raise ValueError(f"{what} of problem {i} must be (N_b, {d}), got shape {p.shape}")
+            counts = [p.shape[0] for p in parts]
+            row_off = np.zeros(B + 1, dtype=np.int64)
+            row_off[1:] = np.cumsum(counts)
+            flat = np.ascontiguousarray(np.concatenate(parts, axis=0)) if row_off[-1] > 0 else np.zeros((1, d))
+            return flat, row_off, counts
+        p = _f64(a)
+        if p.ndim == 1 and d == 1:
+            p = p.reshape(-1, 1)
+        if p.ndim != 2 or p.shape[1] != d:
+            raise ValueError(f"{what} must be (N, {d}) or a list of {B} such arrays, got shape {p.shape}")
+        return (p if p.shape[0] > 0 else np.zeros((1, d))), None, [p.shape[0]] * B
+
+    @staticmethod
+    def _transform_block(t, B, d, what):
+        if t is None:
+            return None
+        t = _f64(t)
+        if t.shape != (B, 2, d):
+            raise ValueError(f"{what} must be (B, 2, {d}) = (shift, scale) per problem, got shape {t.shape}")
+        if not np.all(np.isfinite(t[:, 1])) or np.any(t[:, 1] == 0.):
+            raise ValueError(f"{what}: every scale must be finite and nonzero")
+        return t
+
+    def predict(self, x, c, b, W, M, Q, Cc, mode='average', y=None, P=None, ld=None, variance='full', x_transform=None,
+                y_transform=None):
+        """Posterior-predictive mixture moments of B models in one launch (mimo_predict_batched): per problem what
+        HipEngine.predict returns on the uploaded rows (x_b - shift_b) / scale_b, bit for bit, whatever else is in the batch.
+        x: one (N, dx) array every problem reads (shared form: uploaded once) or a list of B arrays (N_b, dx) (ragged form);
+        y (for nlpd, with P and ld) takes the form of x.  c (B, K), b (B, K, dx), W (B, K, dx, dx), M (B, K, dy, dx + 1),
+        Q (B, K, dx + 1, dx + 1), Cc / P (B, K, dy, dy), ld (B, K): affine experts only, dx, dy <= 8.
+        x_transform (B, 2, dx) / y_transform (B, 2, dy): per problem (shift, scale), applied in the kernel; None: rows as they are.
+        Returns a list of B tuples (mu (N_b, dy), covar (N_b, dy, dy) | (var, std), nlpd (N_b,) | None).
+        The rows are an argument, not state: B comes from c, nothing uploaded is read and nothing resident changes."""
+        c, b, W = _f64(c), _f64(b), _f64(W)
+        if c.ndim != 2:
+            raise ValueError(f"c must be (B, K), got shape {c.shape}")
+        B, K = c.shape
+        if B < 1 or K < 1:
+            raise ValueError(f"c must hold at least one problem and one component, got shape {c.shape}")
+        if b.ndim != 3 or b.shape[:2] != (B, K) or b.shape[2] < 1:
+            raise ValueError(f"b must be (B, K, dx) = ({B}, {K}, dx), got shape {b.shape}")
+        dx = b.shape[2]
+        if W.shape != (B, K, dx, dx):
+            raise ValueError(f"W must be ({B}, {K}, {dx}, {dx}), got shape {W.shape}")
+        M, Q, Cc = _f64(M), _f64(Q), _f64(Cc)
+        if M.ndim != 4 or M.shape[:2] != (B, K) or M.shape[2] < 1:
+            raise ValueError(f"M must be (B, K, dy, dx + 1) = ({B}, {K}, dy, {dx + 1}), got shape {M.shape}")
+        dy = M.shape[2]
+        if M.shape[3] != dx + 1:
+            raise ValueError(f"affine experts only: M must be ({B}, {K}, {dy}, dx + 1 = {dx + 1}), got shape {M.shape}")
+        if Q.shape != (B, K, dx + 1, dx + 1) or Cc.shape != (B, K, dy, dy):
+            raise ValueError(f"predictive blocks {Q.shape}, {Cc.shape} do not match B={B}, K={K}, dy={dy}, dc={dx + 1}")
+        if mode not in ('average', 'mode'):
+            raise ValueError(f"mode must be 'average' or 'mode', got {mode!r}")
+        if variance not in ('full', 'diagonal'):
+            raise ValueError(f"variance must be 'full' or 'diagonal', got {variance!r}")
+        X, row_off, counts = self._rows_form(x, B, dx, "x")
+        xt = self._transform_block(x_transform, B, dx, "x_transform")
+        yt = self._transform_block(y_transform, B, dy, "y_transform")
+        Y = None
+        if y is not None:
+            if isinstance(y, (list, tuple)) != isinstance(x, (list, tuple)):
+                raise ValueError("x and y must take the same form: both one array (shared) or both lists of B arrays (ragged)")
+            if P is None or ld is None:
+                raise ValueError("nlpd (y given) needs P (B, K, dy, dy) and ld (B, K)")
+            P, ld = _f64(P), _f64(ld)
+            if P.shape != (B, K, dy, dy) or ld.shape != (B, K):
+                raise ValueError(f"nlpd needs P ({B}, {K}, {dy}, {dy}) and ld ({B}, {K}), got {P.shape}, {ld.shape}")
+            Y, _, ycounts = self._rows_form(y, B, dy, "y")
+            if ycounts != counts:
+                raise ValueError(f"y must hold one row per row of x: {ycounts} against {counts}")
+        elif yt is not None:
+            raise ValueError("y_transform without y")
+        diag = variance == 'diagonal'
+        ncov = 2 * dy if diag else dy * dy
+        total = int(sum(counts))
+        mu = np.empty(max(total, 1) * dy)
+        second = np.empty(max(total, 1) * ncov)
+        nlpd = np.empty(max(total, 1)) if Y is not None else None
+        self._check(self._lib.mimo_predict_batched(
+            self._ctx, B, _ptr(X), _ptr(row_off) if row_off is not None else None, 0 if row_off is not None else counts[0], dx,
+            _ptr(xt) if xt is not None else None, _ptr(c), _ptr(b), _ptr(W), K, _ptr(M), _ptr(Q), _ptr(Cc), dy,
+            0 if mode == 'average' else 1, _ptr(Y) if Y is not None else None, _ptr(yt) if yt is not None else None,
+            _ptr(P) if Y is not None else None, _ptr(ld) if Y is not None else None, _ptr(mu), _ptr(second),
+            _ptr(nlpd) if Y is not None else None, _lib.F_DIAG_VAR if diag else 0))
+        out, o = [], 0
+        for n in counts:
+            blk = second[o * ncov:(o + n) * ncov]
+            if diag:
+                sec = (blk[:n * dy].reshape(n, dy).copy(), blk[n * dy:].reshape(n, dy).copy())
+            else:
+                sec = blk.reshape(n, dy, dy).copy()
+            out.append((mu[o * dy:(o + n) * dy].reshape(n, dy).copy(), sec, nlpd[o:o + n].copy() if Y is not None else None))
+            o += n
+        return out
+
     def get_resp(self, K=None):
         """The table of the last random_resp_stats, resident on the device: a list of B arrays (K, N_b)."""
         K = int(K if K is not None else getattr(self, '_K', 0))

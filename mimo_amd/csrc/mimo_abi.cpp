@@ -6,6 +6,7 @@
 #include "mimo_kernels.h"
 #include "mimo_extra.h"
 #include "mimo_batched.h"
+#include "mimo_predict_batched.h"
 #include "mimo_route.h"
 #include "mimo_theta.h"
 
@@ -1922,6 +1923,118 @@ int mimo_random_resp_stats_batched(mimo_ctx* ctx, int K, const uint64_t* seeds, 
                                           ctx->stream));
   ctx->resp_K = K; ctx->resp_valid = true;
   return batched_table_stats(ctx, ctx->resp, K, S);
+  });
+}
+
+// ------------------------------------------------------------------------------------------
+// Batched prediction (mimo_predict_batched.hip)
+// ------------------------------------------------------------------------------------------
+// The rows are an argument: nothing of the context's data, batch or kept tables is read or written.  Buffers: the parameter,
+// transform and row_off blocks go through the operand image's pinned staging buffer in ONE transfer (theta_h -> theta_d, restaged
+// by every pass); X and y go through the staged-weights workspace `win`, as mimo_predict_flags uses it (pure staging: nothing
+// resident lives there, so nothing is invalidated); the outputs are one block of S_d / S_h (ensure_block / hand_out).
+int mimo_predict_batched(mimo_ctx* ctx, int B, const double* X, const int64_t* row_off, int64_t N_shared, int dx,
+                         const double* x_tf, const double* c, const double* b, const double* W, int K,
+                         const double* M, const double* Q, const double* Cc, int dy, int mode,
+                         const double* y, const double* y_tf, const double* P, const double* ld,
+                         double* mu, double* covar, double* nlpd, int flags) {
+  return guarded(ctx, [&]() -> int {
+  const char* const me = "mimo_predict_batched";
+  int rc = bind(ctx); if (rc) return rc;
+  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
+  if (ctx->comm)
+    return fail(ctx, MIMO_E_UNSUPPORTED, "%s: a communicator is attached (mimo_comm_init); the batched pass has no ranks", me);
+  if (flags & ~MIMO_F_DIAG_VAR)
+    return fail(ctx, MIMO_E_INVALID, "%s: flags 0x%x: only MIMO_F_DIAG_VAR (host pointers throughout)", me, flags);
+  if (!c || !b || !W || !M || !Q || !Cc || !mu || !covar)
+    return fail(ctx, MIMO_E_INVALID, "%s: c, b, W, M, Q, Cc, mu and covar must be non-NULL", me);
+  if (B < 1 || K < 1 || (mode != 0 && mode != 1))
+    return fail(ctx, MIMO_E_INVALID, "%s: B = %d, K = %d must be >= 1 and mode = %d must be 0 or 1", me, B, K, mode);
+  if (!predict_batched_covers(dx, dy) || B > kPredictBatchedMaxB)
+    return fail(ctx, MIMO_E_UNSUPPORTED, "%s: dx = %d, dy = %d, B = %d outside the batched prediction kernel (affine experts, "
+                "1 <= dx <= %d, 1 <= dy <= %d, B <= %d)", me, dx, dy, B, kPredictBatchedMaxDx, kPredictBatchedMaxDy, kPredictBatchedMaxB);
+  if (N_shared < 0) return fail(ctx, MIMO_E_INVALID, "%s: N_shared = %lld is negative", me, (long long)N_shared);
+  if (row_off && N_shared != 0)
+    return fail(ctx, MIMO_E_INVALID, "%s: row_off and N_shared = %lld are both given (ragged form: N_shared = 0; shared form: "
+                "row_off = NULL)", me, (long long)N_shared);
+  int64_t max_rows = N_shared;
+  if (row_off) {
+    if (row_off[0] != 0) return fail(ctx, MIMO_E_INVALID, "%s: row_off[0] = %lld, must be 0", me, (long long)row_off[0]);
+    for (int p = 0; p < B; ++p) {
+      if (row_off[p + 1] < row_off[p]) return fail(ctx, MIMO_E_INVALID, "%s: row_off decreases at problem %d", me, p);
+      max_rows = std::max<int64_t>(max_rows, row_off[p + 1] - row_off[p]);
+    }
+  }
+  const bool want_nlpd = nlpd != nullptr, diag = (flags & MIMO_F_DIAG_VAR) != 0;
+  if (want_nlpd && (!y || !P || !ld)) return fail(ctx, MIMO_E_INVALID, "%s: nlpd needs y, P and ld", me);
+  if (y_tf && !y) return fail(ctx, MIMO_E_INVALID, "%s: y_tf without y", me);
+  const int dd[2] = {dx, dy};
+  const double* const tfs[2] = {x_tf, y_tf};
+  for (int t = 0; t < 2; ++t)
+    for (int p = 0; tfs[t] && p < B; ++p)
+      for (int i = 0; i < dd[t]; ++i) {
+        const double s = tfs[t][((size_t)p * 2 + 1) * dd[t] + i];
+        if (s == 0.0 || !std::isfinite(s))
+          return fail(ctx, MIMO_E_INVALID, "%s: %s of problem %d: scale[%d] = %g must be finite and nonzero", me, t ? "y_tf" : "x_tf", p, i, s);
+      }
+  const size_t n_in = (size_t)(row_off ? row_off[B] : N_shared);        // rows of X (and y)
+  const size_t n_out = row_off ? n_in : (size_t)N_shared * (size_t)B;   // rows of the outputs
+  if (max_rows == 0) return MIMO_OK;                                    // an all-empty batch: nothing to launch
+  if (!X) return fail(ctx, MIMO_E_INVALID, "%s: X is NULL", me);
+
+  // one staged block: [gate (c, b, W interleaved per component) | M | Q | Cc | P | ld | x_tf | y_tf | row_off]
+  const int dc = dx + 1;
+  const size_t BK = (size_t)B * K, gk = 1 + (size_t)dx + (size_t)dx * dx;
+  const size_t ng = BK * gk, nM = BK * dy * dc, nQ = BK * dc * dc, nC = BK * dy * dy;
+  const size_t nxt = x_tf ? (size_t)B * 2 * dx : 0, nyt = y_tf ? (size_t)B * 2 * dy : 0, nro = row_off ? (size_t)B + 1 : 0;
+  const size_t nparam = ng + nM + nQ + 2 * nC + BK + nxt + nyt + nro;
+  if ((rc = ctx->theta_d.ensure(ctx, nparam))) return rc;
+  if ((rc = ctx->theta_h.ensure(ctx, nparam))) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));    // the staging buffer may still be in flight from the previous call on this stream
+  double* q = ctx->theta_h;
+  for (size_t k = 0; k < BK; ++k) {
+    *q++ = c[k];
+    memcpy(q, b + k * dx, sizeof(double) * dx); q += dx;
+    memcpy(q, W + k * dx * dx, sizeof(double) * dx * dx); q += (size_t)dx * dx;
+  }
+  memcpy(q, M, sizeof(double) * nM); q += nM;
+  memcpy(q, Q, sizeof(double) * nQ); q += nQ;
+  memcpy(q, Cc, sizeof(double) * nC); q += nC;
+  if (want_nlpd) { memcpy(q, P, sizeof(double) * nC); memcpy(q + nC, ld, sizeof(double) * BK); }
+  else memset(q, 0, sizeof(double) * (nC + BK));
+  q += nC + BK;
+  if (nxt) { memcpy(q, x_tf, sizeof(double) * nxt); q += nxt; }
+  if (nyt) { memcpy(q, y_tf, sizeof(double) * nyt); q += nyt; }
+  if (nro) memcpy(q, row_off, sizeof(int64_t) * nro);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, ctx->theta_h, nparam * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+
+  // the rows: X, then y
+  const size_t nX = n_in * dx, nY = want_nlpd ? n_in * dy : 0;
+  if ((rc = ctx->win.ensure(ctx, nX + nY))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->win, X, nX * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (nY) HIP_TRY(ctx, hipMemcpyAsync(ctx->win + nX, y, nY * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+
+  // the outputs: [mu | second output | nlpd], one block
+  const size_t ncov = diag ? 2 * (size_t)dy : (size_t)dy * dy;
+  const size_t n_mu = n_out * dy, n_cov = n_out * ncov, n_nl = want_nlpd ? n_out : 0, out = n_mu + n_cov + n_nl;
+  if ((rc = ensure_block(ctx, out))) return rc;
+
+  PredictBatchedArgs a{};
+  const double* d = ctx->theta_d;
+  a.X = ctx->win; a.N_shared = row_off ? 0 : N_shared;
+  a.B = B; a.dx = dx; a.dy = dy; a.K = K; a.mode = mode; a.diag = diag ? 1 : 0;
+  a.gate = d; a.M = d + ng; a.Q = a.M + nM; a.Cc = a.Q + nQ; a.P = a.Cc + nC; a.ld = a.P + nC;
+  const double* tail = a.ld + BK;
+  a.x_tf = nxt ? tail : nullptr; tail += nxt;
+  a.y_tf = nyt ? tail : nullptr; tail += nyt;
+  a.row_off = nro ? reinterpret_cast<const int64_t*>(tail) : nullptr;
+  a.y = want_nlpd ? ctx->win + nX : nullptr;
+  a.mu = ctx->S_d; a.covar = ctx->S_d + n_mu; a.nlpd = want_nlpd ? ctx->S_d + n_mu + n_cov : nullptr;
+  if ((rc = TIMED_HIP(ctx, "predict_batched_kernel", launch_predict_batched(a, max_rows, ctx->stream)))) return rc;
+  if (ctx->prof) ctx->prof_n += 1;
+  if ((rc = hand_out(ctx, out, mu, n_mu, covar, n_mu, n_cov))) return rc;
+  if (want_nlpd) memcpy(nlpd, ctx->S_h + n_mu + n_cov, n_nl * sizeof(double));
+  return MIMO_OK;
   });
 }
 

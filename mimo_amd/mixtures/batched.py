@@ -335,3 +335,58 @@ def meanfield_stochastic_descent_batched(models, data, randomize=True, maxiter=5
     finally:
         nstreams.restore()
         pstreams.restore()
+
+
+def meanfield_prediction_batched(models, x, y=None, prediction='average', dist='gaussian', incremental=False,
+                                 variance='diagonal', engine=None):
+    """meanfield_prediction of B fitted BayesianMixtureOfLinearGaussians in ONE launch (BatchedHipEngine.predict): what the
+    reference's parallel job ends with (examples/ilr/evaluate_sinc_parallel.py:196-201: every model's prediction over the
+    same inputs).  models: one size and one set of dimensions, affine experts with input_dim, output_dim <= 8 (stacked or
+    tied: both expose predictive_blocks()).  x: one (N, dx) array all models predict on (it goes to the device once), or a
+    list of B arrays; y (optional: adds nlpd) takes the form of x.  Each model's standardisation is applied in the kernel
+    (scale=False: shift 0, scale 1); the host tail is the solo method's (_prediction_tail).  engine: a BatchedHipEngine
+    (default: a new one on the device of the first model's engine); nothing it holds is read or changed.
+    Returns a list of B tuples, each what the model's solo meanfield_prediction returns — bit for bit."""
+    models = list(models)
+    B = len(models)
+    if B == 0:
+        raise ValueError("no models")
+    if any(type(m) is not BayesianMixtureOfLinearGaussians for m in models):
+        raise ValueError("the models must all be BayesianMixtureOfLinearGaussians")
+    models[0]._check_dist(dist)
+    if prediction not in ('average', 'mode'):
+        raise NotImplementedError(prediction)
+    dims = [(m.size, m.input_dim, m.output_dim) for m in models]
+    if any(d != dims[0] for d in dims):
+        raise ValueError(f"the models differ in size or dimensions: {dims}")
+    K, dx, dy = dims[0]
+    if any(not m.affine for m in models) or dx > 8 or dy > 8:
+        raise NotImplementedError("the batched prediction covers affine experts with input_dim <= 8 and output_dim <= 8 "
+                                  f"(got affine = {[bool(m.affine) for m in models]}, input_dim = {dx}, output_dim = {dy})")
+    ragged = isinstance(x, (list, tuple))
+    if ragged and len(x) != B:
+        raise ValueError(f"inputs for {len(x)} models, {B} given")
+    if y is not None and isinstance(y, (list, tuple)) != ragged:
+        raise ValueError("x and y must take the same form: both one array or both lists of B arrays")
+    xs = [np.reshape(xi, (-1, dx)) for xi in x] if ragged else np.reshape(x, (-1, dx))
+    ys = None
+    if y is not None:
+        ys = [np.reshape(yi, (-1, dy)) for yi in y] if ragged else np.reshape(y, (-1, dy))
+
+    def transform(t, scaled, d):
+        return np.stack([t.mean_, t.scale_]) if scaled else np.stack([np.zeros(d), np.ones(d)])
+    gates = [m._predictive_gate() for m in models]
+    blocks = [m.models.predictive_blocks() for m in models]
+    stack = lambda parts: np.stack([np.asarray(p, dtype=float) for p in parts])
+    c, b, W = (stack([g[i] for g in gates]) for i in range(3))
+    Ms, Q, Cc, P, ld = (stack([bl[i] for bl in blocks]) for i in range(5))
+    x_tf = np.stack([transform(m.input_transform, m.scale, dx) for m in models])
+    y_tf = np.stack([transform(m.output_transform, m.scale, dy) for m in models]) if ys is not None else None
+    if engine is None:
+        engine = BatchedHipEngine(getattr(models[0].engine, 'device', 0))
+    diag = variance == 'diagonal'
+    res = engine.predict(xs, c, b, W, Ms, Q, Cc, mode=prediction, y=ys, P=P if ys is not None else None,
+                         ld=ld if ys is not None else None, variance='diagonal' if diag else 'full',
+                         x_transform=x_tf, y_transform=y_tf)
+    return [m._prediction_tail(xs[i] if ragged else xs, y, mu, second, nlpd, incremental, diag)
+            for i, (m, (mu, second, nlpd)) in enumerate(zip(models, res))]

@@ -477,6 +477,12 @@ class BayesianMixtureOfLinearGaussians:
         mu, second, nlpd = eng.predict(*self._predictive_gate(), Ms, Q, Cc, affine=self.affine, mode=prediction,
                                        y=None if yy is None else np.ascontiguousarray(yy), P=P, ld=ld,
                                        variance='diagonal' if diag else 'full')
+        return self._prediction_tail(x, y, mu, second, nlpd, incremental, diag)
+
+    def _prediction_tail(self, x, y, mu, second, nlpd, incremental, diag):
+        """The host tail of meanfield_prediction behind the kernel (ilr.py:411-430): the inverse output transform, the
+        variances' rescaling, std, incremental.  x: the raw inputs (N, dx); mu, second, nlpd: what the engine's predict
+        returned.  Shared with the batched driver (mixtures/batched.py: meanfield_prediction_batched)."""
         if diag:
             var, std = second
             if self.scale:                         # diag(S covar S') = var * sigma^2 for the diagonal output scaling S

@@ -2,7 +2,7 @@
 data resident), on the same inputs, after warm-up; wall time per pass (each call returns synchronised host results) and the
 largest relative difference of the outputs.  Writes <out>/bench_batched.json.
 
-    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3] [--start-only | --no-start | --svi]
+    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3] [--start-only | --no-start | --svi | --predict]
 
 Also times one iteration of meanfield_coordinate_descent_batched against B solo meanfield_iteration calls at shape 1
 (24 ILR models, K = 100, dx = dy = 1), split into host time and pass time.
@@ -23,6 +23,14 @@ same run, outputs compared bit for bit; and one outer iteration of meanfield_sto
 models of shape 1 (minibatches of 256) against 24 solo meanfield_stochastic_descent iterations.  --trace-svi SHAPE only runs
 the two passes a few times (for a kernel trace from outside: the selection pass is batched_kernel<.., 4>, the plain pass
 batched_kernel<.., 0>) and writes nothing.
+
+Prediction leg (--predict, on its own; writes <out>/bench_batched_predict.json): per prediction shape, one
+BatchedHipEngine.predict (standardisation in the kernel) against the B solo HipEngine.predict calls it replaces, each
+uploading its own standardised rows (the uploads count: that is the path replaced), alternated in the same run, outputs
+compared bit for bit.  Prediction shapes: 1. B = 24, shared N = 2500, dx = dy = 1, K = 100 (the reference job's evaluation,
+diagonal variance); 2. B = 64, N_b = 1e4 own rows, dx = dy = 1, K = 4 (full covariance); 3. B = 8, N_b = 2.5e5 own rows,
+dx = 8, dy = 4, K = 64, diagonal variance.  --trace-predict SHAPE only runs the batched call and the solo calls a few times
+(for a kernel trace from outside: predict_batched_kernel against predict_reg_kernel) and writes nothing.
 
 Shapes: 1. B = 24, N_b = 1600, Dz = 2, K = 100 (the reference's parallel ILR example); 2. B = 64, N_b = 1e4, Dz = 2, K = 4
 (restarts of the toy GMM); 3. B = 8, N_b = 2.5e5, Dz = 12, K = 64 (C4 per model)."""
@@ -438,6 +446,69 @@ def svi_driver_iteration(reps, batch=256):
             "speedup": solo / total, "reps": reps}
 
 
+# (B, N, dx, dy, K, shared rows, variance)
+PREDICT_SHAPES = {1: (24, 2500, 1, 1, 100, True, 'diagonal'), 2: (64, 10000, 1, 1, 4, False, 'full'),
+                  3: (8, 250000, 8, 4, 64, False, 'diagonal')}
+
+
+def predict_inputs(sid):
+    B, N, dx, dy, K, shared, variance = PREDICT_SHAPES[sid]
+    rng = np.random.default_rng(200 + sid)
+    dc = dx + 1
+
+    def spd(d, lead):
+        A = rng.standard_normal(lead + (d, d))
+        return A @ np.swapaxes(A, -1, -2) / d + 0.3 * np.eye(d)
+    x = rng.standard_normal((N, dx)) * 3. + 1. if shared else [rng.standard_normal((N, dx)) * 3. + 1. for _ in range(B)]
+    par = dict(c=rng.standard_normal((B, K)), b=rng.standard_normal((B, K, dx)), W=spd(dx, (B, K)),
+               M=rng.standard_normal((B, K, dy, dc)), Q=0.05 * spd(dc, (B, K)), Cc=spd(dy, (B, K)))
+    tf = np.stack([np.stack([rng.standard_normal(dx), 0.5 + rng.random(dx)]) for _ in range(B)])
+    return x, par, tf, shared, variance
+
+
+def predict_calls(sid):
+    """(batched call, solo calls, results dict, close)."""
+    B = PREDICT_SHAPES[sid][0]
+    x, par, tf, shared, variance = predict_inputs(sid)
+    beng, seng = BatchedHipEngine(0), HipEngine(0)
+    out = {}
+
+    def batched():
+        out["b"] = beng.predict(x, par["c"], par["b"], par["W"], par["M"], par["Q"], par["Cc"], variance=variance, x_transform=tf)
+
+    def solo():
+        res = []
+        for i in range(B):
+            xi = x if shared else x[i]
+            seng.upload(np.ascontiguousarray((xi - tf[i, 0]) / tf[i, 1]))
+            res.append(seng.predict(*(par[k][i] for k in ("c", "b", "W", "M", "Q", "Cc")), variance=variance))
+        out["s"] = res
+
+    def close():
+        beng.close()
+        seng.close()
+    return batched, solo, out, close
+
+
+def run_predict_shape(sid, reps):
+    B, N, dx, dy, K, shared, variance = PREDICT_SHAPES[sid]
+    batched, solo, out, close = predict_calls(sid)
+    tb, ts = timed_alternating(batched, solo, reps)
+    flat = lambda r: [r[0]] + (list(r[1]) if isinstance(r[1], tuple) else [r[1]])
+    same = all(np.array_equal(u, v) for rb, rs in zip(out["b"], out["s"]) for u, v in zip(flat(rb), flat(rs)))
+    close()
+    return {"predict_shape": sid, "B": B, "N_b": N, "dx": dx, "dy": dy, "K": K, "shared_rows": shared, "variance": variance,
+            "batched_ms": tb, "solo_sum_ms": ts, "speedup": ts / tb, "bit_identical": bool(same), "reps": reps}
+
+
+def trace_predict(sid, reps=5):
+    batched, solo, _, close = predict_calls(sid)
+    for _ in range(reps):
+        batched()
+        solo()
+    close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
@@ -450,7 +521,20 @@ def main():
     ap.add_argument("--trace-start", type=int, default=0, metavar="SHAPE", help="only run the batched start passes of SHAPE")
     ap.add_argument("--svi", action="store_true", help="only the SVI leg (selection pass, SVI iteration)")
     ap.add_argument("--trace-svi", type=int, default=0, metavar="SHAPE", help="only run the selection pass and the plain pass of SHAPE")
+    ap.add_argument("--predict", action="store_true", help="only the prediction leg (batched predict against B solo predicts)")
+    ap.add_argument("--trace-predict", type=int, default=0, metavar="SHAPE", help="only run the batched and the solo predictions of SHAPE")
     args = ap.parse_args()
+    if args.trace_predict:
+        trace_predict(args.trace_predict)
+        return
+    if args.predict:
+        os.makedirs(args.out, exist_ok=True)
+        res = [run_predict_shape(int(s), args.reps) for s in args.shapes.split(",")]
+        for r in res:
+            print(json.dumps(r))
+        with open(os.path.join(args.out, "bench_batched_predict.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if args.trace_svi:
         trace_svi(args.trace_svi)
         return

@@ -399,6 +399,48 @@ int mimo_weighted_stats_batched(mimo_ctx* ctx, const double* resp, int K, int fl
  * mimo_estep_batched. */
 int mimo_random_resp_stats_batched(mimo_ctx* ctx, int K, const uint64_t* seeds, int flags, double* S);
 
+/* ---- nested batch: M inner mixtures over ONE data set -----------------------------------
+ * A batch whose B problems all read the same rows: Z (N, Dz) is copied once, every problem owns all N rows.
+ * Replaces: the M binds of the same `obs` by the inner mixtures of a mixture of mixtures
+ *   (mimo/mixtures/hgmm.py:355-414: `for m in range(self.cluster_size): self.components[m].meanfield_...(obs, ...)`).
+ * The batch behaves as mimo_upload_batched of B copies of Z with row_off[b] = b N: every batched pass returns, per problem,
+ * exactly those bits, and every per-problem buffer keeps that layout — mimo_get_lse, mimo_get_labels and mimo_get_resp
+ * return B N entries (K B N for the table), uniforms, labels, weights and tables are passed with B N rows, the local row
+ * indices of mimo_estep_batched_rows lie in [0, N).
+ * N >= 1, 1 <= B <= 65535 (MIMO_E_INVALID otherwise), Dz <= 16 (MIMO_E_UNSUPPORTED otherwise), every element finite
+ * (MIMO_E_INVALID otherwise).  The context is a shared batch until the next mimo_upload, mimo_upload_batched or mimo_attach. */
+int mimo_upload_batched_shared(mimo_ctx* ctx, const double* Z_host, int64_t N, int B, int Dz);
+
+/* mimo_estep_batched with per-row weights: per problem b what mimo_estep_weighted returns for its rows — the statistics are
+ * those of r_kn w_n, the scalars and a kept lse those of the unweighted r_kn.
+ * Replaces: per inner mixture, the weighted pass of its inner descent (mimo/mixtures/hgmm.py:199-207: resp * weights feeds the
+ *   update, the unweighted resp the bound) with weights = the outer responsibilities resp[m, :] (hgmm.py:355-414).
+ * row_weights: row_off[B] doubles on the host, problem b's at row_off[b] (a shared batch: B N, problem b's at b N), each
+ *   finite and >= 0 (MIMO_E_INVALID otherwise).  They are copied to a device buffer of the context and stay there.
+ *   NULL: the resident weights — those of the previous call or of mimo_outer_resp_batched; MIMO_E_STATE if there are none
+ *   (an upload drops them).
+ * c, b, W, S, scalars, flags, coverage and the determinism rule: those of mimo_estep_batched, on ragged and shared batches.
+ * With every weight exactly 1.0 the call returns the bits of mimo_estep_batched. */
+int mimo_estep_batched_weighted(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K,
+                                const double* row_weights, int flags, double* S, double* scalars);
+
+/* The outer step of a mixture of mixtures on the device, over a shared batch whose last softmax pass kept its lse
+ * (MIMO_F_KEEP_LSE); anything else is MIMO_E_STATE.
+ * Replaces: expected_log_complete_likelihood + expected_responsibilities of the outer mixture (mimo/mixtures/hgmm.py:355-414:
+ *   the stacked inner log-normalisers + E[log pi_m], softmax over m) and the copy of resp[m, :] back into the inner passes
+ *   (hgmm.py:199-207) — the (B, N) table never leaves the device.
+ * Per row n: t_b = lse[b N + n] + log_gating[b], m = max_b t_b, e_b = exp(t_b - m), s = sum_b e_b;
+ *   w[b N + n] = e_b / s goes to the resident weights of mimo_estep_batched_weighted (row_weights = NULL reads them);
+ *   out[b] = sum_n w[b N + n] (the outer gating counts), out[B] = sum_n (m + log s) (the outer log-likelihood).
+ * log_gating: B doubles on the host; -inf is allowed (that problem's weights are exactly 0); NaN, +inf or every entry -inf is
+ *   MIMO_E_INVALID.  flags: 0.  out: B + 1 doubles on the host.
+ * The sums run over a row split that depends on N alone, in a fixed order: two calls return identical bits. */
+int mimo_outer_resp_batched(mimo_ctx* ctx, const double* log_gating, int flags, double* out);
+
+/* The resident row weights (mimo_estep_batched_weighted, mimo_outer_resp_batched; hgmm.py:199-207, 355-414): row_off[B] doubles
+ * to the host, problem b's at row_off[b].  MIMO_E_STATE if none are valid. */
+int mimo_get_row_weights_batched(mimo_ctx* ctx, double* out);
+
 /* Posterior-predictive mixture moments of B ILR models in one launch: per problem b what mimo_predict_flags returns on a
  * context whose resident rows are (X_b - shift_b) / scale_b, bit for bit, and the same bits whatever else is in the batch.
  * Replaces: the loop `for ilr in ilrs: ilr.meanfield_prediction(input)` of examples/ilr/evaluate_sinc_parallel.py:196-201 over

@@ -41,6 +41,10 @@ SIGNATURES = {
     "mimo_label_stats_batched": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     "mimo_weighted_stats_batched": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     "mimo_random_resp_stats_batched": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
+    "mimo_upload_batched_shared": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int]),
+    "mimo_estep_batched_weighted": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "mimo_outer_resp_batched": (C.c_int, [_vp, _vp, C.c_int, _vp]),
+    "mimo_get_row_weights_batched": (C.c_int, [_vp, _vp]),
     "mimo_estep_weighted": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "mimo_wait": (C.c_int, [_vp, _vp, _vp]),
     "mimo_gibbs_labels": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_uint64, C.c_uint64, _vp,

@@ -7,6 +7,10 @@ B problems share Dz and K; each has its own rows and its own (c, b, W).  Where t
 joblib (examples/ilr/evaluate_sinc_parallel.py: one ILR fit per train split) or random restarts, every pass of every
 fit is a chain of small launches; here one launch covers all of them.  A problem's results do not depend on what else
 is in the batch, bit for bit.  No CPU fallback: without the library or a GPU the constructor raises.
+
+A nested batch (upload_shared) holds ONE data set that B problems read — the M inner mixtures of a mixture of mixtures
+(mixtures/hgmm.py): estep(row_weights=...) is their weighted inner pass, outer_responsibilities the outer step, whose
+(B, N) weights stay on the device for the next inner passes (mixtures/batched.py: meanfield_coordinate_descent_nested).
 """
 import ctypes as C
 
@@ -28,6 +32,7 @@ class BatchedHipEngine:
         self.device = int(device)
         self.B, self.D = 0, 0
         self.row_off = np.zeros(1, dtype=np.int64)
+        self.shared = False           # upload_shared: the B problems read one block of rows
 
     def _check(self, rc):
         if rc != 0:
@@ -64,6 +69,47 @@ class BatchedHipEngine:
         Z = np.ascontiguousarray(np.concatenate(arrays, axis=0)) if row_off[-1] > 0 else np.zeros((1, D))
         self._check(self._lib.mimo_upload_batched(self._ctx, _ptr(Z), _ptr(row_off), len(arrays), int(D)))
         self.B, self.D, self.row_off = len(arrays), int(D), row_off
+        self.shared = False
+
+    def upload_shared(self, Z, B):
+        """ONE (N, Dz) host array that all B problems read (mimo_upload_batched_shared): copied once; the batch behaves as
+        upload([Z] * B), bit for bit in every pass, with row_off = arange(B + 1) * N."""
+        Z = _f64(Z)
+        B = int(B)
+        if Z.ndim != 2:
+            raise ValueError("the shared data must be (N, Dz)")
+        if Z.shape[0] < 1:
+            raise ValueError("a shared batch needs at least one row")
+        if B < 1:
+            raise ValueError(f"a shared batch needs at least one problem, got B = {B}")
+        N, D = Z.shape
+        self._check(self._lib.mimo_upload_batched_shared(self._ctx, _ptr(Z), int(N), B, int(D)))
+        self.B, self.D, self.row_off = B, int(D), np.arange(B + 1, dtype=np.int64) * int(N)
+        self.shared = True
+
+    def _row_weights(self, row_weights):
+        """A list of B arrays (N_b,), or one (B, N) array on a shared batch -> the concatenated weights; raises ValueError
+        before any library call."""
+        if isinstance(row_weights, np.ndarray) and row_weights.ndim == 2:
+            if not getattr(self, 'shared', False):
+                raise ValueError("one (B, N) weight array needs a shared batch (upload_shared); pass a list of B arrays")
+            w = _f64(row_weights)
+            if w.shape != (self.B, int(self.row_off[1])):
+                raise ValueError(f"row_weights must be (B, N) = ({self.B}, {int(self.row_off[1])}), got shape {w.shape}")
+            flat = w.reshape(-1)
+        else:
+            parts = list(row_weights)
+            if len(parts) != self.B:
+                raise ValueError(f"row weights for {len(parts)} problems, {self.B} uploaded")
+            parts = [_f64(p).reshape(-1) for p in parts]
+            for i, p in enumerate(parts):
+                if p.shape[0] != self.row_off[i + 1] - self.row_off[i]:
+                    raise ValueError(f"row_weights of problem {i} must hold one weight per datum "
+                                     f"({int(self.row_off[i + 1] - self.row_off[i])}), got {p.shape[0]}")
+            flat = np.concatenate(parts) if self.row_off[-1] > 0 else np.zeros(1)
+        if not np.all(np.isfinite(flat)) or np.any(flat < 0.):
+            raise ValueError("row_weights must be finite and >= 0")
+        return np.ascontiguousarray(flat)
 
     def _params(self, c, b, W):
         c, b, W = _f64(c), _f64(b), _f64(W)
@@ -95,14 +141,27 @@ class BatchedHipEngine:
         flat = np.concatenate(rows).astype(np.int64, copy=False) if sel_off[-1] > 0 else np.zeros(1, dtype=np.int64)
         return np.ascontiguousarray(flat), sel_off
 
-    def estep(self, c, b, W, stats=True, keep_lse=False, entropy_split=False, rows=None):
+    def estep(self, c, b, W, stats=True, keep_lse=False, entropy_split=False, rows=None, row_weights=None):
         """One pass over all problems.  c (B, K), b (B, K, Dz), W (B, K, Dz, Dz).  Returns (list of B SuffStats, or None
         without stats; scalars (B, 3)) — per problem what HipEngine.estep returns; scalars[:, 1:] are NaN unless
         entropy_split or keep_lse is set.
         rows: a list of B integer arrays, problem b's a selection of its local rows in [0, N_b) — any order, duplicates
         allowed, empty allowed.  The pass then runs over the selected rows only, gathered on the device from the resident
         batch (mimo_estep_batched_rows): per problem, bit for bit, what a plain pass returns on a batch that holds
-        Z_b[rows_b].  No keep_lse with rows."""
+        Z_b[rows_b].  No keep_lse with rows.
+        row_weights: a list of B arrays (N_b,), one (B, N) array on a shared batch, or 'resident' (the weights of the last
+        weighted pass or of outer_responsibilities, as they lie on the device): the statistics are those of r_kn * w_n, the
+        scalars and a kept lse stay unweighted (mimo_estep_batched_weighted) — per problem what HipEngine.estep(row_weights=)
+        returns.  Not together with rows."""
+        w = None
+        if row_weights is not None:
+            if rows is not None:
+                raise ValueError("row_weights together with rows: the minibatch pass takes no weights")
+            if isinstance(row_weights, str):
+                if row_weights != 'resident':
+                    raise ValueError(f"row_weights must be arrays or 'resident', got {row_weights!r}")
+            else:
+                w = self._row_weights(row_weights)
         if rows is not None:
             if keep_lse:
                 raise ValueError("keep_lse with rows: the normalisers of a selection have no place in the resident lse")
@@ -116,6 +175,10 @@ class BatchedHipEngine:
         if rows is not None:
             self._check(self._lib.mimo_estep_batched_rows(self._ctx, _ptr(c), _ptr(b), _ptr(W), K, _ptr(sel), _ptr(sel_off),
                                                           flags, _ptr(S) if stats else None, _ptr(sc)))
+        elif row_weights is not None:
+            self._check(self._lib.mimo_estep_batched_weighted(self._ctx, _ptr(c), _ptr(b), _ptr(W), K,
+                                                              _ptr(w) if w is not None else None, flags,
+                                                              _ptr(S) if stats else None, _ptr(sc)))
         else:
             self._check(self._lib.mimo_estep_batched(self._ctx, _ptr(c), _ptr(b), _ptr(W), K, flags,
                                                      _ptr(S) if stats else None, _ptr(sc)))
@@ -334,6 +397,26 @@ class BatchedHipEngine:
             out.append((mu[o * dy:(o + n) * dy].reshape(n, dy).copy(), sec, nlpd[o:o + n].copy() if Y is not None else None))
             o += n
         return out
+
+    def outer_responsibilities(self, log_gating):
+        """The outer step of a mixture of mixtures on a shared batch whose last pass kept its lse (mimo_outer_resp_batched):
+        w[b, n] = softmax_b(lse[b, n] + log_gating[b]) stays on the device as the resident row weights
+        (estep(row_weights='resident'), get_row_weights()).  Returns (counts (B,) = sum_n w[b, n], the outer
+        log-likelihood sum_n logsumexp_b(lse[b, n] + log_gating[b]))."""
+        lg = _f64(log_gating).reshape(-1)
+        if lg.shape[0] != self.B:
+            raise ValueError(f"log_gating has {lg.shape[0]} entries, {self.B} problems uploaded")
+        if np.any(np.isnan(lg)) or np.any(lg == np.inf) or not np.any(np.isfinite(lg)):
+            raise ValueError("log_gating must hold no NaN and no +inf, and one finite entry at least")
+        out = np.empty(self.B + 1)
+        self._check(self._lib.mimo_outer_resp_batched(self._ctx, _ptr(lg), 0, _ptr(out)))
+        return out[:self.B].copy(), float(out[self.B])
+
+    def get_row_weights(self):
+        """The resident row weights (the last weighted pass's, or those of outer_responsibilities): a list of B arrays (N_b,)."""
+        out = np.empty(max(int(self.row_off[-1]), 1))
+        self._check(self._lib.mimo_get_row_weights_batched(self._ctx, _ptr(out)))
+        return self._split(out)
 
     def get_resp(self, K=None):
         """The table of the last random_resp_stats, resident on the device: a list of B arrays (K, N_b)."""

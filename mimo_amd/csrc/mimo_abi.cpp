@@ -147,6 +147,11 @@ struct mimo_ctx {
   Buf<int64_t> batch_row_off_d;                            // [B + 1]
   Buf<BatchedWork> batch_work_d;                           // [G]
   Buf<int32_t> batch_wg_off_d;                             // [B + 1]: problem b owns the workgroups [wg_off[b], wg_off[b + 1])
+  // shared batch (mimo_upload_batched_shared): Z holds ONE block of N rows that all B problems read; every per-problem buffer
+  // (lse, labels, weights, uniforms, tables) still has row_off[B] = B N rows — table_rows() — while ctx->N counts the data rows
+  bool batch_shared = false;
+  Buf<double> batch_w;                                     // [row_off[B]] per-row weights of mimo_estep_batched_weighted / mimo_outer_resp_batched
+  bool batch_w_valid = false;
 
   void* comm = nullptr;         // RCCL communicator (mimo_comm_init): every pass then returns statistics summed over the ranks
   int comm_world = 1;
@@ -268,6 +273,12 @@ static int prepare_features(mimo_ctx* ctx, int D) {
     ctx->feat_full_D = D;
   }
   return MIMO_OK;
+}
+
+// Rows of the per-row buffers (lse, labels, weights, uniforms, the columns of a table): the data rows, except on a shared batch,
+// whose B problems each own all N of them (row_off[B] = B N)
+static int64_t table_rows(const mimo_ctx* ctx) {
+  return ctx->batched ? ctx->batch_rows[(size_t)ctx->batch_B] : ctx->N;
 }
 
 // The single-problem entry points on a context that holds a batch (mimo_upload_batched)
@@ -816,8 +827,10 @@ static int set_data(mimo_ctx* ctx, int64_t N, int Dz) {
   ctx->N = N; ctx->D = Dz;
   ctx->order_K = 0;
   ctx->batched = false;
+  ctx->batch_shared = false;
   ctx->resp_valid = ctx->logp_valid = ctx->lse_valid = ctx->labels_valid = false;
   ctx->weights_resident = false;
+  ctx->batch_w_valid = false;
   return prepare_features(ctx, Dz);
 }
 
@@ -1263,7 +1276,7 @@ enum class Kept { Resp, Logp, Lse, Labels };
 static int get_kept(mimo_ctx* ctx, void* out, Kept which, const char* what) {
   return guarded(ctx, [&]() -> int {
   if (!ctx) return fail(nullptr, MIMO_E_INVALID, "null context");
-  const size_t n = (size_t)ctx->N;
+  const size_t n = (size_t)table_rows(ctx);
   switch (which) {
     case Kept::Resp: return copy_out(ctx, out, ctx->resp, ctx->resp_K * n * sizeof(double), ctx->resp_valid, what);
     case Kept::Logp: return copy_out(ctx, out, ctx->logp, ctx->logp_K * n * sizeof(double), ctx->logp_valid, what);
@@ -1596,23 +1609,16 @@ int mimo_plan_shape(int Dz, int K, int structure, int64_t N, int gibbs, int64_t*
 // ------------------------------------------------------------------------------------------
 // Batched softmax pass (mimo_batched.hip)
 // ------------------------------------------------------------------------------------------
-int mimo_upload_batched(mimo_ctx* ctx, const double* Z_host, const int64_t* row_off, int B, int Dz) {
-  return guarded(ctx, [&]() -> int {
-  int rc = bind(ctx); if (rc) return rc;
-  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
-  if (B < 1 || B > 65535 || !row_off) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: B = %d outside [1, 65535] or row_off is NULL", B);
-  if (Dz < 1 || Dz > kBatchedMaxD)
-    return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_upload_batched: Dz = %d outside [1, %d] (batched pass)", Dz, kBatchedMaxD);
-  if (row_off[0] != 0) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: row_off[0] = %lld, must be 0", (long long)row_off[0]);
-  for (int b = 0; b < B; ++b)
-    if (row_off[b + 1] < row_off[b])
-      return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: row_off decreases at problem %d", b);
-  const int64_t N = row_off[B];
-  if (!Z_host && N > 0) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: Z is NULL");
+// The upload of a batch: `N` data rows, the concatenated rows of B problems (row_off[B] = N) or, `shared`, ONE block that all B
+// problems read (row_off[b] = b N).  Both forms build the same tables from row_off.
+static int upload_batch(mimo_ctx* ctx, const double* Z_host, int64_t N, const int64_t* row_off, int B, int Dz, bool shared,
+                        const char* me) {
+  int rc;
+  if (!Z_host && N > 0) return fail(ctx, MIMO_E_INVALID, "%s: Z is NULL", me);
   // batched mode has no NaN-row semantics: every element must be finite
   for (int64_t i = 0; i < N * Dz; ++i)
     if (!std::isfinite(Z_host[i]))
-      return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: row %lld holds a NaN or an infinity", (long long)(i / Dz));
+      return fail(ctx, MIMO_E_INVALID, "%s: row %lld holds a NaN or an infinity", me, (long long)(i / Dz));
   // work table: problem b's tiles in runs of batched_tiles_per_wg(N_b), a function of N_b alone
   std::vector<BatchedWork> work;
   std::vector<int32_t> wg_off((size_t)B + 1, 0);
@@ -1622,7 +1628,7 @@ int mimo_upload_batched(mimo_ctx* ctx, const double* Z_host, const int64_t* row_
     const int tpw = batched_tiles_per_wg(nb);
     for (int64_t t = 0; t < tiles; t += tpw)
       work.push_back(BatchedWork{b, (int32_t)t, (int32_t)std::min<int64_t>(tpw, tiles - t), 0});
-    if (work.size() > (size_t)INT32_MAX) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: too many rows");
+    if (work.size() > (size_t)INT32_MAX) return fail(ctx, MIMO_E_INVALID, "%s: too many rows", me);
     wg_off[(size_t)b + 1] = (int32_t)work.size();
   }
   if ((rc = set_data(ctx, N, Dz))) return rc;
@@ -1642,7 +1648,38 @@ int mimo_upload_batched(mimo_ctx* ctx, const double* Z_host, const int64_t* row_
   ctx->batch_B = B;
   ctx->batch_G = (int)work.size();
   ctx->batched = true;
+  ctx->batch_shared = shared;
   return MIMO_OK;
+}
+
+int mimo_upload_batched(mimo_ctx* ctx, const double* Z_host, const int64_t* row_off, int B, int Dz) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
+  if (B < 1 || B > 65535 || !row_off) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: B = %d outside [1, 65535] or row_off is NULL", B);
+  if (Dz < 1 || Dz > kBatchedMaxD)
+    return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_upload_batched: Dz = %d outside [1, %d] (batched pass)", Dz, kBatchedMaxD);
+  if (row_off[0] != 0) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: row_off[0] = %lld, must be 0", (long long)row_off[0]);
+  for (int b = 0; b < B; ++b)
+    if (row_off[b + 1] < row_off[b])
+      return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: row_off decreases at problem %d", b);
+  return upload_batch(ctx, Z_host, row_off[B], row_off, B, Dz, false, "mimo_upload_batched");
+  });
+}
+
+int mimo_upload_batched_shared(mimo_ctx* ctx, const double* Z_host, int64_t N, int B, int Dz) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
+  if (B < 1 || B > 65535) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched_shared: B = %d outside [1, 65535]", B);
+  if (N < 1) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched_shared: N = %lld, must be >= 1", (long long)N);
+  if (Dz < 1 || Dz > kBatchedMaxD)
+    return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_upload_batched_shared: Dz = %d outside [1, %d] (batched pass)", Dz, kBatchedMaxD);
+  if (N > std::numeric_limits<int64_t>::max() / ((int64_t)B * kBatchedMaxK))      // B N K: the longest per-problem buffer
+    return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched_shared: too many rows");
+  std::vector<int64_t> row_off((size_t)B + 1);
+  for (int b = 0; b <= B; ++b) row_off[(size_t)b] = (int64_t)b * N;
+  return upload_batch(ctx, Z_host, N, row_off.data(), B, Dz, true, "mimo_upload_batched_shared");
   });
 }
 
@@ -1678,36 +1715,38 @@ static BatchedArgs batched_args(mimo_ctx* ctx, int K) {
   a.D = ctx->D; a.K = K; a.K16 = (K + 15) / 16; a.F16 = ctx->F16;
   a.ZS = (ctx->D + 2) | 1;
   a.do_stats = 1;
+  a.shared = ctx->batch_shared ? 1 : 0;
   a.u = nullptr; a.seeds = nullptr; a.labels = nullptr; a.sweep = 0;
   a.resp = nullptr;
   a.sel = nullptr; a.sel_off = nullptr;
   return a;
 }
 
-int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, int flags, double* S,
-                       double* scalars) {
-  return guarded(ctx, [&]() -> int {
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, "mimo_estep_batched"))) return rc;
+// The softmax pass of a batch, plain (weights = null: launch_batched) or with the device weights `weights` on the statistics
+// (launch_batched_weighted); the caller has run batched_ready and its own argument checks.
+static int batched_softmax_pass(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, const double* weights,
+                                int flags, double* S, double* scalars, const char* me) {
+  int rc;
   if (flags & ~(MIMO_F_NO_STATS | MIMO_F_ENTROPY_SPLIT | MIMO_F_KEEP_LSE))
-    return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: flags 0x%x: only MIMO_F_NO_STATS, MIMO_F_ENTROPY_SPLIT, MIMO_F_KEEP_LSE", flags);
+    return fail(ctx, MIMO_E_INVALID, "%s: flags 0x%x: only MIMO_F_NO_STATS, MIMO_F_ENTROPY_SPLIT, MIMO_F_KEEP_LSE", me, flags);
   const bool no_stats = (flags & MIMO_F_NO_STATS) != 0;
   if (!c || !b || !W || !scalars || (!no_stats && !S))
-    return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched: c, b, W, scalars (and S without MIMO_F_NO_STATS) must be non-NULL");
+    return fail(ctx, MIMO_E_INVALID, "%s: c, b, W, scalars (and S without MIMO_F_NO_STATS) must be non-NULL", me);
   const int D = ctx->D, B = ctx->batch_B;
   const int F = ctx->F, F16 = ctx->F16, K16 = (K + 15) / 16;
-  if ((rc = batched_theta(ctx, c, b, W, K, nullptr, 0, "mimo_estep_batched"))) return rc;
+  if ((rc = batched_theta(ctx, c, b, W, K, nullptr, 0, me))) return rc;
 
   const int G = ctx->batch_G;
   if ((rc = ctx->partials.ensure(ctx, partial_stride(K16, F16) * (size_t)std::max(G, 1)))) return rc;
   const bool keep_lse = (flags & MIMO_F_KEEP_LSE) != 0;
-  if (keep_lse && (rc = ctx->lse.ensure(ctx, (size_t)ctx->N))) return rc;
+  if (keep_lse && (rc = ctx->lse.ensure(ctx, (size_t)table_rows(ctx)))) return rc;
   ctx->lse_valid = keep_lse;
   ctx->resp_valid = ctx->logp_valid = ctx->labels_valid = false;
   BatchedArgs a = batched_args(ctx, K);
   a.lse = keep_lse ? ctx->lse : nullptr;
   a.do_stats = no_stats ? 0 : 1;
-  HIP_TRY(ctx, launch_batched(a, G, ctx->stream));
+  a.u = weights;
+  HIP_TRY(ctx, weights ? launch_batched_weighted(a, G, ctx->stream) : launch_batched(a, G, ctx->stream));
   const size_t nstats = no_stats ? 0 : packed_len(K, D) * B, out = nstats + 3 * (size_t)B;
   if ((rc = ensure_block(ctx, out))) return rc;
   double* sc_d = ctx->S_d + nstats;
@@ -1715,6 +1754,86 @@ int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const do
   HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, D, F, F16, split,
                                      no_stats ? nullptr : ctx->S_d, sc_d, ctx->stream));
   return hand_out(ctx, out, no_stats ? nullptr : S, nstats, scalars, nstats, 3 * (size_t)B);
+}
+
+int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, int flags, double* S,
+                       double* scalars) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, "mimo_estep_batched"))) return rc;
+  return batched_softmax_pass(ctx, c, b, W, K, nullptr, flags, S, scalars, "mimo_estep_batched");
+  });
+}
+
+int mimo_estep_batched_weighted(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, const double* row_weights,
+                                int flags, double* S, double* scalars) {
+  return guarded(ctx, [&]() -> int {
+  const char* const me = "mimo_estep_batched_weighted";
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, me))) return rc;
+  const int64_t rows = table_rows(ctx);
+  if (!row_weights) {
+    if (!ctx->batch_w_valid || !ctx->batch_w)
+      return fail(ctx, MIMO_E_STATE, "%s: row_weights is NULL and no weights are resident (an earlier call or mimo_outer_resp_batched "
+                  "leaves them; an upload drops them)", me);
+  } else {
+    for (int64_t n = 0; n < rows; ++n)
+      if (!(std::isfinite(row_weights[n]) && row_weights[n] >= 0.0))
+        return fail(ctx, MIMO_E_INVALID, "%s: weight %lld is negative, NaN or an infinity", me, (long long)n);
+    ctx->batch_w_valid = false;
+    if ((rc = ctx->batch_w.ensure(ctx, (size_t)rows))) return rc;
+    if (rows > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->batch_w, row_weights, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // row_weights is pageable host memory
+    ctx->batch_w_valid = true;
+  }
+  return batched_softmax_pass(ctx, c, b, W, K, ctx->batch_w, flags, S, scalars, me);
+  });
+}
+
+int mimo_outer_resp_batched(mimo_ctx* ctx, const double* log_gating, int flags, double* out) {
+  return guarded(ctx, [&]() -> int {
+  const char* const me = "mimo_outer_resp_batched";
+  int rc = bind(ctx); if (rc) return rc;
+  if (!ctx->batched || !ctx->batch_shared)
+    return fail(ctx, MIMO_E_STATE, "%s: the context holds no shared batch (call mimo_upload_batched_shared)", me);
+  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
+  if (!ctx->lse_valid || !ctx->lse)
+    return fail(ctx, MIMO_E_STATE, "%s: no lse is resident (run mimo_estep_batched / _weighted with MIMO_F_KEEP_LSE first)", me);
+  if (flags != 0) return fail(ctx, MIMO_E_INVALID, "%s: flags 0x%x: none are defined", me, flags);
+  if (!log_gating || !out) return fail(ctx, MIMO_E_INVALID, "%s: log_gating and out must be non-NULL", me);
+  const int B = ctx->batch_B;
+  const int64_t N = ctx->N;
+  bool any = false;
+  for (int p = 0; p < B; ++p) {
+    if (std::isnan(log_gating[p]) || log_gating[p] == std::numeric_limits<double>::infinity())
+      return fail(ctx, MIMO_E_INVALID, "%s: log_gating[%d] is NaN or +inf", me, p);
+    any = any || std::isfinite(log_gating[p]);
+  }
+  if (!any) return fail(ctx, MIMO_E_INVALID, "%s: every entry of log_gating is -inf", me);
+  // log_gating goes the way the seeds of the random start go: through the operand image's pinned buffer
+  if ((rc = ctx->theta_d.ensure(ctx, (size_t)B))) return rc;
+  if ((rc = ctx->theta_h.ensure(ctx, (size_t)B))) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));    // the staging buffer may still be in flight from the previous call on this stream
+  memcpy(ctx->theta_h, log_gating, (size_t)B * sizeof(double));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, ctx->theta_h, (size_t)B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  ctx->batch_w_valid = false;
+  if ((rc = ctx->batch_w.ensure(ctx, (size_t)B * (size_t)N))) return rc;
+  if ((rc = ctx->partials.ensure(ctx, outer_resp_partials(B, N)))) return rc;
+  if ((rc = ensure_block(ctx, (size_t)B + 1))) return rc;
+  HIP_TRY(ctx, launch_outer_resp(ctx->lse, ctx->theta_d, B, N, ctx->batch_w, ctx->partials, ctx->S_d, ctx->stream));
+  ctx->batch_w_valid = true;
+  return hand_out(ctx, (size_t)B + 1, out, (size_t)B + 1, nullptr, 0, 0);
+  });
+}
+
+int mimo_get_row_weights_batched(mimo_ctx* ctx, double* out) {
+  return guarded(ctx, [&]() -> int {
+  if (!ctx) return fail(nullptr, MIMO_E_INVALID, "null context");
+  if (!ctx->batched || !ctx->batch_w_valid)
+    return fail(ctx, MIMO_E_STATE, "mimo_get_row_weights_batched: no row weights are resident");
+  const size_t rows = (size_t)table_rows(ctx);
+  if (rows == 0) return MIMO_OK;
+  return copy_out(ctx, out, ctx->batch_w, rows * sizeof(double), true, "mimo_get_row_weights_batched");
   });
 }
 
@@ -1817,7 +1936,7 @@ int mimo_gibbs_labels_batched(mimo_ctx* ctx, const double* c, const double* b, c
     return fail(ctx, MIMO_E_INVALID, "mimo_gibbs_labels_batched: u and seeds are both NULL (give the uniforms or one Philox "
                 "seed per problem)");
   const int B = ctx->batch_B, G = ctx->batch_G;
-  const int64_t N = ctx->N;
+  const int64_t N = table_rows(ctx);
   // the seeds travel behind the operand image, in its transfer
   if ((rc = batched_theta(ctx, c, b, W, K, u ? nullptr : seeds, u ? 0 : (size_t)B, "mimo_gibbs_labels_batched"))) return rc;
   const size_t count = (size_t)((K + 15) / 16) * (ctx->F16 / 4) * 64 * B;
@@ -1852,7 +1971,7 @@ int mimo_label_stats_batched(mimo_ctx* ctx, const int32_t* labels, int K, int fl
   if ((rc = batched_ready(ctx, K, "mimo_label_stats_batched"))) return rc;
   if (flags != 0) return fail(ctx, MIMO_E_INVALID, "mimo_label_stats_batched: flags 0x%x: none are defined", flags);
   if (!S) return fail(ctx, MIMO_E_INVALID, "mimo_label_stats_batched: S is NULL");
-  const int64_t N = ctx->N;
+  const int64_t N = table_rows(ctx);
   const int G = ctx->batch_G;
   // the kernel indexes its accumulators by label: the caller's labels are checked on the host, before anything is staged
   for (int64_t n = 0; labels && n < N; ++n)
@@ -1894,7 +2013,7 @@ int mimo_weighted_stats_batched(mimo_ctx* ctx, const double* resp, int K, int fl
   if (!S) return fail(ctx, MIMO_E_INVALID, "mimo_weighted_stats_batched: S is NULL");
   const double* table = nullptr;
   bool copied = false;        // (flags is 0: the table is the resident one or host memory; its values are taken as they are)
-  if ((rc = stage_input<double>(ctx, resp, (size_t)K * (size_t)ctx->N, flags, ctx->win,
+  if ((rc = stage_input<double>(ctx, resp, (size_t)K * (size_t)table_rows(ctx), flags, ctx->win,
                                 {ctx->resp, ctx->resp_valid && ctx->resp_K == K && ctx->resp,
                                  "mimo_weighted_stats_batched: resp is NULL and no (K=%d, N_total) table is resident"},
                                 K, &table, &copied))) return rc;
@@ -1910,7 +2029,7 @@ int mimo_random_resp_stats_batched(mimo_ctx* ctx, int K, const uint64_t* seeds, 
   if (flags != 0) return fail(ctx, MIMO_E_INVALID, "mimo_random_resp_stats_batched: flags 0x%x: none are defined", flags);
   if (!S || !seeds) return fail(ctx, MIMO_E_INVALID, "mimo_random_resp_stats_batched: S and seeds must be non-NULL");
   const int B = ctx->batch_B;
-  const int64_t N = ctx->N;
+  const int64_t N = table_rows(ctx);
   ctx->resp_valid = false;
   if ((rc = ctx->resp.ensure(ctx, (size_t)K * (size_t)N))) return rc;
   // the seeds go the way the label pass sends them: through the operand image's pinned buffer (there is no image here)

@@ -35,8 +35,12 @@ struct BatchedArgs {
   int D, K, K16, F16;
   int ZS;                     // LDS row stride (doubles) of the z~ tile
   int do_stats;
-  // label modes (launch_batched_labels) only; the softmax pass reads none of these
-  const double* u;            // (N_total,) uniforms of the draw, or null: Philox keyed by seeds[b], counter (local row, sweep)
+  int shared;                 // 1: Z holds ONE (N, D) block that every problem reads (mimo_upload_batched_shared); row_off[b] = b N still
+                              // places the problem's rows in every per-problem buffer (lse, labels, u, resp, sel)
+  // label modes (launch_batched_labels) and the weighted softmax mode (launch_batched_weighted) only; the softmax pass reads none
+  // of these
+  const double* u;            // (N_total,) uniforms of the draw, or null: Philox keyed by seeds[b], counter (local row, sweep);
+                              // weighted softmax mode: the per-row weights of the statistics
   const uint64_t* seeds;      // [B] (Philox draw)
   int32_t* labels;            // (N_total,): the labels drawn (kBatchedDraw) or given (kBatchedGiven)
   uint64_t sweep;
@@ -51,7 +55,9 @@ struct BatchedArgs {
 // drawn), or the statistics of labels given on the device (no L product, no draw).
 // Table mode: the statistics of a weight table given on the device (no L product, no normalise phase; weights as they are).
 // Row-selection mode: the softmax pass over rows gathered through an index list (the minibatch pass of batched SVI).
-enum BatchedLabelMode : int { kBatchedSoftmax = 0, kBatchedDraw = 1, kBatchedGiven = 2, kBatchedWeights = 3, kBatchedSoftmaxRows = 4 };
+// Weighted softmax mode: the softmax pass whose statistics are those of r_kn w_n, w = a.u (scalars and lse: those of r_kn).
+enum BatchedLabelMode : int { kBatchedSoftmax = 0, kBatchedDraw = 1, kBatchedGiven = 2, kBatchedWeights = 3, kBatchedSoftmaxRows = 4,
+                              kBatchedSoftmaxWeighted = 5 };
 
 // Tiles per workgroup for a problem of `nrows` rows: a function of the row count alone (the determinism rule: a problem's
 // result does not depend on what else is in the batch).
@@ -69,6 +75,18 @@ hipError_t launch_batched_weights(const BatchedArgs& a, int grid, hipStream_t st
 // those launch_batched writes for a batch whose problem b holds the rows Z_b[sel_b] in that order, bit for bit.  Every index
 // must lie in [0, N_b): the kernel does not check.
 hipError_t launch_batched_rows(const BatchedArgs& a, int grid, hipStream_t stream);
+// The weighted softmax mode (kBatchedSoftmaxWeighted) on the upload's work table: a.u holds one weight per row of the batch
+// (problem b's at row_off[b]); the statistics blocks are those of r_kn w_n, the scalars and a.lse those of launch_batched.
+// With every weight exactly 1.0 the partial blocks are those of launch_batched, bit for bit.
+hipError_t launch_batched_weighted(const BatchedArgs& a, int grid, hipStream_t stream);
+// The outer step of a mixture of mixtures over a SHARED batch: lse (B, N) holds the B problems' per-row log-normalisers.
+// Per row n: t_b = lse[b N + n] + log_gating[b], m = max_b t_b, e_b = exp(t_b - m) (exactly 0 where log_gating[b] = -inf),
+// s = sum_b e_b (b ascending); w[b N + n] = e_b / s.  out[b] = sum_n w[b N + n], out[B] = sum_n (m + log s): workgroup g sums
+// the rows [256 g, 256 g + 256) into partials[g (B + 1) ..] — a row split that depends on N alone — and a second kernel adds
+// the blocks in ascending order.  log_gating, lse, w, partials (outer_resp_partials(B, N) doubles), out: device pointers.
+size_t outer_resp_partials(int B, int64_t N);
+hipError_t launch_outer_resp(const double* lse, const double* log_gating, int B, int64_t N, double* w, double* partials, double* out,
+                             hipStream_t stream);
 // Random responsibilities of every problem in one launch, in the layout of BatchedArgs::resp: column n of problem b is
 // random_resp_column (mimo_device.h) with key seeds[b] and the LOCAL row n — the table launch_random_resp writes for the
 // problem's rows alone at row offset 0, bit for bit.  row_off and seeds are device pointers.

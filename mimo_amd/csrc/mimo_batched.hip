@@ -37,6 +37,16 @@
 // problem's "row count" is its selection's length, and a.work is a table built for those lengths.  Every phase after the tile
 // store is the softmax mode's, so the result is that of a plain pass over the gathered rows, bit for bit.  The indices are
 // read one tile ahead of the rows they address (three tiles ahead of their use), so the dependent load is never waited for.
+//
+// Weighted softmax mode (LM = kBatchedSoftmaxWeighted, the inner passes of a mixture of mixtures): the softmax mode with
+// ka.u = a.u + row_off[b], the problem's per-row weights: the generic normalise mode writes r_kn w_n back into Lt, so the
+// statistics are those of r_kn w_n while the scalars and lse stay those of r_kn (mimo/mixtures/hgmm.py:199-207).  A weight of
+// exactly 1.0 leaves every bit of the softmax mode's tile.
+//
+// Shared batch (a.shared, every mode): the B problems read ONE (N, D) block, Zb = a.Z for all of them; row_off[b] = b N still
+// places problem b in every per-problem buffer.  The work table is that of B problems of N rows, so each problem's partial
+// blocks are those of a ragged batch of B copies of the block, bit for bit.  outer_resp_kernel (below) is the outer step over
+// such a batch's lse.
 #include "mimo_batched.h"
 #include "mimo_tile.h"
 
@@ -81,8 +91,10 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
   uint8_t* fe = reinterpret_cast<uint8_t*>(etab + 64);   // [F16][2]
   int* labs = reinterpret_cast<int*>(red);        // [T] labels of the tile (label modes; unused by the softmax and the table mode)
   constexpr bool ROWS = LM == kBatchedSoftmaxRows;                           // the softmax mode over a row selection
-  constexpr bool HAS_L = LM == kBatchedSoftmax || ROWS || LM == kBatchedDraw;  // L product + normalise phase
-  constexpr bool A_FROM_LT = LM == kBatchedSoftmax || ROWS || LM == kBatchedWeights;   // phase 5 reads its A operand from Lt
+  constexpr bool WEIGHTED = LM == kBatchedSoftmaxWeighted;                   // the softmax mode with per-row weights on the statistics
+  constexpr bool SOFTMAX = LM == kBatchedSoftmax || ROWS || WEIGHTED;
+  constexpr bool HAS_L = SOFTMAX || LM == kBatchedDraw;                      // L product + normalise phase
+  constexpr bool A_FROM_LT = SOFTMAX || LM == kBatchedWeights;               // phase 5 reads its A operand from Lt
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -102,7 +114,7 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
     nrows = a.sel_off[prob + 1] - a.sel_off[prob];
   }
   const int64_t Nb = nrows;
-  const double* Zb = a.Z + rbeg * D;
+  const double* Zb = a.Z + (a.shared ? 0 : rbeg) * D;   // a shared batch: every problem reads the one block (scalar select)
   double* const out_lse = !ROWS && a.lse ? a.lse + rbeg : nullptr;    // (a selection's normalisers have no place in lse)
   const gptr_t th = (gptr_t)(a.theta + (size_t)prob * K16 * NSI * 64);
 
@@ -121,6 +133,7 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
     ka.seed = a.u ? 0 : a.seeds[prob];
     ka.sweep = a.sweep;
   }
+  if constexpr (WEIGHTED) ka.u = a.u + rbeg;   // the generic normalise mode scales the weights it writes back by u[local row]
 
   // Z tile staging: thread element e = tid + 256 i (T * D <= 512) of the tile; the next tile is read into registers
   // while the current one is processed
@@ -373,7 +386,7 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
       }
     }
   }
-  if constexpr (!(LM == kBatchedSoftmax || ROWS)) {
+  if constexpr (!SOFTMAX) {
     // no scalars in the label and table modes (and red, which holds the labels, is left alone)
     if (tid < 4) Pb[(size_t)Kpad * F16 + tid] = 0.0;
     return;
@@ -493,6 +506,100 @@ hipError_t launch_batched_rows(const BatchedArgs& a, int grid, hipStream_t strea
 hipError_t launch_batched_weights(const BatchedArgs& a, int grid, hipStream_t stream) {
   if (!a.resp) return hipErrorInvalidValue;
   return launch_mode<kBatchedWeights>(a, grid, stream);
+}
+
+hipError_t launch_batched_weighted(const BatchedArgs& a, int grid, hipStream_t stream) {
+  if (!a.u) return hipErrorInvalidValue;
+  return launch_mode<kBatchedSoftmaxWeighted>(a, grid, stream);
+}
+
+// ---- outer step of a mixture of mixtures over a shared batch -----------------------------------------------------------
+// One row per lane, 256 rows per workgroup (blockIdx.x = the row block: the split depends on N alone).  Three sweeps over b, each
+// reading lse[b N + n] coalesced across the wave: the maximum, the sum of exponentials, the weights.  log_gating is staged in LDS
+// in chunks of kOuterChunk entries, so B is bounded by nothing here; the third sweep also sums every weight over the workgroup's
+// rows: a wave butterfly per b, the four wave sums through LDS, added in wave order.  The exponentials of the second sweep are
+// recomputed in the third (same inputs, same bits), so nothing per b is held in registers.
+constexpr int kOuterChunk = 256;
+
+__global__ __launch_bounds__(kWG) void outer_resp_kernel(const double* __restrict__ lse, const double* __restrict__ log_gating, int B,
+                                                         int64_t N, double* __restrict__ w, double* __restrict__ partials) {
+  __shared__ double etab[64];
+  __shared__ double lg[kOuterChunk];
+  __shared__ double red[kOuterChunk][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t n = (int64_t)blockIdx.x * kWG + tid;
+  const bool valid = n < N;
+  const double* col = lse + (valid ? n : 0);      // rows past the end read row 0 and contribute nothing
+  double* Pb = partials + (size_t)blockIdx.x * ((size_t)B + 1);
+  if (tid < 64) etab[tid] = exp2((double)tid * (1.0 / 64.0));
+
+  // every sweep walks the chunks of log_gating through LDS: f(b, lse[b N + n] + log_gating[b], log_gating[b] == -inf)
+  auto sweep = [&](auto&& f, auto&& chunk_done) {
+    for (int c0 = 0; c0 < B; c0 += kOuterChunk) {
+      const int len = min(kOuterChunk, B - c0);
+      wg_sync();                                  // the previous chunk's readers are done (first chunk: etab is in LDS)
+      if (tid < len) lg[tid] = log_gating[c0 + tid];
+      wg_sync();
+      for (int i = 0; i < len; ++i) {
+        const double g = lg[i];
+        f(c0, i, col[(int64_t)(c0 + i) * N] + g, g == -INFINITY);
+      }
+      chunk_done(c0, len);
+    }
+  };
+  auto nothing = [](int, int) {};
+
+  double m = -INFINITY;
+  sweep([&](int, int, double t, bool off) { m = off ? m : fmax(m, t); }, nothing);     // (one entry at least is finite: checked by the host)
+  double s = 0.0;
+  sweep([&](int, int, double t, bool off) { s += off ? 0.0 : exp_nonpos(t - m, etab); }, nothing);
+  sweep([&](int c0, int i, double t, bool off) {
+          const double wv = off ? 0.0 : exp_nonpos(t - m, etab) / s;
+          if (valid) w[(int64_t)(c0 + i) * N + n] = wv;
+          const double ws = wave_sum(valid ? wv : 0.0);
+          if (lane == 0) red[i][wave] = ws;
+        },
+        [&](int c0, int len) {
+          wg_sync();
+          if (tid < len) Pb[c0 + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+        });
+  const double ll = wave_sum(valid ? m + log(s) : 0.0);
+  wg_sync();
+  if (lane == 0) red[0][wave] = ll;
+  wg_sync();
+  if (tid == 0) Pb[B] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+}
+
+// One thread per output (B counts and the log-likelihood): the row blocks' partial sums in ascending order, four interleaved chains
+// combined in a fixed order (as batched_reduce_kernel sums a problem's blocks).
+__global__ __launch_bounds__(256) void outer_resp_reduce_kernel(const double* __restrict__ partials, int B, int64_t G, double* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e > B) return;
+  const int64_t stride = (int64_t)B + 1;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  int64_t g = 0;
+  for (; g + 3 < G; g += 4) {
+    s0 += partials[g * stride + e];
+    s1 += partials[(g + 1) * stride + e];
+    s2 += partials[(g + 2) * stride + e];
+    s3 += partials[(g + 3) * stride + e];
+  }
+  for (; g < G; ++g) s0 += partials[g * stride + e];
+  out[e] = (s0 + s1) + (s2 + s3);
+}
+
+size_t outer_resp_partials(int B, int64_t N) { return (size_t)((N + kWG - 1) / kWG) * ((size_t)B + 1); }
+
+hipError_t launch_outer_resp(const double* lse, const double* log_gating, int B, int64_t N, double* w, double* partials, double* out,
+                             hipStream_t stream) {
+  if (B < 1 || N < 1 || !lse || !log_gating || !w || !partials || !out) return hipErrorInvalidValue;
+  const int64_t G = (N + kWG - 1) / kWG;
+  if (G > (int64_t)INT32_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(outer_resp_kernel, dim3((unsigned)G), dim3(kWG), 0, stream, lse, log_gating, B, N, w, partials);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(outer_resp_reduce_kernel, dim3((unsigned)(((int64_t)B + 1 + 255) / 256)), dim3(256), 0, stream, partials, B, G, out);
+  return hipGetLastError();
 }
 
 // One thread per row of the concatenated batch: its problem is the last one that starts at or before it (empty problems own no

@@ -13,7 +13,12 @@ canonical form, host uniforms), then one batched label pass draws every model's 
 SVI: per outer iteration each model draws its minibatch indices, in model order; one batched pass over the chosen rows
 of every model's resident data (BatchedHipEngine.estep(rows=...): the rows are gathered on the device, nothing but the
 indices is uploaded) gives the minibatch statistics; each model takes its natural-gradient step (_svi_step, the step of
-its solo meanfield_stochastic_descent); one batched pass over all rows gives the bounds."""
+its solo meanfield_stochastic_descent); one batched pass over all rows gives the bounds.
+
+Nested VI (meanfield_coordinate_descent_nested): the M inner mixtures of a mixture of mixtures (mixtures/hgmm.py) are the
+problems of ONE shared batch over one copy of the data; their inner descents run in lockstep on weighted batched passes, and
+the outer responsibilities — the weights of those passes — are computed and kept on the device."""
+import copy
 import random
 from contextlib import contextmanager
 
@@ -21,6 +26,7 @@ import numpy as np
 import numpy.random as npr
 
 from mimo_amd.batched import BatchedHipEngine
+from mimo_amd.engine import SuffStats
 from mimo_amd.distributions import native_sweep as _native_sweep
 from mimo_amd.distributions.lingauss import joint_rows
 from mimo_amd.mixtures.gmm import BayesianMixtureOfGaussians, _component_stats
@@ -131,6 +137,126 @@ def meanfield_coordinate_descent_batched(models, data, randomize=True, maxiter=2
                 still.append(i)
         active = still
     return vlbs
+
+
+def _nested_setup(model, obs, engine):
+    """The shared batch of a mixture of mixtures: its M inner mixtures over ONE copy of obs -> (inner mixtures, engine)."""
+    from mimo_amd.mixtures.hgmm import BayesianMixtureOfMixtureOfGaussians
+    if type(model) is not BayesianMixtureOfMixtureOfGaussians:
+        raise ValueError("the nested drivers take a BayesianMixtureOfMixtureOfGaussians")
+    inner = list(model.components)
+    if len(inner) != model.cluster_size or any(m.size != inner[0].size or m.dim != model.dim for m in inner):
+        raise ValueError("the inner mixtures must share one size and the outer model's dimension")
+    obs = np.ascontiguousarray(np.asarray(obs, dtype=float).reshape(-1, model.dim))
+    if engine is None:
+        engine = BatchedHipEngine(getattr(inner[0].engine, 'device', 0))
+    engine.set_structure('full')
+    engine.upload_shared(obs, len(inner))
+    return inner, engine
+
+
+def _tied(S):
+    """A full-structure block as the tied ('linear') update reads it: only the pooled second moment exists."""
+    return SuffStats(S.n, S.sx, None, sxx_total=S.sxx.sum(0))
+
+
+def _nested_canons(inner):
+    """The inner mixtures' canonical forms with K equal W_k (the batched pass is full-structure only)."""
+    return _stack([tuple(np.array(p, dtype=float) for p in m.canonical_expected()) for m in inner])
+
+
+def expected_responsibilities_nested(model, obs, engine=None):
+    """expected_responsibilities of a BayesianMixtureOfMixtureOfGaussians (mixtures/hgmm.py) -> (M, N): one batched pass
+    that keeps the M inner log-normalisers on the device, the outer softmax there (outer_responsibilities), one copy out."""
+    inner, engine = _nested_setup(model, obs, engine)
+    engine.estep(*_nested_canons(inner), stats=False, keep_lse=True)
+    engine.outer_responsibilities(model.gating.expected_log_gating())
+    return np.stack(engine.get_row_weights())
+
+
+def meanfield_coordinate_descent_nested(model, obs, randomize=True, maxiter=250, maxsubiter=5, maxsubsubiter=5, engine=None):
+    """meanfield_coordinate_descent of a BayesianMixtureOfMixtureOfGaussians (mixtures/hgmm.py) with ONE shared batch of
+    cluster_size problems: the M inner mixtures read one copy of obs, their inner descents run in lockstep — one weighted
+    batched pass per inner iteration —, and the outer responsibilities are computed and kept on the device
+    (BatchedHipEngine.outer_responsibilities): after the start no (M, N) table crosses PCIe.
+
+    Per outer iteration: the gating update from the outer counts; the M inner descents (per inner iteration every
+    still-active inner mixture runs its conjugate update, then one weighted pass with the resident weights gives each its
+    next statistics and its bound; an inner mixture stops where its solo run stops — two bounds closer than the inner
+    driver's default tol = 1e-8 — and is left alone from then on); one pass that keeps the inner log-normalisers; the outer
+    step.  randomize: the outer start is numpy.random.rand(M, N), normalised, and at the first outer iteration each inner
+    mixture starts from numpy.random.rand(K, N), normalised, times its outer weights, for m = 0 .. M - 1 in that order.
+    numpy's global stream is consumed exactly as the solo driver consumes it (same seeds: same tables, same drawn point
+    estimates, same state afterwards); the price is that the FIRST outer iteration of a random start is not in lockstep
+    (see below).  Returns [] (the reference records no bound)."""
+    inner, engine = _nested_setup(model, obs, engine)
+    M, K, N = len(inner), inner[0].size, int(engine.row_off[1])
+    tol = 1e-8
+    resp = None
+    if randomize:
+        resp = npr.rand(M, N)
+        resp /= np.sum(resp, axis=0)
+        counts = np.sum(resp, axis=1)
+    else:
+        engine.estep(*_nested_canons(inner), stats=False, keep_lse=True)
+        counts, _ = engine.outer_responsibilities(model.gating.expected_log_gating())
+    def stopped(vlb):
+        return len(vlb) > 1 and abs(vlb[-1] - vlb[-2]) < tol
+
+    for it in range(int(maxiter)):
+        model.gating.meanfield_update(None, counts)
+        if it == 0 and randomize:
+            # The solo stream: table of mixture 0, its inner iterations' gating draws, table of mixture 1, ...  A Dirichlet
+            # draw takes a number of generator words that depends on its parameters, so mixture m's table can only be drawn
+            # once mixture m - 1 has finished: this one outer iteration runs the inner descents one after another (each
+            # pass still covers the whole batch; the other problems' blocks are not read).
+            weights = resp                       # the only upload of an (M, N) table: the random start's
+            for m in range(M):
+                r = npr.rand(K, N)
+                r /= np.sum(r, axis=0)
+                tables = [np.zeros((K, N))] * M
+                tables[m] = r * resp[m]
+                Sm = engine.weighted_stats(tables)[m]
+                vlb = []
+                for _ in range(int(maxsubiter)):
+                    inner[m]._update_from_stats(_tied(Sm), maxsubsubiter)
+                    Sb, sc = engine.estep(*_nested_canons(inner), row_weights=weights)
+                    weights = 'resident'
+                    Sm = Sb[m]
+                    vlb.append(inner[m]._vlb_prior_terms() + sc[m, 0])
+                    if stopped(vlb):
+                        break
+        else:
+            # Lockstep.  The gating draws the solo updates end with (likelihood.params = posterior.rvs()) read nothing but the
+            # posterior and feed nothing here: each is postponed and replayed below in the solo order — mixture by mixture,
+            # iteration by iteration — so numpy's stream, and every drawn point estimate, is the solo run's.
+            S, _ = engine.estep(*_nested_canons(inner), row_weights='resident')
+            vlbs, gatings = [[] for _ in range(M)], [[] for _ in range(M)]
+            active = list(range(M))
+            for _ in range(int(maxsubiter)):
+                if not active:
+                    break
+                for m in active:
+                    mix = inner[m]
+                    mix.components.meanfield_update(None, None, maxsubsubiter,
+                                                    stats=_component_stats(_tied(S[m]), mix.components))
+                    mix.gating.meanfield_update(None, S[m].n, sample=False)
+                    gatings[m].append(copy.deepcopy(mix.gating.posterior))
+                Sb, sc = engine.estep(*_nested_canons(inner), row_weights='resident')
+                still = []
+                for m in active:
+                    vlbs[m].append(inner[m]._vlb_prior_terms() + sc[m, 0])
+                    S[m] = Sb[m]
+                    if not stopped(vlbs[m]):
+                        still.append(m)
+                active = still
+            for m in range(M):
+                for posterior in gatings[m]:       # (the last one is the mixture's final posterior)
+                    inner[m].gating.posterior = posterior
+                    inner[m].gating.refresh_likelihood()
+        engine.estep(*_nested_canons(inner), stats=False, keep_lse=True)
+        counts, _ = engine.outer_responsibilities(model.gating.expected_log_gating())
+    return []
 
 
 class _NumpyStreams:

@@ -32,6 +32,11 @@ diagonal variance); 2. B = 64, N_b = 1e4 own rows, dx = dy = 1, K = 4 (full cova
 dx = 8, dy = 4, K = 64, diagonal variance.  --trace-predict SHAPE only runs the batched call and the solo calls a few times
 (for a kernel trace from outside: predict_batched_kernel against predict_reg_kernel) and writes nothing.
 
+Nested leg (--nested, on its own; writes <out>/bench_batched_nested.json): wall time per outer iteration of
+meanfield_coordinate_descent_nested (one shared batch of M inner mixtures) against the solo
+BayesianMixtureOfMixtureOfGaussians.meanfield_coordinate_descent, same seeds, the legs alternated in one run.  Nested
+shapes (--shapes 1,2): 1. M = 4, K = 4, Dz = 2, N = 400 (the scale of the reference's examples/hgmm); 2. the same at N = 1e5.
+
 Shapes: 1. B = 24, N_b = 1600, Dz = 2, K = 100 (the reference's parallel ILR example); 2. B = 64, N_b = 1e4, Dz = 2, K = 4
 (restarts of the toy GMM); 3. B = 8, N_b = 2.5e5, Dz = 12, K = 64 (C4 per model)."""
 import argparse
@@ -306,6 +311,21 @@ class _TimedEngine:
         self.pass_s.append(time.perf_counter() - t0)
         return out
 
+    # the nested driver's calls: the shared upload, and the outer step counted with the passes
+    def upload_shared(self, Z, B):
+        t0 = time.perf_counter()
+        self.eng.upload_shared(Z, B)
+        self.upload_s += time.perf_counter() - t0
+
+    def outer_responsibilities(self, log_gating):
+        t0 = time.perf_counter()
+        out = self.eng.outer_responsibilities(log_gating)
+        self.pass_s.append(time.perf_counter() - t0)
+        return out
+
+    def __getattr__(self, name):           # (row_off, set_structure, ...: the wrapped engine's)
+        return getattr(self.eng, name)
+
 
 def ilr_models(B, N, K, engines, seed=0):
     from mimo_amd.distributions import (TruncatedStickBreaking, CategoricalWithStickBreaking, StackedNormalWisharts,
@@ -509,6 +529,98 @@ def trace_predict(sid, reps=5):
     close()
 
 
+NESTED_SHAPES = {1: (4, 4, 2, 400), 2: (4, 4, 2, 100000)}      # (M, K, Dz, N): the reference's examples/hgmm scale, and a large N
+
+
+def nested_model(M, K, D, engines, seed):
+    """A mixture of mixtures built as tests/model_checks.py::check_hier_gmm builds it; engines: one per inner mixture."""
+    import numpy.random as npr
+    from mimo_amd.distributions import (NormalWishart, TiedGaussiansWithScaledPrecision, Dirichlet, CategoricalWithDirichlet,
+                                        TiedGaussiansWithHierarchicalNormalWisharts)
+    from mimo_amd.mixtures import BayesianMixtureOfGaussiansWithHierarchicalPrior, BayesianMixtureOfMixtureOfGaussians
+    npr.seed(seed)
+
+    def inner(eng):
+        gating = CategoricalWithDirichlet(dim=K, prior=Dirichlet(dim=K, alphas=np.ones((K,))))
+        hyper = NormalWishart(dim=D, mu=np.zeros((D,)), kappa=1e-2, psi=np.eye(D), nu=D + 1. + 1e-8)
+        prior = TiedGaussiansWithScaledPrecision(size=K, dim=D, kappas=1e-2 * np.ones((K,)))
+        comps = TiedGaussiansWithHierarchicalNormalWisharts(size=K, dim=D, hyper_prior=hyper, prior=prior, engine=eng)
+        return BayesianMixtureOfGaussiansWithHierarchicalPrior(size=K, dim=D, gating=gating, components=comps, engine=eng)
+    gating = CategoricalWithDirichlet(dim=M, prior=Dirichlet(dim=M, alphas=np.ones((M,))))
+    return BayesianMixtureOfMixtureOfGaussians(cluster_size=M, mixture_size=K, dim=D, gating=gating,
+                                               components=[inner(e) for e in engines])
+
+
+def run_nested_shape(sid, reps, iters=10):
+    """Wall time per OUTER iteration of meanfield_coordinate_descent_nested against the solo
+    BayesianMixtureOfMixtureOfGaussians.meanfield_coordinate_descent (one engine per inner mixture, and one engine shared by
+    all of them): per repetition a fresh model from the same seeds runs 1 and 1 + iters outer iterations (randomize=False:
+    every iteration is a lockstep iteration); the difference / iters is the repetition's figure, the median over the
+    repetitions is reported.  Every call returns synchronised host results.  Also the largest relative difference of the
+    posteriors after 1 + iters iterations."""
+    import numpy.random as npr
+    from mimo_amd.mixtures.batched import meanfield_coordinate_descent_nested
+    M, K, D, N = NESTED_SHAPES[sid]
+    rng = np.random.default_rng(sid)
+    centres = rng.standard_normal((M * K, D)) * 6.0
+    X = np.ascontiguousarray(centres[rng.integers(M * K, size=N)] + rng.standard_normal((N, D)))
+    own, shared, beng = [HipEngine(0) for _ in range(M)], [HipEngine(0)] * M, BatchedHipEngine(0)
+
+    def nested(n, out=None):
+        mm = nested_model(M, K, D, own, 11)
+        npr.seed(12)
+        t0 = time.perf_counter()
+        meanfield_coordinate_descent_nested(mm, X, randomize=False, maxiter=n, engine=beng)
+        dt = time.perf_counter() - t0
+        if out is not None:
+            out.append(mm)
+        return dt
+
+    def solo(engines):
+        def run(n, out=None):
+            mm = nested_model(M, K, D, engines, 11)
+            npr.seed(12)
+            t0 = time.perf_counter()
+            mm.meanfield_coordinate_descent(X, randomize=False, maxiter=n, progress_bar=False)
+            dt = time.perf_counter() - t0
+            if out is not None:
+                out.append(mm)
+            return dt
+        return run
+    legs = {"nested": nested, "solo_own_engines": solo(own), "solo_shared_engine": solo(shared)}
+    kept = {name: [] for name in legs}
+    for name, fn in legs.items():                        # warm-up, and the models the outputs are compared on
+        fn(1)
+        fn(1 + iters, kept[name])
+    per = {name: [] for name in legs}
+    for _ in range(reps):                                # the legs alternate within a repetition
+        for name, fn in legs.items():
+            per[name].append((fn(1 + iters) - fn(1)) / iters)
+
+    def post(mm):
+        return [mm.gating.posterior.alphas] + [c.components.posterior.mus for c in mm.components] \
+            + [c.components.hyper_posterior.wishart.psi for c in mm.components] + [c.gating.posterior.alphas for c in mm.components]
+    diff = max(float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
+               for a, b in zip(post(kept["nested"][0]), post(kept["solo_own_engines"][0])))
+    res = {"nested_shape": sid, "M": M, "K": K, "Dz": D, "N": N, "iters_per_figure": iters, "reps": reps,
+           "max_rel_diff_posteriors": diff}
+    for name in legs:
+        res[name + "_ms_per_outer_iteration"] = float(np.median(per[name])) * 1e3
+    res["speedup_vs_own_engines"] = res["solo_own_engines_ms_per_outer_iteration"] / res["nested_ms_per_outer_iteration"]
+    res["speedup_vs_shared_engine"] = res["solo_shared_engine_ms_per_outer_iteration"] / res["nested_ms_per_outer_iteration"]
+    # where the nested iteration's time goes: its engine calls against everything else (host updates, canonical forms)
+    teng = _TimedEngine(beng)
+    mm = nested_model(M, K, D, own, 11)
+    npr.seed(12)
+    t0 = time.perf_counter()
+    meanfield_coordinate_descent_nested(mm, X, randomize=False, maxiter=1 + iters, engine=teng)
+    total = time.perf_counter() - t0
+    res["nested_engine_calls_ms_per_outer_iteration"] = float(np.sum(teng.pass_s)) / (1 + iters) * 1e3
+    res["nested_total_ms_per_outer_iteration_with_start"] = total / (1 + iters) * 1e3
+    res["nested_engine_calls_per_outer_iteration"] = len(teng.pass_s) / (1 + iters)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
@@ -523,7 +635,16 @@ def main():
     ap.add_argument("--trace-svi", type=int, default=0, metavar="SHAPE", help="only run the selection pass and the plain pass of SHAPE")
     ap.add_argument("--predict", action="store_true", help="only the prediction leg (batched predict against B solo predicts)")
     ap.add_argument("--trace-predict", type=int, default=0, metavar="SHAPE", help="only run the batched and the solo predictions of SHAPE")
+    ap.add_argument("--nested", action="store_true", help="only the nested leg (nested VI driver against the solo mixture of mixtures)")
     args = ap.parse_args()
+    if args.nested:
+        os.makedirs(args.out, exist_ok=True)
+        res = [run_nested_shape(int(s), args.reps) for s in args.shapes.split(",") if int(s) in NESTED_SHAPES]
+        for r in res:
+            print(json.dumps(r))
+        with open(os.path.join(args.out, "bench_batched_nested.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if args.trace_predict:
         trace_predict(args.trace_predict)
         return

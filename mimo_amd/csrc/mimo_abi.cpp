@@ -420,18 +420,18 @@ static Route route_for(const mimo_ctx* ctx, int K, const RouteRequest& q) {
 }
 
 // Workgroups of the pass's first kernel (what mimo_plan reports; the label-statistics stage behind a label kernel has label_stats_grid)
-static int route_grid(const Route& route, const KernelArgs& a, int num_cu, int F, int src) {
+static int route_grid(const Route& route, const TwoStagePlan& ts, const KernelArgs& a, int num_cu, int F, int src) {
   switch (route.family) {
     case Family::Small: return small_grid(a, num_cu, src);
     case Family::Narrow: return narrow_grid(a, num_cu, F, route.narrow_mode - 1);
     case Family::Mid: return mid_grid(a, num_cu);
     case Family::MidLabels: return mid_labels_grid(a, num_cu);
     case Family::Rowwave: case Family::RowwaveVi: return rowwave_grid(a, num_cu);
-    case Family::LabelStats: return label_stats_grid(a, num_cu);
+    case Family::LabelStats: return label_stats_grid(label_stats_plan(a.K, a.D, a.diag, a.N), a.N, num_cu);   // (a.diag: the two reduced maps plan alike)
     case Family::TwoStage:
       // two-stage pass on the pipelined E-step (mimo_wide.hip): that kernel is built for two workgroups per CU whatever K is
       // (fused_grid's fallback assumes one for K > 128); the statistics launches of the pass share the grid (partial blocks)
-      if (src == kSrcEstep && wide_estep_covers(a.K16, a.D, a.F16, a.gibbs)) {
+      if (ts.estep == TwoStagePlan::Wide) {
         const int64_t g2 = 2 * (int64_t)num_cu;
         return (int)(g2 < a.ntiles ? g2 : (a.ntiles > 0 ? a.ntiles : 1));
       }
@@ -480,15 +480,14 @@ static int timed_launch(mimo_ctx* ctx, const char* name, L&& launch) {
 // (a single launch under its profile name)
 #define TIMED_HIP(ctx, name, expr) timed_launch(ctx, name, [&]() -> int { HIP_TRY(ctx, expr); return MIMO_OK; })
 
-// buffers of the ranked tiles for a label-statistics pass of several launches (Dz = 10 .. 16: windows) or the one-pass kernel.
+// buffers of the ranked tiles where the pass's LabelStatsPlan asks for them: several launches (Dz = 10 .. 16: windows) or the one-pass kernel.
 // Tiles of 256 rows: label_tile_sort_kernel<256> writes, and label_stats_wide_kernel / label_stats_gram_kernel read, list entries
 // [256 t, 256 t + 256) and starts [257 t, 257 t + 256] of the tiles t < ceil(N / 256) and nothing else.
 // The one-pass kernel is the only route of its shapes, so it gets its buffers for an empty data set too (one tile nobody reads:
 // every workgroup then writes an all-zero block); the windowed launches rank their own tiles without them.
-static int prepare_label_presort(mimo_ctx* ctx, KernelArgs& a) {
+static int prepare_label_presort(mimo_ctx* ctx, KernelArgs& a, const LabelStatsPlan& lp) {
   a.sort_list = nullptr; a.sort_start = nullptr;
-  if (ctx->structure != 0 || a.D < 10) return MIMO_OK;
-  if (!label_stats_sorted(a.K, a.D, ctx->structure) && (a.N < 1 || label_stats_launches(a.K, a.D, ctx->structure) < 2)) return MIMO_OK;
+  if (lp.ranked < 2 && (lp.ranked < 1 || a.N < 1)) return MIMO_OK;
   const size_t tiles = a.N < 1 ? 1 : (size_t)((a.N + 255) / 256);
   int rc;
   if ((rc = ctx->sort_list.ensure(ctx, tiles * 256))) return rc;
@@ -497,15 +496,14 @@ static int prepare_label_presort(mimo_ctx* ctx, KernelArgs& a) {
   return MIMO_OK;
 }
 
-// Two-stage path: chunked E-step writes responsibilities / labels, then the statistics kernel
-// runs once per group of <= kMaxNCB feature column blocks, all into the same partial block.
-static int launch_two_stage(mimo_ctx* ctx, KernelArgs& a, int src, int grid) {
+// Two-stage path, the kernels of `ts`: the E-step writes responsibilities / labels, then the statistics kernel
+// runs once per group of <= ts.gmax feature column blocks, all into the same partial block.
+static int launch_two_stage(mimo_ctx* ctx, KernelArgs& a, int src, const TwoStagePlan& ts, int grid) {
   const int K = a.K, D = a.D;
   const int ncb_total = a.F16 / 16;
   int rc;
   KernelArgs st = a;
-  int stats_src = src;
-  if (src == kSrcEstep) {
+  if (ts.estep != TwoStagePlan::NoEstep) {
     KernelArgs e = a;
     e.RS = 16 * kChunkNCB + 1;
     e.split = (a.split || a.resp || a.logp || a.lse) ? 1 : 0;   // include/mimo_hip.h: scalars[1..2] come with the split or any kept table
@@ -515,41 +513,37 @@ static int launch_two_stage(mimo_ctx* ctx, KernelArgs& a, int src, int grid) {
     }
     if (chunked_lds_bytes(e) > 160 * 1024)
       return fail(ctx, MIMO_E_UNSUPPORTED, "K=%d, Dz=%d needs more LDS than one CU has", K, D);
-    if (wide_estep_covers(a.K16, D, a.F16, e.gibbs))            // pipelined softmax / label pass (mimo_wide.hip)
+    if (ts.estep == TwoStagePlan::Wide)                          // pipelined softmax / label pass (mimo_wide.hip)
       rc = TIMED_HIP(ctx, "wide_estep_kernel", launch_wide_estep(e, grid, ctx->stream));
     else
       rc = TIMED_HIP(ctx, "estep_chunked_kernel", launch_estep_chunked(e, grid, ctx->stream));
     if (rc) return rc;
     st.resp = e.resp; st.labels = e.labels; st.write_scalars = 0;
-    stats_src = e.gibbs ? kSrcLabels : kSrcWeights;
     if (ctx->n_bad > 0 && !e.gibbs && a.do_stats) {     // rows with NaN: their weights are dropped from the statistics
       if ((rc = ctx->table_tmp.ensure(ctx, (size_t)K * (size_t)ctx->N))) return rc;
       HIP_TRY(ctx, launch_mask_table(e.resp, ctx->row_mask, ctx->table_tmp, K, ctx->N, ctx->stream));
       st.resp = ctx->table_tmp;
     }
   }
-  if (!a.do_stats) return MIMO_OK;
-  if (stats_src == kSrcLabels && label_stats_covers(K, D, ctx->structure)) {
-    // label-indexed statistics of the labels just drawn: the HBM-bound pass instead of one-hot products per column group
+  if (ts.stats == TwoStagePlan::NoStats) return MIMO_OK;
+  if (ts.stats == TwoStagePlan::LabelStats) {
     KernelArgs g = st;
     g.gibbs = 0; g.do_stats = 1; g.logp = nullptr; g.lse = nullptr;
-    if ((rc = prepare_label_presort(ctx, g))) return rc;
+    if ((rc = prepare_label_presort(ctx, g, label_stats_plan(K, D, ctx->structure, g.N)))) return rc;
     return TIMED_HIP(ctx, "label_stats_kernel", launch_label_stats(g, ctx->structure, grid, ctx->stream));
   }
-  const bool wide = stats_src == kSrcWeights && wide_stats_covers(a.K16, D);     // 8-wave statistics kernel (mimo_wide.hip)
-  const int gmax = wide ? wide_stats_group_ncb(a.K16, ncb_total) : stats_group_ncb(a.K16);
-  for (int cb0 = 0; cb0 < ncb_total; cb0 += gmax) {
+  for (int cb0 = 0; cb0 < ncb_total; cb0 += ts.gmax) {
     KernelArgs g = st;
-    const int ncb = ncb_total - cb0 < gmax ? ncb_total - cb0 : gmax;
+    const int ncb = ncb_total - cb0 < ts.gmax ? ncb_total - cb0 : ts.gmax;
     g.cb0 = cb0; g.F16 = 16 * ncb; g.RS = g.F16 + 1; g.F16_total = a.F16;
     g.gibbs = 0; g.do_stats = 1; g.logp = nullptr; g.lse = nullptr;
     if (cb0 > 0) g.write_scalars = 0;
-    if (wide) {
+    if (ts.stats == TwoStagePlan::WideColumns) {        // 8-wave statistics kernel (mimo_wide.hip)
       rc = TIMED_HIP(ctx, "wide_stats_kernel", launch_wide_stats(g, grid, ctx->stream));
     } else {
       rc = timed_launch(ctx, src == kSrcEstep ? "fused_kernel(statistics of a column group)" : "fused_kernel", [&]() -> int {
         bool unsupported = false;
-        HIP_TRY(ctx, launch_fused(g, stats_src, grid, ctx->stream, &unsupported));
+        HIP_TRY(ctx, launch_fused(g, ts.stats_src, grid, ctx->stream, &unsupported));
         if (unsupported) return fail(ctx, MIMO_E_UNSUPPORTED, "no statistics kernel for K=%d, Dz=%d", K, D);
         return MIMO_OK;
       });
@@ -567,9 +561,11 @@ static int launch_route(mimo_ctx* ctx, KernelArgs& a, int src, const Route& rout
   const int K = a.K, D = a.D;
   const bool small = route.family == Family::Small;
   if (small) { a.F16_total = 16; a.F16 = 16; }
-  const int kgrid = route_grid(route, a, ctx->num_cu, ctx->F, src);
+  const TwoStagePlan ts = two_stage_plan(route, a, ctx->structure, src);
+  const int kgrid = route_grid(route, ts, a, ctx->num_cu, ctx->F, src);
   const bool lstats = route.label_draw() || route.family == Family::LabelStats;     // the label-statistics kernels close the pass
-  const int grid = lstats ? label_stats_grid(a, ctx->num_cu) : kgrid;               // partial blocks
+  const LabelStatsPlan lp = label_stats_plan(K, D, ctx->structure, a.N);            // (of that stage)
+  const int grid = lstats ? label_stats_grid(lp, a.N, ctx->num_cu) : kgrid;         // partial blocks
   *out = {grid, partial_stride(a.K16, a.F16)};
   int rc;
   if ((rc = ctx->partials.ensure(ctx, out->pstride * (size_t)grid))) return rc;
@@ -586,7 +582,7 @@ static int launch_route(mimo_ctx* ctx, KernelArgs& a, int src, const Route& rout
   // a resident-Theta label kernel counts its labels for the slot table of the statistics kernel behind it
   // (not with NaN rows: their labels are masked before the statistics; MIMO_FUSE_LABEL_HIST=0: off)
   static const bool fuse_on = [] { const char* e = getenv("MIMO_FUSE_LABEL_HIST"); return !e || atoi(e) != 0; }();
-  const bool fuse_hist = fuse_on && a.do_stats && ctx->n_bad == 0 && a.aux && label_stats_uses_slots(K, D, a.N);
+  const bool fuse_hist = fuse_on && a.do_stats && ctx->n_bad == 0 && a.aux && lp.kind == LabelStatsPlan::Slots;
   rc = MIMO_OK;
   switch (route.family) {
   case Family::LabelStats: break;
@@ -612,11 +608,11 @@ static int launch_route(mimo_ctx* ctx, KernelArgs& a, int src, const Route& rout
       return MIMO_OK;
     });
     break;
-  case Family::TwoStage: rc = launch_two_stage(ctx, a, src, grid); break;
+  case Family::TwoStage: rc = launch_two_stage(ctx, a, src, ts, grid); break;
   }
   if (rc) return rc;
   if (lstats && a.do_stats) {
-    if ((rc = prepare_label_presort(ctx, a))) return rc;
+    if ((rc = prepare_label_presort(ctx, a, lp))) return rc;
     if ((rc = TIMED_HIP(ctx, "label_stats_kernel", launch_label_stats(a, ctx->structure, grid, ctx->stream)))) return rc;
   }
   if (ctx->prof) ctx->prof_n += 1;
@@ -1501,17 +1497,18 @@ int mimo_profile_kernels(mimo_ctx* ctx, char* buf, int len) {
 }
 
 // The route of a plain pass (the one run_pass launches from) described without anything that needs a device: kind, launches, passes
-// (out8[6] — the grid — stays 0), and a one-line description of the kernels (desc, may be null).
+// (out8[6] — the grid — stays 0), and a one-line description of the kernels (desc, may be null).  It prints what the Route, the
+// TwoStagePlan and the LabelStatsPlan of the pass say and decides nothing itself.  The counters: out8[1] kernels per pass, out8[2] /
+// out8[3] writes / reads of the (K, N) table, out8[4] / out8[5] passes over Z / the labels.  "Kernels per pass" counts the kernels that
+// read Z and leaves out the helper launches: the label histogram and its reset, label_slots_kernel, the tile sort, the two reduction kernels.
 static void plan_route(const mimo_ctx* ctx, const Route& route, const KernelArgs& a, int K, int gibbs, int64_t* out8, char* desc, size_t dlen) {
   const int ncb = a.F16 / 16, D = ctx->D;
   char lst[160] = "";           // the label-statistics stage of a label pass
   auto label_stage = [&]() {
-    const int ll = label_stats_launches(K, D, ctx->structure);
-    if (label_stats_uses_slots(K, D, a.N)) snprintf(lst, sizeof lst, "label_slots_kernel + label_stats_slots_kernel");
-    else if (label_stats_sorted(K, D, ctx->structure)) snprintf(lst, sizeof lst, "label_tile_sort_kernel + label_stats_gram_kernel");
-    else if (ctx->structure != 0 || D <= 9) snprintf(lst, sizeof lst, "label_stats_kernel");
-    else snprintf(lst, sizeof lst, "label_stats_wide_kernel x %d", ll);
-    return ll;
+    const LabelStatsPlan lp = label_stats_plan(K, D, ctx->structure, a.N);
+    if (lp.kind == LabelStatsPlan::Windows) snprintf(lst, sizeof lst, "%s x %d", lp.name, lp.launches);
+    else snprintf(lst, sizeof lst, "%s", lp.name);
+    return lp.launches;
   };
   memset(out8, 0, 8 * sizeof(int64_t));
   out8[4] = 1;                           // passes over Z
@@ -1550,20 +1547,22 @@ static void plan_route(const mimo_ctx* ctx, const Route& route, const KernelArgs
     if (desc) snprintf(desc, dlen, "fused_kernel<%d column blocks, %d row block%s per wave%s>", ncb, a.K16 <= 4 ? 1 : a.K16 <= 8 ? 2 : a.K16 <= 12 ? 3 : 4,
                        a.K16 <= 4 ? "" : "s", K <= 32 && D >= 7 ? ", work split over the waves" : "");
   } else {
-    const bool wide = !gibbs && wide_stats_covers(a.K16, D);       // (the sub-kernels of the family: as run_pass picks them)
-    const int gmax = wide ? wide_stats_group_ncb(a.K16, ncb) : stats_group_ncb(a.K16), groups = (ncb + gmax - 1) / gmax;
-    out8[0] = MIMO_PLAN_TWO_STAGE; out8[1] = 1 + groups;
-    out8[2] = gibbs ? 0 : 1;             // the (K, N) responsibility table goes through HBM
-    out8[3] = gibbs ? 0 : groups;        // and is read once per statistics launch
-    out8[4] = 1 + groups;                // Z: the E-step + every statistics launch
-    out8[5] = gibbs ? 1 + groups : 0;
-    const char* est = wide_estep_covers(a.K16, D, a.F16, gibbs) ? "wide_estep_kernel" : "estep_chunked_kernel";
-    if (gibbs && label_stats_covers(K, D, ctx->structure)) {      // label-indexed statistics
+    const TwoStagePlan ts = two_stage_plan(route, a, ctx->structure, kSrcEstep);
+    const char* est = ts.estep == TwoStagePlan::Wide ? "wide_estep_kernel" : "estep_chunked_kernel";
+    const int groups = ts.groups;
+    out8[0] = MIMO_PLAN_TWO_STAGE;
+    if (ts.stats == TwoStagePlan::LabelStats) {      // label-indexed statistics
       const int ll = label_stage();
       out8[1] = 1 + ll; out8[4] = 1 + ll; out8[5] = 1 + ll;
       if (desc) snprintf(desc, dlen, "%s (label draw) + %s", est, lst);
-    } else if (desc) {
-      snprintf(desc, dlen, "%s (%s) + %s x %d", est, gibbs ? "label draw" : "softmax -> (K, N) table", wide ? "wide_stats_kernel" : "fused_kernel (statistics)", groups);
+    } else {
+      out8[1] = 1 + groups;
+      out8[2] = gibbs ? 0 : 1;             // the (K, N) responsibility table goes through HBM
+      out8[3] = gibbs ? 0 : groups;        // and is read once per statistics launch
+      out8[4] = 1 + groups;                // Z: the E-step + every statistics launch
+      out8[5] = gibbs ? 1 + groups : 0;
+      if (desc) snprintf(desc, dlen, "%s (%s) + %s x %d", est, gibbs ? "label draw" : "softmax -> (K, N) table",
+                         ts.stats == TwoStagePlan::WideColumns ? "wide_stats_kernel" : "fused_kernel (statistics)", groups);
     }
   }
 }
@@ -1581,7 +1580,7 @@ int mimo_plan(mimo_ctx* ctx, int K, int gibbs, int64_t* out8) {
   const Route route = route_for(ctx, K, {kSrcEstep, gibbs != 0});
   plan_route(ctx, route, a, K, gibbs, out8, nullptr, 0);
   if (order_applies(ctx, route, a)) out8[0] |= MIMO_PLAN_ORDERED;
-  out8[6] = route_grid(route, a, ctx->num_cu, ctx->F, kSrcEstep);
+  out8[6] = route_grid(route, two_stage_plan(route, a, ctx->structure, kSrcEstep), a, ctx->num_cu, ctx->F, kSrcEstep);
   out8[7] = ctx->num_cu;
   return MIMO_OK;
   });

@@ -37,12 +37,17 @@ hipError_t launch_wide_stats(const KernelArgs& a, int grid, hipStream_t stream);
 bool wide_estep_covers(int K16, int D, int F16, int gibbs);
 hipError_t launch_wide_estep(const KernelArgs& a, int grid, hipStream_t stream);
 
-// label statistics (mimo_label_stats.hip): launches of one pass — 1, or the 128-component windows of label_stats_wide_kernel
-int label_stats_launches(int K, int D, int structure);
-bool label_stats_sorted(int K, int D, int structure);       // the one-pass kernel over the ranked tiles serves the shape (needs the presort buffers)
+// label statistics (mimo_label_stats.hip): what closes a label pass over N rows, decided by label_stats_plan alone
+struct LabelStatsPlan {
+  enum Kind { None, PerComponent, Slots, Windows, Ranked } kind;   // None: no kernel; Slots needs KernelArgs::aux
+  int launches;           // statistics launches that read Z: 1, or the 128-component windows of label_stats_wide_kernel
+  int ranked;             // ranked-tile buffers (sort_list / sort_start): 0 none, 1 used when present (windows, K > 128), 2 required (Ranked)
+  int tile, per_cu;       // rows per tile and workgroups per CU: what label_stats_grid sizes the grid from
+  const char* name;       // the stage in mimo_plan_shape's description (Windows: "x launches" behind it)
+};
+LabelStatsPlan label_stats_plan(int K, int D, int structure, int64_t N);
+int label_stats_grid(const LabelStatsPlan& p, int64_t N, int num_cu);
 void set_sorted_range_cap(int tiles);                        // tiles per range of the one-pass kernel at most (mimo_tune "sorted_range"; 0: default)
-// ... and the slot-table variant for skewed label vectors (K >= 17, Dz <= 9, N >= 2^17): needs KernelArgs::aux
-bool label_stats_uses_slots(int K, int D, int64_t N);
 size_t label_stats_aux_words();
 hipError_t launch_label_hist_reset(const KernelArgs& a, hipStream_t stream);
 bool gibbs_rowwave_counts_labels(int K, int F16, int ZS);

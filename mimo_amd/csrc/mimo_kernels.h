@@ -118,8 +118,7 @@ bool rowwave_covers(int K, int F16, int ZS);
 int rowwave_image_ns(int K, int F16, int ZS);     // contraction steps of the operand image (padded to whole chunks where Theta streams)
 int rowwave_grid(const KernelArgs& a, int num_cu);
 hipError_t launch_gibbs_rowwave(const KernelArgs& a, int grid, hipStream_t stream);
-bool label_stats_covers(int K, int D, int structure);
-int label_stats_grid(const KernelArgs& a, int num_cu);
+bool label_stats_covers(int K, int D, int structure);   // (the plan and the grid of the stage: mimo_extra.h)
 hipError_t launch_label_stats(const KernelArgs& a, int structure, int grid, hipStream_t stream);
 
 hipError_t launch_table_entropy(const double* table, int64_t count, double* partials, int nblocks,

@@ -7,7 +7,8 @@
 //   label_stats_gram_kernel<DZ>        Dz >= 17 (and K > 128 from Dz = 15): one pass over the tiles ranked by
 //   label_tile_sort_kernel<256>        ... this kernel, Gram matrices per component on the matrix cores
 //
-// and the routing between them (label_stats_covers, label_stats_launches, label_stats_grid, launch_label_stats).
+// and the routing between them: label_stats_plan decides kernel, launches, ranked-tile buffers and grid rule once;
+// label_stats_covers, label_stats_grid and launch_label_stats read its LabelStatsPlan.
 //
 // The statistics of hard labels are a scatter; done deterministically without float atomics: per tile of rows a bitmap per
 // component (integer atomic OR: order-free), stable ranks by popcount, then the threads of a component walk ITS rows in
@@ -17,6 +18,7 @@
 // Reference behaviour reproduced: mimo/mixtures/gmm.py:227-237 (resample_components' statistics), gaussian.py:491-502,
 // data.py:160-169.
 #include "mimo_device.h"
+#include "mimo_extra.h"
 
 #include <cstdlib>
 
@@ -1024,12 +1026,6 @@ __global__ __launch_bounds__(kWG, gram_wgs_per_cu(DZ)) void label_stats_gram_ker
 
 static int g_sorted_range_cap = kSortedRange;
 void set_sorted_range_cap(int tiles) { g_sorted_range_cap = tiles < 1 || tiles > kSortedRange ? kSortedRange : tiles; }
-// Dz >= 17; and K > 128 from Dz = 15 (against the two windows of label_stats_wide_kernel, N = 2e6, ms: Dz=16 K=256 0.36 -> 0.27, K=192 0.32 -> 0.25,
-// Dz=15 K=160 0.26 -> 0.24; Dz=14 K=200 0.23 -> 0.25 and Dz=13 K=256 0.25 -> 0.26 stay windowed)
-static bool label_stats_sorted_covers(int K, int D) {
-  if (D > kMaxD || K < 1 || K > 256) return false;
-  return D >= 17 || (D >= 15 && K > 128);
-}
 template <int DZ>
 static hipError_t launch_sorted(const KernelArgs& a, int grid, hipStream_t stream) {
   hipError_t e = launch_label_tile_sort(a, grid, stream);
@@ -1041,37 +1037,40 @@ static hipError_t launch_sorted(const KernelArgs& a, int grid, hipStream_t strea
   return hipGetLastError();
 }
 
-bool label_stats_sorted(int K, int D, int structure) { return structure == 0 && label_stats_sorted_covers(K, D); }
-
-// Dz = 10 .. 16: four feature slices per component up to K = 64, two beyond — in windows of 128 components per launch
-static bool label_stats_wide_covers(int D) { return D >= 10 && D <= 16; }
+// The one decision about the statistics stage of a label pass: which kernel closes it, in how many launches, whether it takes the ranked
+// tiles, what its grid is sized from.  launch_label_stats and label_stats_grid below and the C-ABI layer (presort buffers, the histogram
+// fused into the label kernel, mimo_plan's description) read this value.  structure: MIMO_STRUCT_*.  In order of precedence:
+//   Slots         K = 17 .. 256 at Dz <= 9 with at least 2^17 rows, any structure (MIMO_LABEL_STATS_SLOTS=0: the round-2 kernel, tuning knob)
+//   Ranked        full map, Dz >= 17; and K > 128 from Dz = 15 (against the two windows of label_stats_wide_kernel, N = 2e6, ms: Dz=16 K=256
+//                 0.36 -> 0.27, K=192 0.32 -> 0.25, Dz=15 K=160 0.26 -> 0.24; Dz=14 K=200 0.23 -> 0.25 and Dz=13 K=256 0.25 -> 0.26 stay windowed)
+//   PerComponent  reduced maps up to Dz = 16 (at most 2 Dz + 1 accumulators), the full map up to Dz = 9
+//   Windows       full map, Dz = 10 .. 16: four feature slices per component up to K = 64, two beyond; 128 components per launch
+LabelStatsPlan label_stats_plan(int K, int D, int structure, int64_t N) {
+  static const bool slots_on = [] { const char* e = getenv("MIMO_LABEL_STATS_SLOTS"); return !e || atoi(e) != 0; }();
+  LabelStatsPlan p = {LabelStatsPlan::None, 1, 0, D <= (structure != 0 ? 10 : 9) ? kLsTile : kLsWideTile, 2, ""};
+  if (K < 1 || K > 256 || D < 1 || D > kMaxD) return p;
+  if (slots_on && K >= 17 && D <= 9 && N >= (1 << 17)) {
+    p.kind = LabelStatsPlan::Slots; p.name = "label_slots_kernel + label_stats_slots_kernel";
+    if (D <= 2) p.per_cu = 3;                    // (52 KB of LDS, <= 88 registers: three per CU)
+  } else if (structure == 0 && (D >= 17 || (D >= 15 && K > 128))) {
+    p.kind = LabelStatsPlan::Ranked; p.name = "label_tile_sort_kernel + label_stats_gram_kernel";
+    p.ranked = 2; p.per_cu = gram_wgs_per_cu(D);
+  } else if (D <= (structure != 0 ? 16 : 9)) {
+    p.kind = LabelStatsPlan::PerComponent; p.name = "label_stats_kernel";
+  } else if (structure == 0 && D <= 16) {
+    p.kind = LabelStatsPlan::Windows; p.name = "label_stats_wide_kernel";
+    p.launches = (K + 127) / 128; p.ranked = K > 128 ? 1 : 0;
+  }
+  return p;
+}
 bool label_stats_covers(int K, int D, int structure) {
-  if (K < rowwave_min_k() || K > 256 || D < 1) return false;
-  if (structure != 0) return D <= 16;            // reduced maps (diagonal / linear): at most 2 Dz + 1 accumulators
-  return D <= 9 || label_stats_wide_covers(D) || label_stats_sorted_covers(K, D);
-}
-
-// launches of one statistics pass (each reads Z once): 1, or the 128-component windows of label_stats_wide_kernel
-int label_stats_launches(int K, int D, int structure) {
-  if (structure != 0 || !label_stats_wide_covers(D) || label_stats_sorted_covers(K, D)) return 1;
-  return (K + 127) / 128;
-}
-
-// K >= 17 at Dz <= 9 with at least 2^17 rows: label_stats_slots_kernel (MIMO_LABEL_STATS_SLOTS=0: the round-2 kernel, tuning knob)
-static bool label_stats_slots_on() {
-  static const bool on = [] { const char* e = getenv("MIMO_LABEL_STATS_SLOTS"); return !e || atoi(e) != 0; }();
-  return on;
-}
-bool label_stats_uses_slots(int K, int D, int64_t N) {
-  return label_stats_slots_on() && K >= 17 && K <= 256 && D >= 1 && D <= 9 && N >= (1 << 17);
+  return K >= rowwave_min_k() && label_stats_plan(K, D, structure, INT64_MAX).kind != LabelStatsPlan::None;
 }
 size_t label_stats_aux_words() { return kLsAuxWords; }
-
-int label_stats_grid(const KernelArgs& a, int num_cu) {
-  const int tile = a.D <= (a.diag ? 10 : 9) ? kLsTile : kLsWideTile;
-  const int64_t tiles = (a.N + tile - 1) / tile;
-  int64_t g = (int64_t)num_cu * (label_stats_uses_slots(a.K, a.D, a.N) && a.D <= 2 ? 3 : 2);     // (52 KB of LDS, <= 88 registers: three per CU)
-  if (!a.diag && label_stats_sorted_covers(a.K, a.D)) g = (int64_t)num_cu * gram_wgs_per_cu(a.D);
+// (the grid fixes the number of partial blocks, and with it the order of the sums)
+int label_stats_grid(const LabelStatsPlan& p, int64_t N, int num_cu) {
+  const int64_t tiles = (N + p.tile - 1) / p.tile;
+  int64_t g = (int64_t)num_cu * p.per_cu;
   if (g > tiles) g = tiles;
   return (int)(g < 1 ? 1 : g);
 }
@@ -1117,9 +1116,11 @@ hipError_t launch_label_hist_reset(const KernelArgs& a, hipStream_t stream) {
 // structure: 0 full, 1 diagonal, 2 linear (MIMO_STRUCT_*)
 hipError_t launch_label_stats(const KernelArgs& a, int structure, int grid, hipStream_t stream) {
   typedef void (*fn_t)(const KernelArgs);
-  if (a.D < 1 || a.D > kMaxD || a.K < 1 || a.K > 256) return hipErrorInvalidValue;
+  const LabelStatsPlan p = label_stats_plan(a.K, a.D, structure, a.N);
   fn_t fn = nullptr;
-  if (label_stats_uses_slots(a.K, a.D, a.N)) {
+  switch (p.kind) {
+  case LabelStatsPlan::None: break;
+  case LabelStatsPlan::Slots:
     if (!a.aux) return hipErrorInvalidValue;
     fn = structure == 1 ? pick_label_stats_slots<1>(a.D) : structure == 2 ? pick_label_stats_slots<2>(a.D) : pick_label_stats_slots<0>(a.D);
     if (!fn) return hipErrorInvalidValue;
@@ -1131,21 +1132,19 @@ hipError_t launch_label_stats(const KernelArgs& a, int structure, int grid, hipS
       hipLaunchKernelGGL(label_hist_kernel, dim3(hg), dim3(kWG), 0, stream, a.labels, a.N, a.K, a.aux);
     }
     hipLaunchKernelGGL(label_slots_kernel, dim3(1), dim3(kWG), 0, stream, a.aux, a.K);
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(kWG), 0, stream, a);
-    return hipGetLastError();
-  }
-  if (structure == 0 && a.sort_list && a.sort_start && label_stats_sorted_covers(a.K, a.D)) {
+    break;
+  case LabelStatsPlan::Ranked:          // (the only kernel of its shapes: without the presort buffers, launch_label_tile_sort's error)
     switch (a.D) {
 #define MIMO_SD(d) case d: return launch_sorted<d>(a, grid, stream);
       MIMO_SD(10) MIMO_SD(11) MIMO_SD(12) MIMO_SD(13) MIMO_SD(14) MIMO_SD(15) MIMO_SD(16) MIMO_SD(17) MIMO_SD(18) MIMO_SD(19) MIMO_SD(20)
       MIMO_SD(21) MIMO_SD(22) MIMO_SD(23) MIMO_SD(24) MIMO_SD(25) MIMO_SD(26) MIMO_SD(27) MIMO_SD(28) MIMO_SD(29) MIMO_SD(30) MIMO_SD(31) MIMO_SD(32)
 #undef MIMO_SD
     }
-  }
-  if (structure == 1) fn = pick_label_stats_struct<1>(a.D);
-  else if (structure == 2) fn = pick_label_stats_struct<2>(a.D);
-  else if (a.D <= 9) fn = pick_label_stats_struct<0>(a.D);
-  else if (label_stats_wide_covers(a.D)) {
+    break;
+  case LabelStatsPlan::PerComponent:
+    fn = structure == 1 ? pick_label_stats_struct<1>(a.D) : structure == 2 ? pick_label_stats_struct<2>(a.D) : pick_label_stats_struct<0>(a.D);
+    break;
+  case LabelStatsPlan::Windows: {
     static const fn_t wide4[7] = {label_stats_wide_kernel<10, 4>, label_stats_wide_kernel<11, 4>, label_stats_wide_kernel<12, 4>,
                                   label_stats_wide_kernel<13, 4>, label_stats_wide_kernel<14, 4>, label_stats_wide_kernel<15, 4>,
                                   label_stats_wide_kernel<16, 4>};
@@ -1153,22 +1152,23 @@ hipError_t launch_label_stats(const KernelArgs& a, int structure, int grid, hipS
                                   label_stats_wide_kernel<13, 2>, label_stats_wide_kernel<14, 2>, label_stats_wide_kernel<15, 2>,
                                   label_stats_wide_kernel<16, 2>};
     fn = a.K <= 64 ? wide4[a.D - 10] : wide2[a.D - 10];
-    if (a.K > 128) {                  // windows of 128 components, one launch each into the same partial block
-      const bool presort = label_presort_on() && a.sort_list && a.sort_start;
-      if (presort) {
-        hipError_t e = launch_label_tile_sort(a, grid, stream);
-        if (e != hipSuccess) return e;
-      }
-      for (int k0 = 0; k0 < a.K; k0 += 128) {
-        KernelArgs w = a;
-        w.presort = presort ? 1 : 0;
-        w.k0 = k0;
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(kWG), 0, stream, w);
-      }
-      return hipGetLastError();
+    if (p.launches < 2) break;
+    // windows of 128 components, one launch each into the same partial block
+    const bool presort = label_presort_on() && a.sort_list && a.sort_start;
+    if (presort) {
+      hipError_t e = launch_label_tile_sort(a, grid, stream);
+      if (e != hipSuccess) return e;
     }
+    for (int k0 = 0; k0 < a.K; k0 += 128) {
+      KernelArgs w = a;
+      w.presort = presort ? 1 : 0;
+      w.k0 = k0;
+      hipLaunchKernelGGL(fn, dim3(grid), dim3(kWG), 0, stream, w);
+    }
+    return hipGetLastError();
   }
-  if (!fn) return hipErrorInvalidValue;       // (the full map at Dz >= 17 has the one-pass kernel only: without the presort buffers, an error)
+  }
+  if (!fn) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(kWG), 0, stream, a);
   return hipGetLastError();
 }

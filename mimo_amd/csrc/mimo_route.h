@@ -1,6 +1,9 @@
 // Which kernel family serves a pass: the shape and the request in, a Route value out.  choose_route() is the only place where
 // the precedence between the families is written; the entry points (Theta image), run_pass (launches, grid) and mimo_plan /
-// mimo_plan_shape (description) all take its Route.  Host only, included by mimo_abi.cpp alone; no HIP call below.
+// mimo_plan_shape (description) all take its Route.  Below the family, two_stage_plan() at the end of this file decides what a
+// two-stage pass launches (TwoStagePlan), and label_stats_plan() (mimo_label_stats.hip, LabelStatsPlan in mimo_extra.h) which
+// label-statistics kernel closes a label pass: launcher, grid and description read those two values the same way.
+// Host only, included by mimo_abi.cpp (and the host tool tools/stage_plan_sweep.cpp); no HIP call below.
 #pragma once
 #include "mimo_kernels.h"
 #include "mimo_extra.h"
@@ -186,6 +189,29 @@ inline Route choose_route(const RouteShape& s, int K, const RouteRequest& q, con
     if (plain && !q.weighted && s.n_bad == 0 && s.D <= 16 && vi_rowwave_covers(K, s.F16, route_zs(K, s.D))) return is(Family::RowwaveVi, Image::RowOwner);
   }
   return is(fused ? Family::Fused : Family::TwoStage);
+}
+
+// What a two-stage pass launches: the E-step in front (none for the statistics of a caller's table / labels) and the statistics
+// behind it.  Decided here alone: launch_two_stage runs it, route_grid sizes the grid from it, plan_route prints it
+// (a route of another family: the empty plan).
+struct TwoStagePlan {
+  enum Estep { NoEstep, Chunked, Wide } estep = NoEstep;      // estep_chunked_kernel | the pipelined wide_estep_kernel (mimo_wide.hip)
+  enum Stats { NoStats, LabelStats, WideColumns, FusedColumns } stats = NoStats;   // label statistics | per column group: 8-wave wide_stats_kernel, fused_kernel
+  int stats_src = kSrcWeights;                                // what the statistics read: the (K, N) table or the labels
+  int gmax = 0, groups = 0;                                   // (per column group) feature column blocks per statistics launch; launches
+};
+inline TwoStagePlan two_stage_plan(const Route& route, const KernelArgs& a, int structure, int src) {
+  TwoStagePlan p;
+  if (route.family != Family::TwoStage) return p;
+  if (src == kSrcEstep) p.estep = wide_estep_covers(a.K16, a.D, a.F16, a.gibbs) ? TwoStagePlan::Wide : TwoStagePlan::Chunked;
+  p.stats_src = src != kSrcEstep ? src : a.gibbs ? kSrcLabels : kSrcWeights;
+  if (!a.do_stats) return p;
+  // label-indexed statistics of the labels just drawn: the HBM-bound pass instead of one-hot products per column group
+  if (p.stats_src == kSrcLabels && label_stats_covers(a.K, a.D, structure)) { p.stats = TwoStagePlan::LabelStats; return p; }
+  p.stats = p.stats_src == kSrcWeights && wide_stats_covers(a.K16, a.D) ? TwoStagePlan::WideColumns : TwoStagePlan::FusedColumns;
+  p.gmax = p.stats == TwoStagePlan::WideColumns ? wide_stats_group_ncb(a.K16, a.F16 / 16) : stats_group_ncb(a.K16);
+  p.groups = (a.F16 / 16 + p.gmax - 1) / p.gmax;
+  return p;
 }
 
 }  // namespace mimo

@@ -116,7 +116,10 @@ void fused_kernel(const KernelArgs a) {
   const bool do_stats = (MODE == kFastVI || MODE == kFastGibbs) ? true : a.do_stats != 0;
   constexpr int NSI = 4 * NCB;  // contraction steps of 4 features in the Theta image (row-block stride)
   // steps actually needed: with Dz known at compile time the zero-padded tail of the last column block is skipped
-  constexpr int NS = DS > 0 ? ((DS + 1) * (DS + 2) / 2 + 3) / 4 : NSI;
+  // (SEED, below at TRIM: nor is the constant feature contracted)
+  constexpr int NFEAT = (DS + 1) * (DS + 2) / 2;
+  constexpr bool SEED = MODE == kFastVI && DS >= 10 && RBW == 1 && SPLIT == 0 && NFEAT % 4 == 1;
+  constexpr int NS = DS > 0 ? (NFEAT - (SEED ? 1 : 0) + 3) / 4 : NSI;
   constexpr int T = kTile;
 
   extern __shared__ __align__(16) unsigned char smem[];
@@ -180,6 +183,20 @@ void fused_kernel(const KernelArgs a) {
 #pragma unroll
     for (int e = 0; e < PF; ++e) ring[e] = theta_slice(e);
   }
+  // SEED: c of this lane's four accumulator rows (component 16 wave + q + 4 r), from the slice that is no longer streamed: lane
+  // (i, kk = 0) of slice NS holds Theta[16 wave + i][4 NS] = c.  Dz = 16 (dense and SKIP): loaded once, 8 loop-invariant VGPRs (199 ->
+  // 207 and 211 -> 219; the LDS holds these kernels at two workgroups per CU whatever their registers).  Dz = 13 (SEED_TILE) sits
+  // at 165 VGPRs, three short of the 168 that its third workgroup per CU allows, and the loop-invariant form takes it to 173 (as
+  // does a load at the top of the tile: 175): there the four values are loaded per tile from the L2-resident image at the start of
+  // step 3, where they live no longer than the accumulators they become, behind the step's opaque base (or the loads are hoisted
+  // back out of the loop); the other two waves of the SIMD cover the L2 round trip.
+  constexpr bool SEED_TILE = SEED && DS < 14;
+  double cseed[4] = {0.0, 0.0, 0.0, 0.0};
+  auto load_seed = [&](gptr_t base) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) cseed[r] = base[NS * 64 + q + 4 * r];
+  };
+  if constexpr (SEED && !SEED_TILE) load_seed(thw0);
 
   d4 sacc[RBW][NCB];
 #pragma unroll
@@ -213,6 +230,18 @@ void fused_kernel(const KernelArgs a) {
   // SIMD -> two; the statistics modes: + 4 VGPRs).  Those keep the forms they had and their device code does not change;
   // the ten TRIM instantiations keep their occupancy with 0 scratch (profiles/r07_c2_valu_trim.txt).
   constexpr bool TRIM = MODE == kFastVI && DS >= 10 && RBW == 1 && SPLIT == 0;
+  // SEED (declared with NS, which depends on it): the TRIM instantiations whose feature count is 1 mod 4 (Dz = 13 and 16, dense and
+  // SKIP).  The last feature of the map is z~_D z~_D = 1, the constant, and there it sits alone in the last contraction step: two
+  // MFMAs per wave-tile that multiply c_k by 1.0 and three zero pads by zeros.  Instead the accumulators of step 3 start at c_k
+  // (cseed) and the step is not issued: NS - 1 steps, the operand image, F16, the feature tile and the statistics as they were (the
+  // constant column of Phi still feeds n_k).  l sums the same terms with c first instead of last, so it moves by rounding.  The
+  // rows of a tile past N, whose features are all zero, now carry l = c_k instead of 0; every consumer of such a row in
+  // normalise_tile (sc_lse, sc_prod, scale, the live mask) tests `valid`, c is finite in the image (padding and switched-off
+  // components: kPadLogDensity, as before), so their weights are 0 as before.  Every other instantiation keeps its device code:
+  // the Gibbs labels and the batched kernels are compared bit for bit (profiles/r15_c2_estep_seed.txt); that includes the fast VI
+  // kernels of Dz = 5 and 8, whose feature count is 1 mod 4 as well (not measured, and Dz = 8 sits at an occupancy step).  Staging the
+  // next tile (step 1') in front of the statistics in these kernels was measured on top of the seed and did not show (same file).
+  static_assert(!SEED || TRIM, "accumulator seed: a TRIM instantiation");
   constexpr bool LX = fused_lane_regs(NCB, RBW, MODE, DS, SPLIT, SKIP);
   int zoff[ZPT];
 #pragma unroll
@@ -400,6 +429,7 @@ void fused_kernel(const KernelArgs a) {
       } else if (wave < K16) {   // wave-uniform (scalar) test: this wave owns at least row block `wave`
         thw = thw0;
         asm volatile("" : "+s"(thw));  // opaque per tile: slice addresses = scalar base + immediates, not 2*NE hoisted VGPRs
+        if constexpr (SEED_TILE) load_seed(thw);   // (behind the opaque base: not hoisted back out of the tile loop)
         const double* p0 = Ph + j * RS + q;
         const double* p1 = Ph + (16 + j) * RS + q;
 #pragma unroll
@@ -407,7 +437,10 @@ void fused_kernel(const KernelArgs a) {
           if (RBW == 1 || wave + 4 * h * RP < K16) {   // scalar: the pass has at least one live row block
             d4 acc[RP][2];
 #pragma unroll
-            for (int i2 = 0; i2 < RP; ++i2) { acc[i2][0] = d4{0.0, 0.0, 0.0, 0.0}; acc[i2][1] = d4{0.0, 0.0, 0.0, 0.0}; }
+            for (int i2 = 0; i2 < RP; ++i2) {
+              if constexpr (SEED) acc[i2][0] = acc[i2][1] = d4{cseed[0], cseed[1], cseed[2], cseed[3]};   // RP = 1: c of row block `wave`
+              else { acc[i2][0] = d4{0.0, 0.0, 0.0, 0.0}; acc[i2][1] = d4{0.0, 0.0, 0.0, 0.0}; }
+            }
             // B operands are read two contraction steps ahead of their MFMAs (an LDS read is ~2-3 MFMA
             // issue slots away); sched_barriers keep hipcc from sinking the reads back to their use
             double bq0[3], bq1[3];

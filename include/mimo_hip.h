@@ -441,6 +441,63 @@ int mimo_outer_resp_batched(mimo_ctx* ctx, const double* log_gating, int flags, 
  * to the host, problem b's at row_off[b].  MIMO_E_STATE if none are valid. */
 int mimo_get_row_weights_batched(mimo_ctx* ctx, double* out);
 
+/* ---- device-resident batched VI: the conjugate update and the bound between two passes, on the device ----
+ * For B mixtures of Gaussians with a Dirichlet gating and full (untied) Normal-Wishart components — the family
+ * mimo_host_gmm_vi_sweep covers with tied = 0 — a whole mean-field iteration stays on the device: the statistics a batched pass
+ * left resident are turned into the posterior, its canonical form goes straight into the operand image the next pass reads, and
+ * the prior terms of the bound meet the pass's scalars there.  Shapes, structure, communicator and pending calls: as
+ * mimo_estep_batched (MIMO_E_UNSUPPORTED / MIMO_E_STATE otherwise), on ragged and shared batches.  Every sum runs in a fixed order
+ * that depends on (K, Dz) alone: a problem's numbers do not depend on what else is in the batch, bit for bit.
+ *
+ * mimo_vi_prior_batched: the priors of the B problems, copied to the device once.
+ * Replaces: the prior's nat_param / log_partition() read by every meanfield_update and bound (mimo/distributions/
+ *   bayesian.py:225-230,258-265; composite.py:50-72,95-98) and the Dirichlet prior's alphas (dirichlet.py:31-33).
+ *   alpha0 (B,K) the Dirichlet concentrations; pa (B,K,Dz), pb (B,K), pc (B,K,Dz,Dz), pd (B,K) the Normal-Wishart natural
+ *   parameters (kappa m, kappa, psi^-1 + kappa m m', nu - Dz); prior_logZ (B,K) their log-partitions.  Every element finite
+ *   (MIMO_E_INVALID otherwise).  The call resets the loop state: every problem active, its trace empty, its status clear, its
+ *   posterior block zero.  An upload drops the prior block. */
+int mimo_vi_prior_batched(mimo_ctx* ctx, int K, const double* alpha0, const double* pa, const double* pb, const double* pc,
+                          const double* pd, const double* prior_logZ);
+
+/* `iters` mean-field iterations of every active problem, enqueued without a host synchronisation: per iteration the update of the
+ * K Normal-Wishart blocks from the resident statistics (eta_post = eta_prior + S, nat -> std, SPD inverse, E[stats], canonical
+ * form, the component's term of the bound), the Dirichlet update with E[log pi] and its term of the bound, the batched softmax
+ * pass on the image just written, its reduction, and vlb = prior terms + sum lse with the drivers' stopping rule.
+ * Replaces: per model and iteration, what meanfield_coordinate_descent runs between two data passes (mimo/mixtures/
+ *   gmm.py:275-285): meanfield_update of the components and the gating (bayesian.py:78-83,225-230; composite.py:50-72,106-118;
+ *   wishart.py:139-143; dirichlet.py:31-33,85-87), the expected log-densities (gmm.py:244-254), the bound's prior terms
+ *   (bayesian.py:93-96,258-265; composite.py:95-98,120-128; wishart.py:129-132; dirichlet.py:78-97) and the stopping rule of the
+ *   descent — the arithmetic of mimo_host_gmm_vi_sweep and mimo_host_gmm_vi_bound, restated for the device.
+ * Needs the prior block (mimo_vi_prior_batched) and resident statistics of this K from the last batched pass that returned
+ * statistics (mimo_estep_batched and its weighted / row-selection forms without MIMO_F_NO_STATS, mimo_label_stats_batched,
+ * mimo_weighted_stats_batched, mimo_random_resp_stats_batched, an earlier mimo_vi_run_batched); MIMO_E_STATE names what is missing.
+ * The loop's own passes are always the plain pass over all rows: statistics left by mimo_estep_batched_weighted or
+ * mimo_estep_batched_rows are taken as the start, but from the second iteration on the run is unweighted and over the full data.
+ *   trace (iters, B): iteration i's bound of problem b at [i B + b], NaN where the problem appended nothing; n_done (B): bounds
+ *   appended in this call; status (B): 0, or bits: 1 a component's block c - kappa m m' of the problem was not positive definite;
+ *   2 a canonical form (c_total, bb, W), a term of the bound or the bound itself was not finite (a digamma argument <= 0, an
+ *   overflow) — what the host packing path refuses with MIMO_E_INVALID.
+ *   A problem stops once two consecutive bounds are closer than tol (tol >= 0; 0: never): from then on its posterior block and its
+ *   operand image stay exactly as they are.  A problem whose status is set stops too and appends nothing for the failing
+ *   iteration; it keeps the posterior block of its last complete iteration (zeros if there is none), but its operand image and
+ *   its rows of the resident statistics are undefined from then on (the other components of the failing iteration may or may not
+ *   have written their entries); the other problems are not affected.  A set status is not an error of the call.
+ *   flags: 0.  1 <= iters <= 65536.
+ * The state persists: a run can be issued in chunks, with identical bits.  The statistics of the last pass stay resident. */
+int mimo_vi_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status);
+
+/* The posterior blocks of the loop, per problem b at out + b (K (10 + 3 Dz + 3 Dz^2) + 2), in the part order of the host sweep:
+ *   alpha K | qa K Dz | qb K | qc K Dz^2 | qd K | mus K Dz | psis K Dz^2 | nus K | half_logdet_psi K | cc K | bb K Dz | W K Dz^2 |
+ *   E2 K | E4 K | E[log pi] K | c_total K | the Dirichlet term and the summed component terms of the bound
+ * (mimo/distributions/composite.py:50-72,106-128; dirichlet.py:31-33,78-97).  Zeros for a problem that has not finished an iteration. */
+int mimo_vi_get_batched(mimo_ctx* ctx, int K, double* out);
+
+/* Test hook: what the loop's passes read and leave on the device.  theta (or NULL): the operand images, B x ceil(K/16) x (F16/4) x 64
+ * doubles (F16: (Dz+1)(Dz+2)/2 rounded up to 16) — per problem the image mimo_estep_batched packs from (c_total, bb, W).  stats (or
+ * NULL): the resident statistics block, B x K (1 + Dz + Dz^2) doubles as mimo_estep_batched returns S, then the B x 3 scalars;
+ * MIMO_E_STATE if none of this K are resident.  No reference counterpart. */
+int mimo_vi_get_theta_batched(mimo_ctx* ctx, int K, double* theta, double* stats);
+
 /* Posterior-predictive mixture moments of B ILR models in one launch: per problem b what mimo_predict_flags returns on a
  * context whose resident rows are (X_b - shift_b) / scale_b, bit for bit, and the same bits whatever else is in the batch.
  * Replaces: the loop `for ilr in ilrs: ilr.meanfield_prediction(input)` of examples/ilr/evaluate_sinc_parallel.py:196-201 over

@@ -412,6 +412,83 @@ class BatchedHipEngine:
         self._check(self._lib.mimo_outer_resp_batched(self._ctx, _ptr(lg), 0, _ptr(out)))
         return out[:self.B].copy(), float(out[self.B])
 
+    # ---- device-resident VI (mimo_vi_prior_batched / mimo_vi_run_batched / mimo_vi_get_batched) ----
+    VI_PARTS = ('alpha', 'qa', 'qb', 'qc', 'qd', 'mus', 'psis', 'nus', 'hld', 'cc', 'bb', 'W', 'E2', 'E4', 'e_log_pi', 'c_total',
+                'vlb')
+
+    def _vi_part_shapes(self, K):
+        D = self.D
+        v, m = (K, D), (K, D, D)
+        return ((K,), v, (K,), m, (K,), v, m, (K,), (K,), (K,), v, m, (K,), (K,), (K,), (K,), (2,))
+
+    def vi_set_prior(self, alpha0, pa, pb, pc, pd, prior_logZ):
+        """The priors of the B problems' mixtures of Gaussians (Dirichlet gating, untied Normal-Wishart components), copied to
+        the device once: alpha0 (B, K), the Normal-Wishart natural parameters pa (B, K, Dz), pb (B, K), pc (B, K, Dz, Dz),
+        pd (B, K) and their log-partitions prior_logZ (B, K), all finite.  Resets the loop: every problem active, its trace
+        empty, its status clear.  An upload drops the priors."""
+        alpha0, pa, pb, pc, pd, plz = (_f64(v) for v in (alpha0, pa, pb, pc, pd, prior_logZ))
+        if alpha0.ndim != 2:
+            raise ValueError(f"alpha0 must be (B, K), got shape {alpha0.shape}")
+        B, K = alpha0.shape
+        if B != self.B:
+            raise ValueError(f"priors for {B} problems, {self.B} uploaded")
+        D = self.D
+        want = ((B, K), (B, K, D), (B, K), (B, K, D, D), (B, K), (B, K))
+        got = tuple(v.shape for v in (alpha0, pa, pb, pc, pd, plz))
+        if got != want:
+            raise ValueError(f"prior shapes {got} do not match B={B}, K={K}, Dz={D}: {want}")
+        if not all(np.all(np.isfinite(v)) for v in (alpha0, pa, pb, pc, pd, plz)):
+            raise ValueError("the priors must be finite")
+        self._check(self._lib.mimo_vi_prior_batched(self._ctx, K, _ptr(alpha0), _ptr(pa), _ptr(pb), _ptr(pc), _ptr(pd), _ptr(plz)))
+
+    def vi_run(self, K, iters, tol):
+        """`iters` mean-field iterations of every problem that is still active, on the device: conjugate update from the
+        statistics the last pass left resident, canonical form, batched pass, bound, stopping rule |vlb_t - vlb_{t-1}| < tol
+        (mimo_vi_run_batched).  Returns (trace (iters, B), NaN where a problem appended nothing; n_done (B,), the bounds
+        appended in this call; status (B,), bits: 1 for a problem one of whose blocks was not positive definite, 2 for one
+        whose canonical form or bound was not finite — such a problem keeps the state of its last complete iteration).  The
+        loop's passes are plain passes over all rows, whatever pass left the statistics it starts from.  The state persists
+        across calls: vi_run(6) and vi_run(2) followed by vi_run(4) give the same bits."""
+        K, iters, tol = int(K), int(iters), float(tol)
+        if K < 1 or iters < 1:
+            raise ValueError(f"K = {K} and iters = {iters} must be >= 1")
+        if not tol >= 0.:
+            raise ValueError(f"tol = {tol} must be >= 0")
+        trace = np.empty((iters, self.B))
+        n_done = np.empty(self.B, dtype=np.int32)
+        status = np.empty(self.B, dtype=np.int32)
+        self._check(self._lib.mimo_vi_run_batched(self._ctx, K, iters, tol, 0, _ptr(trace), _ptr(n_done), _ptr(status)))
+        return trace, n_done, status
+
+    def vi_state(self, K):
+        """The posterior blocks the loop holds, as a dict of arrays with a leading problem axis: alpha, qa, qb, qc, qd (the
+        natural parameters), mus, psis, nus, hld (standard parameters, half log det psi), cc, bb, W, E2, E4, e_log_pi,
+        c_total (the canonical form of the next pass is (c_total, bb, W)), vlb (B, 2) = the Dirichlet term and the summed
+        component terms of the bound — the parts of the host sweep (distributions/native_sweep.py)."""
+        K = int(K)
+        if K < 1:
+            raise ValueError(f"K = {K} must be >= 1")
+        shapes = self._vi_part_shapes(K)
+        sizes = [int(np.prod(s)) for s in shapes]
+        out = np.empty((self.B, sum(sizes)))
+        self._check(self._lib.mimo_vi_get_batched(self._ctx, K, _ptr(out)))
+        state, o = {}, 0
+        for name, shape, n in zip(self.VI_PARTS, shapes, sizes):
+            state[name] = out[:, o:o + n].reshape((self.B,) + shape).copy()
+            o += n
+        return state
+
+    def _vi_resident(self, K):
+        """Test hook: (the operand images the loop's passes read (B, ceil(K/16), F16/4, 64); the statistics the last pass left
+        resident as a list of B SuffStats; its scalars (B, 3))."""
+        K, D = int(K), self.D
+        ns = ((D + 1) * (D + 2) // 2 + 15) // 16 * 4
+        theta = np.empty((self.B, (K + 15) // 16, ns, 64))
+        stats = np.empty(self.B * K * (1 + D + D * D) + 3 * self.B)
+        self._check(self._lib.mimo_vi_get_theta_batched(self._ctx, K, _ptr(theta), _ptr(stats)))
+        S = stats[:self.B * K * (1 + D + D * D)].reshape(self.B, K, 1 + D + D * D)
+        return theta, [SuffStats.from_packed(S[i], K, D) for i in range(self.B)], stats[S.size:].reshape(self.B, 3).copy()
+
     def get_row_weights(self):
         """The resident row weights (the last weighted pass's, or those of outer_responsibilities): a list of B arrays (N_b,)."""
         out = np.empty(max(int(self.row_off[-1]), 1))

@@ -7,6 +7,7 @@
 #include "mimo_extra.h"
 #include "mimo_batched.h"
 #include "mimo_predict_batched.h"
+#include "mimo_vi_batched.h"
 #include "mimo_route.h"
 #include "mimo_theta.h"
 
@@ -152,6 +153,20 @@ struct mimo_ctx {
   bool batch_shared = false;
   Buf<double> batch_w;                                     // [row_off[B]] per-row weights of mimo_estep_batched_weighted / mimo_outer_resp_batched
   bool batch_w_valid = false;
+  // S_d holds the statistics [B][K][1 + Dz + Dz^2] of a batched pass with K = batch_stats_K, its 3 B scalars behind them: set by
+  // every batched pass that reduces statistics, cleared wherever the block is handed to something else (ensure_block)
+  bool batch_stats_valid = false;
+  int batch_stats_K = 0;
+  // device-resident batched VI (mimo_vi_batched.hip); the prior block, and with it the loop state, lives from mimo_vi_prior_batched
+  // to the next upload
+  bool vi_prior_valid = false;
+  int vi_K = 0;
+  Buf<double> vi_prior;                                    // [alpha0 B K | pa B K D | pb B K | pc B K D D | pd B K | log Z B K]
+  Buf<double> vi_post;                                     // [2][B][ViLayout::count()]
+  Buf<double> vi_work;                                     // [terms B K | prior terms B | last bound B]
+  Buf<double> vi_theta;                                    // [B][K16][F16 / 4][64]: the operand images the loop's passes read
+  Buf<double> vi_loop;                                     // [words: kViWords B int32, padded to doubles | trace of the last call]
+  Buf<double, true> vi_loop_h;                             // its pinned sibling
 
   void* comm = nullptr;         // RCCL communicator (mimo_comm_init): every pass then returns statistics summed over the ranks
   int comm_world = 1;
@@ -621,6 +636,7 @@ static int launch_route(mimo_ctx* ctx, KernelArgs& a, int src, const Route& rout
 
 // Room for a block of `len` doubles on the device and in its pinned host sibling
 static int ensure_block(mimo_ctx* ctx, size_t len) {
+  ctx->batch_stats_valid = false;      // whatever the caller puts there next, it says so itself
   const int rc = ctx->S_d.ensure(ctx, len);
   return rc ? rc : ctx->S_h.ensure(ctx, len);
 }
@@ -827,6 +843,8 @@ static int set_data(mimo_ctx* ctx, int64_t N, int Dz) {
   ctx->resp_valid = ctx->logp_valid = ctx->lse_valid = ctx->labels_valid = false;
   ctx->weights_resident = false;
   ctx->batch_w_valid = false;
+  ctx->batch_stats_valid = false;
+  ctx->vi_prior_valid = false;
   return prepare_features(ctx, Dz);
 }
 
@@ -1752,6 +1770,7 @@ static int batched_softmax_pass(mimo_ctx* ctx, const double* c, const double* b,
   const int split = (flags & (MIMO_F_ENTROPY_SPLIT | MIMO_F_KEEP_LSE)) ? 1 : 0;
   HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, D, F, F16, split,
                                      no_stats ? nullptr : ctx->S_d, sc_d, ctx->stream));
+  ctx->batch_stats_valid = !no_stats; ctx->batch_stats_K = K;
   return hand_out(ctx, out, no_stats ? nullptr : S, nstats, scalars, nstats, 3 * (size_t)B);
 }
 
@@ -1904,6 +1923,7 @@ int mimo_estep_batched_rows(mimo_ctx* ctx, const double* c, const double* b, con
   const int split = (flags & MIMO_F_ENTROPY_SPLIT) ? 1 : 0;
   HIP_TRY(ctx, launch_batched_reduce(ctx->partials, reinterpret_cast<const int32_t*>(ex + at_wg), B, ctx->feat_d, K, D, F, F16, split,
                                      no_stats ? nullptr : ctx->S_d, ctx->S_d + nstats, ctx->stream));
+  ctx->batch_stats_valid = !no_stats; ctx->batch_stats_K = K;
   return hand_out(ctx, out, no_stats ? nullptr : S, nstats, scalars, nstats, 3 * (size_t)B);
   });
 }
@@ -1917,6 +1937,7 @@ static int batched_label_stats_out(mimo_ctx* ctx, int K, double* S) {
   if ((rc = ensure_block(ctx, nstats + 3 * (size_t)B))) return rc;
   HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, D, ctx->F, ctx->F16, 0,
                                      ctx->S_d, ctx->S_d + nstats, ctx->stream));
+  ctx->batch_stats_valid = true; ctx->batch_stats_K = K;
   return hand_out(ctx, nstats, S, nstats, nullptr, 0, 0);
 }
 
@@ -2045,12 +2066,190 @@ int mimo_random_resp_stats_batched(mimo_ctx* ctx, int K, const uint64_t* seeds, 
 }
 
 // ------------------------------------------------------------------------------------------
+// Device-resident batched VI (mimo_vi_batched.hip)
+// ------------------------------------------------------------------------------------------
+// doubles the loop's int32 words take at the front of vi_loop
+static size_t vi_words_len(int B) { return ((size_t)kViWords * B + 1) / 2; }
+
+// What the three entry points share beyond batched_ready: a prior block of this K
+static int vi_ready(mimo_ctx* ctx, int K, const char* me) {
+  if (!ctx->vi_prior_valid || !ctx->vi_prior)
+    return fail(ctx, MIMO_E_STATE, "%s: no prior block is resident (call mimo_vi_prior_batched; an upload drops it)", me);
+  if (ctx->vi_K != K)
+    return fail(ctx, MIMO_E_STATE, "%s: the resident prior block is that of K = %d, not K = %d", me, ctx->vi_K, K);
+  return MIMO_OK;
+}
+
+static ViArgs vi_args(mimo_ctx* ctx, int K) {
+  const size_t B = (size_t)ctx->batch_B, BK = B * K, D = (size_t)ctx->D;
+  ViArgs a{};
+  a.S = ctx->S_d;
+  a.scalars = ctx->S_d + packed_len(K, ctx->D) * B;
+  const double* p = ctx->vi_prior;
+  a.alpha0 = p; p += BK;
+  a.pa = p; p += BK * D;
+  a.pb = p; p += BK;
+  a.pc = p; p += BK * D * D;
+  a.pd = p; p += BK;
+  a.plz = p;
+  a.post = ctx->vi_post;
+  a.term = ctx->vi_work;
+  a.prior_terms = ctx->vi_work + BK;
+  a.last = ctx->vi_work + BK + B;
+  a.words = reinterpret_cast<int32_t*>(ctx->vi_loop.p);
+  a.theta = ctx->vi_theta;
+  a.trace = ctx->vi_loop + vi_words_len(ctx->batch_B);
+  a.B = ctx->batch_B; a.K = K; a.D = ctx->D; a.K16 = (K + 15) / 16; a.NS = ctx->F16 / 4;
+  a.tol = 0.0;
+  return a;
+}
+
+int mimo_vi_prior_batched(mimo_ctx* ctx, int K, const double* alpha0, const double* pa, const double* pb, const double* pc,
+                          const double* pd, const double* prior_logZ) {
+  return guarded(ctx, [&]() -> int {
+  const char* const me = "mimo_vi_prior_batched";
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, me))) return rc;
+  if (!alpha0 || !pa || !pb || !pc || !pd || !prior_logZ)
+    return fail(ctx, MIMO_E_INVALID, "%s: alpha0, pa, pb, pc, pd and prior_logZ must be non-NULL", me);
+  const size_t B = (size_t)ctx->batch_B, BK = B * K, D = (size_t)ctx->D;
+  const double* const parts[6] = {alpha0, pa, pb, pc, pd, prior_logZ};
+  const char* const names[6] = {"alpha0", "pa", "pb", "pc", "pd", "prior_logZ"};
+  const size_t lens[6] = {BK, BK * D, BK, BK * D * D, BK, BK};
+  for (int t = 0; t < 6; ++t)
+    for (size_t i = 0; i < lens[t]; ++i)
+      if (!std::isfinite(parts[t][i]))
+        return fail(ctx, MIMO_E_INVALID, "%s: %s of problem %d holds a NaN or an infinity", me, names[t], (int)(i / (lens[t] / B)));
+  ctx->vi_prior_valid = false;
+  const ViLayout L{K, ctx->D};
+  const size_t nprior = BK * (4 + D + D * D), npost = 2 * B * (size_t)L.count(), nwork = BK + 2 * B;
+  const size_t ntheta = B * (size_t)((K + 15) / 16) * (ctx->F16 / 4) * 64, nwords = vi_words_len(ctx->batch_B);
+  if ((rc = ctx->vi_prior.ensure(ctx, nprior))) return rc;
+  if ((rc = ctx->vi_post.ensure(ctx, npost))) return rc;
+  if ((rc = ctx->vi_work.ensure(ctx, nwork))) return rc;
+  if ((rc = ctx->vi_theta.ensure(ctx, ntheta))) return rc;
+  if ((rc = ctx->vi_loop.ensure(ctx, nwords))) return rc;
+  // the loop state: every problem active, nothing appended, status clear, slot 0 current; zero blocks, zero images (the entries no
+  // kernel writes — padded features, the b / W entries of padding components — are the zeros pack_theta leaves there)
+  std::vector<int32_t> words((size_t)kViWords * B, 0);
+  std::fill(words.begin() + (size_t)kViActive * B, words.begin() + (size_t)(kViActive + 1) * B, 1);
+  double* q = ctx->vi_prior;
+  for (int t = 0; t < 6; ++t) {
+    HIP_TRY(ctx, hipMemcpyAsync(q, parts[t], lens[t] * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    q += lens[t];
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_loop, words.data(), words.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_post, 0, npost * sizeof(double), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_work, 0, nwork * sizeof(double), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_theta, 0, ntheta * sizeof(double), ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // the sources are pageable host memory
+  ctx->vi_prior_valid = true;
+  ctx->vi_K = K;
+  return MIMO_OK;
+  });
+}
+
+int mimo_vi_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status) {
+  return guarded(ctx, [&]() -> int {
+  const char* const me = "mimo_vi_run_batched";
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, me))) return rc;
+  if (flags != 0) return fail(ctx, MIMO_E_INVALID, "%s: flags 0x%x: none are defined", me, flags);
+  if (iters < 1 || iters > 65536) return fail(ctx, MIMO_E_INVALID, "%s: iters = %d outside [1, 65536]", me, iters);
+  if (!(tol >= 0.0)) return fail(ctx, MIMO_E_INVALID, "%s: tol = %g must be >= 0", me, tol);
+  if (!trace || !n_done || !status) return fail(ctx, MIMO_E_INVALID, "%s: trace, n_done and status must be non-NULL", me);
+  if ((rc = vi_ready(ctx, K, me))) return rc;
+  if (!ctx->batch_stats_valid || !ctx->S_d)
+    return fail(ctx, MIMO_E_STATE, "%s: no statistics are resident (run a batched pass that returns statistics first; an upload and "
+                "every call that returns something else drop them)", me);
+  if (ctx->batch_stats_K != K)
+    return fail(ctx, MIMO_E_STATE, "%s: the resident statistics are those of K = %d, not K = %d", me, ctx->batch_stats_K, K);
+  const int B = ctx->batch_B, D = ctx->D, G = ctx->batch_G;
+  const int F = ctx->F, F16 = ctx->F16, K16 = (K + 15) / 16;
+  const size_t nwords = vi_words_len(B), ntrace = (size_t)iters * B, total = nwords + ntrace;
+  if (ctx->vi_loop.cap < total) {          // a longer trace than any before: the words move to the new block
+    Buf<double> grown;
+    if ((rc = grown.ensure(ctx, total))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(grown.p, ctx->vi_loop.p, nwords * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::swap(grown.p, ctx->vi_loop.p);
+    std::swap(grown.cap, ctx->vi_loop.cap);
+  }
+  if ((rc = ctx->vi_loop_h.ensure(ctx, total))) return rc;
+  if ((rc = ctx->partials.ensure(ctx, partial_stride(K16, F16) * (size_t)std::max(G, 1)))) return rc;
+  ctx->resp_valid = ctx->logp_valid = ctx->labels_valid = ctx->lse_valid = false;
+
+  ViArgs va = vi_args(ctx, K);
+  va.tol = tol;
+  BatchedArgs a = batched_args(ctx, K);
+  a.theta = ctx->vi_theta;
+  const size_t nstats = packed_len(K, D) * (size_t)B;
+  HIP_TRY(ctx, hipMemsetAsync(va.words + (size_t)kViDone * B, 0, (size_t)B * sizeof(int32_t), ctx->stream));
+  for (int it = 0; it < iters; ++it) {
+    HIP_TRY(ctx, launch_vi_update(va, ctx->stream));
+    HIP_TRY(ctx, launch_vi_gating(va, ctx->stream));
+    HIP_TRY(ctx, launch_batched(a, G, ctx->stream));
+    HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, D, F, F16, 0, ctx->S_d, ctx->S_d + nstats,
+                                       ctx->stream));
+    HIP_TRY(ctx, launch_vi_finish(va, it, ctx->stream));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_loop_h, ctx->vi_loop, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const int32_t* words = reinterpret_cast<const int32_t*>(ctx->vi_loop_h.p);
+  memcpy(trace, ctx->vi_loop_h + nwords, ntrace * sizeof(double));
+  memcpy(n_done, words + (size_t)kViDone * B, (size_t)B * sizeof(int32_t));
+  memcpy(status, words + (size_t)kViStatus * B, (size_t)B * sizeof(int32_t));
+  return MIMO_OK;
+  });
+}
+
+int mimo_vi_get_batched(mimo_ctx* ctx, int K, double* out) {
+  return guarded(ctx, [&]() -> int {
+  const char* const me = "mimo_vi_get_batched";
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, me))) return rc;
+  if (!out) return fail(ctx, MIMO_E_INVALID, "%s: out is NULL", me);
+  if ((rc = vi_ready(ctx, K, me))) return rc;
+  const size_t B = (size_t)ctx->batch_B, per = (size_t)ViLayout{K, ctx->D}.count();
+  std::vector<double> both(2 * B * per);
+  std::vector<int32_t> words((size_t)kViWords * B);
+  HIP_TRY(ctx, hipMemcpyAsync(both.data(), ctx->vi_post, both.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(words.data(), ctx->vi_loop, words.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t p = 0; p < B; ++p) {
+    const size_t slot = words[(size_t)kViSlot * B + p] ? 1 : 0;
+    memcpy(out + p * per, both.data() + (slot * B + p) * per, per * sizeof(double));
+  }
+  return MIMO_OK;
+  });
+}
+
+int mimo_vi_get_theta_batched(mimo_ctx* ctx, int K, double* theta, double* stats) {
+  return guarded(ctx, [&]() -> int {
+  const char* const me = "mimo_vi_get_theta_batched";
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, me))) return rc;
+  if (!theta && !stats) return fail(ctx, MIMO_E_INVALID, "%s: theta and stats are both NULL", me);
+  if ((rc = vi_ready(ctx, K, me))) return rc;
+  if (stats && (!ctx->batch_stats_valid || ctx->batch_stats_K != K || !ctx->S_d))
+    return fail(ctx, MIMO_E_STATE, "%s: no statistics of K = %d are resident", me, K);
+  const size_t B = (size_t)ctx->batch_B, count = B * ((K + 15) / 16) * (ctx->F16 / 4) * 64;
+  if (theta) HIP_TRY(ctx, hipMemcpyAsync(theta, ctx->vi_theta, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (stats)
+    HIP_TRY(ctx, hipMemcpyAsync(stats, ctx->S_d, (packed_len(K, ctx->D) + 3) * B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return MIMO_OK;
+  });
+}
+
+// ------------------------------------------------------------------------------------------
 // Batched prediction (mimo_predict_batched.hip)
 // ------------------------------------------------------------------------------------------
 // The rows are an argument: nothing of the context's data, batch or kept tables is read or written.  Buffers: the parameter,
 // transform and row_off blocks go through the operand image's pinned staging buffer in ONE transfer (theta_h -> theta_d, restaged
 // by every pass); X and y go through the staged-weights workspace `win`, as mimo_predict_flags uses it (pure staging: nothing
-// resident lives there, so nothing is invalidated); the outputs are one block of S_d / S_h (ensure_block / hand_out).
+// resident lives there, so nothing is invalidated); the outputs are one block of S_d / S_h (ensure_block / hand_out), which drops
+// the resident statistics of a batched pass (batch_stats_valid: mimo_vi_run_batched then asks for a new pass).
 int mimo_predict_batched(mimo_ctx* ctx, int B, const double* X, const int64_t* row_off, int64_t N_shared, int dx,
                          const double* x_tf, const double* c, const double* b, const double* W, int K,
                          const double* M, const double* Q, const double* Cc, int dy, int mode,

@@ -1,0 +1,74 @@
+// Internal interface of the device-resident batched VI loop (mimo_vi_batched.hip): the conjugate update, the canonical form and
+// the prior terms of the bound of B mixtures of Gaussians (Dirichlet gating, untied Normal-Wishart components) between two
+// batched softmax passes, without a host round trip.  Not installed; the public surface is include/mimo_hip.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace mimo {
+
+// One problem's posterior block, in the part order of the host-native sweep's output block (distributions/native_sweep.py, untied):
+//   alpha K | qa KD | qb K | qc KDD | qd K | mus KD | psis KDD | nus K | hld K | cc K | bb KD | W KDD | E2 K | E4 K | E[log pi] K |
+//   c_total K | bound terms 2 (Dirichlet term, sum of the component terms)
+struct ViLayout {
+  int K, D;
+  __host__ __device__ int kd() const { return K * D; }
+  __host__ __device__ int kdd() const { return K * D * D; }
+  __host__ __device__ int alpha() const { return 0; }
+  __host__ __device__ int qa() const { return K; }
+  __host__ __device__ int qb() const { return qa() + kd(); }
+  __host__ __device__ int qc() const { return qb() + K; }
+  __host__ __device__ int qd() const { return qc() + kdd(); }
+  __host__ __device__ int mus() const { return qd() + K; }
+  __host__ __device__ int psis() const { return mus() + kd(); }
+  __host__ __device__ int nus() const { return psis() + kdd(); }
+  __host__ __device__ int hld() const { return nus() + K; }
+  __host__ __device__ int cc() const { return hld() + K; }
+  __host__ __device__ int bb() const { return cc() + K; }
+  __host__ __device__ int W() const { return bb() + kd(); }
+  __host__ __device__ int E2() const { return W() + kdd(); }
+  __host__ __device__ int E4() const { return E2() + K; }
+  __host__ __device__ int elp() const { return E4() + K; }
+  __host__ __device__ int c_total() const { return elp() + K; }
+  __host__ __device__ int vlb() const { return c_total() + K; }
+  __host__ __device__ int count() const { return vlb() + 2; }
+};
+
+// The loop's per-problem words, one int32 row of B each: [active | status | appended in all | appended in this call | current slot]
+enum ViWord : int { kViActive = 0, kViStatus = 1, kViTotal = 2, kViDone = 3, kViSlot = 4, kViWords = 5 };
+// status bits
+constexpr int kViNotPosDef = 1;      // a component's posterior block C = c - kappa m m' is not positive definite
+constexpr int kViNotFinite = 2;      // a canonical form (c, b, W), a term of the bound or the bound itself is not finite
+
+struct ViArgs {
+  const double* S;            // [B][K][1 + D + D^2]: the resident statistics block (launch_batched_reduce)
+  const double* scalars;      // [B][3]: the scalars of the same reduction
+  // the priors' natural parameters and log-partitions
+  const double* alpha0;       // [B][K]
+  const double* pa;           // [B][K][D]
+  const double* pb;           // [B][K]
+  const double* pc;           // [B][K][D][D]
+  const double* pd;           // [B][K]
+  const double* plz;          // [B][K]
+  double* post;               // [2][B][ViLayout::count()]: two slots per problem; words[kViSlot][b] names the current one.  An
+                              // iteration writes the other slot and the gating kernel makes it current once the whole problem is done,
+                              // so a problem that fails keeps the block it had
+  double* term;               // [B][K]: the components' terms of the bound (update kernel -> gating kernel)
+  double* prior_terms;        // [B]: Dirichlet term + sum of the component terms (gating kernel -> finish kernel)
+  double* last;               // [B]: the bound appended last
+  int32_t* words;             // [kViWords][B]
+  double* theta;              // [B][K16][NS][64]: the operand images the batched pass reads (ThetaGeneric, identity order)
+  double* trace;              // [iters][B] of this call
+  int B, K, D, K16, NS;
+  double tol;
+};
+
+// update: one wave per (problem, component); gating: one wave per problem.  Both return at once for a problem that is not active
+// or whose status word is set.
+hipError_t launch_vi_update(const ViArgs& a, hipStream_t stream);
+hipError_t launch_vi_gating(const ViArgs& a, hipStream_t stream);
+// finish (behind the pass and its reduction), iteration `it` of this call: trace[it][b] = prior_terms[b] + scalars[b][0] for an
+// active problem (NaN otherwise), and active[b] = 0 once two consecutive bounds are closer than tol.
+hipError_t launch_vi_finish(const ViArgs& a, int it, hipStream_t stream);
+
+}  // namespace mimo

@@ -98,16 +98,95 @@ def _random_start(engine, K, init_rng, seeds):
     return engine.weighted_stats(tables)
 
 
+def _resident_reason(model, sample_likelihood):
+    """Why the device-resident loop does not take this model (None: it does) — the family gmm_vi_sweep covers with untied
+    blocks: a mixture of Gaussians, Dirichlet gating, full Normal-Wishart components."""
+    from mimo_amd.distributions.bayesian import CategoricalWithDirichlet, StackedGaussiansWithNormalWisharts
+    from mimo_amd.distributions.composite import StackedNormalWisharts
+    from mimo_amd.distributions.gating import Dirichlet
+    if sample_likelihood:
+        return "sample_likelihood=True (the loop makes no per-iteration likelihood draws)"
+    if type(model) is not BayesianMixtureOfGaussians:
+        return f"{type(model).__name__} is not a BayesianMixtureOfGaussians"
+    gating, comps = model.gating, model.components
+    if type(gating) is not CategoricalWithDirichlet or type(gating.prior) is not Dirichlet\
+            or type(gating.posterior) is not Dirichlet:
+        return "the gating is not a CategoricalWithDirichlet with Dirichlet prior and posterior"
+    if type(comps) is not StackedGaussiansWithNormalWisharts:
+        return f"the components are {type(comps).__name__} (tied or other blocks), not StackedGaussiansWithNormalWisharts"
+    if type(comps.prior) is not StackedNormalWisharts or type(comps.posterior) is not StackedNormalWisharts:
+        return "the components' prior and posterior are not StackedNormalWisharts"
+    if model._structure() != 'full':
+        return f"the structure is {model._structure()!r}, not 'full'"
+    return None
+
+
+def _resident_descent(models, engine, maxiter, tol, chunk):
+    """The loop of meanfield_coordinate_descent_batched(resident=True) behind the start: the statistics of the start lie on the
+    device; priors up once, vi_run in chunks, state back once."""
+    from mimo_amd.utils.abstraction import Statistics as Stats
+    B, K = len(models), models[0].size
+    maxiter, chunk = int(maxiter), int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk = {chunk} < 1")
+    vlbs = [[] for _ in range(B)]
+    if maxiter <= 0:
+        return vlbs
+    blocks = [_native_sweep._prior_block(m.components.prior) for m in models]
+    engine.vi_set_prior(np.stack([np.asarray(m.gating.prior.alphas, dtype=float) for m in models]),
+                        *(np.stack([blk[j] for blk in blocks]) for j in range(5)))
+    left, stopped = maxiter, np.zeros(B, dtype=bool)
+    while left > 0 and not stopped.all():
+        n = min(chunk, left)
+        trace, n_done, status = engine.vi_run(K, n, tol)
+        left -= n
+        for i in np.flatnonzero(status):
+            if status[i] & 1:
+                raise np.linalg.LinAlgError(f"problem {int(i)}: Matrix is not positive definite (a component's block "
+                                            "c - kappa m m' of its posterior)")
+            raise FloatingPointError(f"problem {int(i)}: the canonical form or the bound of its posterior is not finite")
+        for i in range(B):
+            vlbs[i].extend(float(v) for v in trace[:int(n_done[i]), i])
+            # (the device's own rule, on the same doubles: a problem that stopped at a chunk's last iteration is seen here)
+            stopped[i] = n_done[i] < n or (len(vlbs[i]) > 1 and abs(vlbs[i][-1] - vlbs[i][-2]) < tol)
+    state = engine.vi_state(K)
+    part = lambda name, i: np.ascontiguousarray(state[name][i])
+    for i, m in enumerate(models):
+        if not vlbs[i]:
+            continue
+        post = m.components.posterior
+        qb, nus, bb, W = part('qb', i), part('nus', i), part('bb', i), part('W', i)
+        m.gating.posterior.alphas = part('alpha', i)
+        post.params = (part('mus', i), qb, part('psis', i), nus)
+        post._set_memo(nat=Stats([part('qa', i), qb, part('qc', i), part('qd', i)]), hld=part('hld', i),
+                       estats=(bb, part('E2', i), - 0.5 * W, part('E4', i)), canon=(part('cc', i), bb, W), native=True)
+        m._refresh_likelihoods()
+    return vlbs
+
+
 def meanfield_coordinate_descent_batched(models, data, randomize=True, maxiter=250, tol=1e-8, init_rng='host', seeds=None,
-                                         sample_likelihood=True, engine=None):
+                                         sample_likelihood=True, engine=None, resident=False, chunk=8):
     """models: B BayesianMixtureOfGaussians with data a list of B `obs`, or B BayesianMixtureOfLinearGaussians with data a
     list of B `(x, y)`; one class, one size and one set of dimensions for all.  randomize / init_rng / seeds[i] /
     sample_likelihood as in the solo drivers (the random start is one batched table pass: the host draws are made in
     model order).  engine: a
-    BatchedHipEngine (default: a new one on the device of the first model's engine).  Returns the B ELBO traces."""
+    BatchedHipEngine (default: a new one on the device of the first model's engine).  Returns the B ELBO traces.
+
+    resident=True: everything between two passes runs on the device (BatchedHipEngine.vi_run): the conjugate update, the
+    canonical form, the prior terms of the bound and the stopping rule, `chunk` iterations per call; the posteriors come
+    back once, at the end, and are written into the models as the host-native sweep writes them (then one
+    _refresh_likelihoods() per model).  Only mixtures of Gaussians with a Dirichlet gating and untied Normal-Wishart
+    components, and only sample_likelihood=False; anything else raises ValueError naming the reason.  A problem one of whose
+    blocks is not positive definite raises numpy.linalg.LinAlgError naming the problem, as the NumPy route does; one whose
+    canonical form or bound is not finite raises FloatingPointError naming the problem."""
     models, data, cls = _check_models(models, data)
     B = len(models)
     seeds = _per_model(seeds, B, 0, "seeds")
+    if resident:
+        for i, m in enumerate(models):
+            why = _resident_reason(m, sample_likelihood)
+            if why is not None:
+                raise ValueError(f"resident=True does not cover model {i}: {why}")
     if engine is None:
         engine = BatchedHipEngine(getattr(models[0].engine, 'device', 0))
     engine.upload([_rows(m, d) for m, d in zip(models, data)])
@@ -117,6 +196,8 @@ def meanfield_coordinate_descent_batched(models, data, randomize=True, maxiter=2
     else:
         canons = [m.canonical_expected() for m in models]
         S, _ = engine.estep(*_stack(canons))
+    if resident:
+        return _resident_descent(models, engine, maxiter, tol, chunk)
     canons = [None] * B
     vlbs = [[] for _ in range(B)]
     active = list(range(B))

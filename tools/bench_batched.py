@@ -2,7 +2,7 @@
 data resident), on the same inputs, after warm-up; wall time per pass (each call returns synchronised host results) and the
 largest relative difference of the outputs.  Writes <out>/bench_batched.json.
 
-    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3] [--start-only | --no-start | --svi | --predict]
+    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3] [--start-only | --no-start | --svi | --predict | --nested | --resident]
 
 Also times one iteration of meanfield_coordinate_descent_batched against B solo meanfield_iteration calls at shape 1
 (24 ILR models, K = 100, dx = dy = 1), split into host time and pass time.
@@ -36,6 +36,16 @@ Nested leg (--nested, on its own; writes <out>/bench_batched_nested.json): wall 
 meanfield_coordinate_descent_nested (one shared batch of M inner mixtures) against the solo
 BayesianMixtureOfMixtureOfGaussians.meanfield_coordinate_descent, same seeds, the legs alternated in one run.  Nested
 shapes (--shapes 1,2): 1. M = 4, K = 4, Dz = 2, N = 400 (the scale of the reference's examples/hgmm); 2. the same at N = 1e5.
+
+Resident leg (--resident, on its own; writes <out>/batched_resident_vi.json): wall time per iteration of the device-resident
+loop, meanfield_coordinate_descent_batched(resident=True), against the host route (resident=False, sample_likelihood=False) on the
+same models and the same Philox start, the two alternated in one run after warm-up: per repetition fresh models run 1 and
+1 + iters iterations on each route, each run clocked from the return of the start pass (the upload — 192 MB at shape 3 — and the
+start are outside the clock), the difference / iters is the repetition's figure, the median is reported (what a run does once
+— priors up, state back, the write-back into the models — cancels).  The host route's iteration is split into its passes and everything else.  Also the largest relative difference of the
+traces, and the device / host error ratios of one update on tests/golden/vi_update_hp.npz (tests/vi_update_fixture.py).
+Resident shapes (--shapes 1,2,3): 1. shape 2 (B = 64, N_b = 1e4, Dz = 2, K = 4); 2. a GMM at the size of shape 1 (B = 24,
+N_b = 1600, Dz = 2, K = 100); 3. shape 3 as GMM (B = 8, N_b = 2.5e5, Dz = 12, K = 64).
 
 Shapes: 1. B = 24, N_b = 1600, Dz = 2, K = 100 (the reference's parallel ILR example); 2. B = 64, N_b = 1e4, Dz = 2, K = 4
 (restarts of the toy GMM); 3. B = 8, N_b = 2.5e5, Dz = 12, K = 64 (C4 per model)."""
@@ -621,6 +631,112 @@ def run_nested_shape(sid, reps, iters=10):
     return res
 
 
+RESIDENT_SHAPES = {1: (64, 10000, 2, 4), 2: (24, 1600, 2, 100), 3: (8, 250000, 12, 64)}      # (B, N_b, Dz, K)
+
+
+def gmm_models(B, N, D, K, engine, seed):
+    """B mixtures of Gaussians (Dirichlet gating, untied Normal-Wishart components) on clustered data -> (build, data)."""
+    from mimo_amd.distributions import Dirichlet, CategoricalWithDirichlet, StackedNormalWisharts, StackedGaussiansWithNormalWisharts
+    from mimo_amd.mixtures import BayesianMixtureOfGaussians
+    rng = np.random.default_rng(seed)
+    data = []
+    for _ in range(B):
+        centres = rng.standard_normal((K, D)) * 4.0
+        data.append(np.ascontiguousarray(centres[rng.integers(K, size=N)] + rng.standard_normal((N, D))))
+
+    def build():
+        models = []
+        for _ in range(B):
+            gating = CategoricalWithDirichlet(dim=K, prior=Dirichlet(dim=K, alphas=np.ones(K)))
+            prior = StackedNormalWisharts(K, D, np.zeros((K, D)), 1e-2 * np.ones(K), np.stack(K * [np.eye(D)]), (D + 2.) * np.ones(K))
+            comps = StackedGaussiansWithNormalWisharts(size=K, dim=D, prior=prior, engine=engine)
+            models.append(BayesianMixtureOfGaussians(gating=gating, components=comps, engine=engine))
+        return models
+    return build, data
+
+
+class _StartClock:
+    """BatchedHipEngine that stamps the return of the start pass: a driver run is clocked from there."""
+
+    def __init__(self, eng):
+        self.eng, self.t0 = eng, None
+
+    def random_resp_stats(self, *a, **k):
+        out = self.eng.random_resp_stats(*a, **k)
+        self.t0 = time.perf_counter()
+        return out
+
+    def __getattr__(self, name):
+        return getattr(self.eng, name)
+
+
+def run_resident_shape(sid, reps, iters=10):
+    from mimo_amd.mixtures.batched import meanfield_coordinate_descent_batched
+    B, N, D, K = RESIDENT_SHAPES[sid]
+    solo_engine, beng = HipEngine(0), BatchedHipEngine(0)
+    build, data = gmm_models(B, N, D, K, solo_engine, 300 + sid)
+    kw = dict(randomize=True, init_rng='philox', seeds=list(range(B)), tol=0., sample_likelihood=False)
+
+    def leg(resident, engine=beng):
+        def run(n, out=None):
+            models = build()
+            clock = _StartClock(engine)
+            vlbs = meanfield_coordinate_descent_batched(models, data, maxiter=n, engine=clock, resident=resident, chunk=8, **kw)
+            dt = time.perf_counter() - clock.t0
+            if out is not None:
+                out.append(vlbs)
+            return dt
+        return run
+    legs = {"host": leg(False), "resident": leg(True)}
+    kept = {name: [] for name in legs}
+    for name, fn in legs.items():                        # warm-up, and the traces that are compared
+        fn(1)
+        fn(1 + iters, kept[name])
+    per = {name: [] for name in legs}
+    for _ in range(reps):                                # the legs alternate within a repetition
+        for name, fn in legs.items():
+            per[name].append((fn(1 + iters) - fn(1)) / iters)
+    h, r = np.array(kept["host"][0]), np.array(kept["resident"][0])
+    res = {"resident_shape": sid, "B": B, "N_b": N, "Dz": D, "K": K, "iters_per_figure": iters, "reps": reps, "chunk": 8,
+           "max_rel_trace_diff": float(np.max(np.abs(r - h) / np.abs(h)))}
+    for name in legs:
+        res[name + "_ms_per_iteration"] = float(np.median(per[name])) * 1e3
+    res["speedup"] = res["host_ms_per_iteration"] / res["resident_ms_per_iteration"]
+    # the host route's iteration: its passes (each returns synchronised host results) against everything else
+    teng = _TimedEngine(beng)
+    t0 = time.perf_counter()
+    leg(False, teng)(1 + iters)
+    total = time.perf_counter() - t0 - teng.upload_s
+    res["host_route_pass_ms_per_iteration"] = float(np.sum(teng.pass_s)) / (1 + iters) * 1e3
+    res["host_route_host_ms_per_iteration_with_start"] = (total - float(np.sum(teng.pass_s))) / (1 + iters) * 1e3
+    solo_engine.close()
+    beng.close()
+    return res
+
+
+def resident_error_ratios():
+    """One device update on every shape of tests/golden/vi_update_hp.npz: per shape and output block the largest error of the
+    device and of the host-native route against the 50-digit values, and their ratio."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import vi_update_fixture as fx
+    beng = BatchedHipEngine(0)
+    out = []
+    for shape in fx.shapes():
+        beng.upload(shape["rows"])
+        beng.weighted_stats(shape["tables"])
+        beng.vi_set_prior(**shape["prior"])
+        beng.vi_run(shape["K"], 1, 0.)
+        dev, host = fx.block_errors(beng.vi_state(shape["K"]), shape), fx.block_errors(fx.host_state(shape), shape)
+        blocks = {}
+        for name in fx.BLOCKS:
+            d, h = float(dev[name].max()), float(host[name].max())
+            blocks[name] = {"device": d, "host": h, "ratio": (d / h) if h > 0. else (1.0 if d == 0. else None)}
+        out.append({"B": shape["B"], "Dz": shape["D"], "K": shape["K"], "blocks": blocks,
+                    "worst_ratio": max(v["ratio"] for v in blocks.values() if v["ratio"] is not None)})
+    beng.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
@@ -636,7 +752,18 @@ def main():
     ap.add_argument("--predict", action="store_true", help="only the prediction leg (batched predict against B solo predicts)")
     ap.add_argument("--trace-predict", type=int, default=0, metavar="SHAPE", help="only run the batched and the solo predictions of SHAPE")
     ap.add_argument("--nested", action="store_true", help="only the nested leg (nested VI driver against the solo mixture of mixtures)")
+    ap.add_argument("--resident", action="store_true", help="only the resident leg (device-resident VI loop against the host route)")
     args = ap.parse_args()
+    if args.resident:
+        os.makedirs(args.out, exist_ok=True)
+        res = {"timings": [run_resident_shape(int(s), args.reps) for s in args.shapes.split(",") if int(s) in RESIDENT_SHAPES],
+               "update_error_vs_50_digits": resident_error_ratios()}
+        for r in res["timings"]:
+            print(json.dumps(r))
+        print(json.dumps([{k: e[k] for k in ("B", "Dz", "K", "worst_ratio")} for e in res["update_error_vs_50_digits"]]))
+        with open(os.path.join(args.out, "batched_resident_vi.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if args.nested:
         os.makedirs(args.out, exist_ok=True)
         res = [run_nested_shape(int(s), args.reps) for s in args.shapes.split(",") if int(s) in NESTED_SHAPES]

@@ -87,6 +87,29 @@ class BatchedHipEngine:
         self.B, self.D, self.row_off = B, int(D), np.arange(B + 1, dtype=np.int64) * int(N)
         self.shared = True
 
+    def _stats_block(self, K):
+        """The packed statistics block a pass fills: (B, K, 1 + Dz + Dz^2)."""
+        return np.empty((self.B, K, 1 + self.D + self.D * self.D))
+
+    def _stats_list(self, S, K):
+        return [SuffStats.from_packed(S[i], K, self.D) for i in range(self.B)]
+
+    def _per_problem(self, parts, count_msg, convert, each, dtype=np.float64, before=None):
+        """A list of B per-problem arrays -> (the converted parts, their flattened concatenation as `dtype`: one zero for a
+        batch without entries).  count_msg(n): the text when n != B parts came; convert: applied to every part;
+        before(parts): the caller's checks across the converted parts; each(i, part, N_i): its checks of problem i's part
+        against the problem's row count.  Raises ValueError before any library call."""
+        parts = list(parts)
+        if len(parts) != self.B:
+            raise ValueError(count_msg(len(parts)))
+        parts = [convert(p) for p in parts]
+        if before is not None:
+            before(parts)
+        for i, p in enumerate(parts):
+            each(i, p, int(self.row_off[i + 1] - self.row_off[i]))
+        flat = np.concatenate([p.reshape(-1) for p in parts]) if sum(p.size for p in parts) else np.zeros(1, dtype=dtype)
+        return parts, np.ascontiguousarray(flat, dtype=dtype)
+
     def _row_weights(self, row_weights):
         """A list of B arrays (N_b,), or one (B, N) array on a shared batch -> the concatenated weights; raises ValueError
         before any library call."""
@@ -98,15 +121,11 @@ class BatchedHipEngine:
                 raise ValueError(f"row_weights must be (B, N) = ({self.B}, {int(self.row_off[1])}), got shape {w.shape}")
             flat = w.reshape(-1)
         else:
-            parts = list(row_weights)
-            if len(parts) != self.B:
-                raise ValueError(f"row weights for {len(parts)} problems, {self.B} uploaded")
-            parts = [_f64(p).reshape(-1) for p in parts]
-            for i, p in enumerate(parts):
-                if p.shape[0] != self.row_off[i + 1] - self.row_off[i]:
-                    raise ValueError(f"row_weights of problem {i} must hold one weight per datum "
-                                     f"({int(self.row_off[i + 1] - self.row_off[i])}), got {p.shape[0]}")
-            flat = np.concatenate(parts) if self.row_off[-1] > 0 else np.zeros(1)
+            def each(i, p, n):
+                if p.shape[0] != n:
+                    raise ValueError(f"row_weights of problem {i} must hold one weight per datum ({n}), got {p.shape[0]}")
+            _, flat = self._per_problem(row_weights, lambda n: f"row weights for {n} problems, {self.B} uploaded",
+                                        lambda p: _f64(p).reshape(-1), each)
         if not np.all(np.isfinite(flat)) or np.any(flat < 0.):
             raise ValueError("row_weights must be finite and >= 0")
         return np.ascontiguousarray(flat)
@@ -124,22 +143,18 @@ class BatchedHipEngine:
 
     def _selection(self, rows):
         """B integer index arrays -> (the concatenated int64 indices, sel_off); raises ValueError before any library call."""
-        rows = list(rows)
-        if len(rows) != self.B:
-            raise ValueError(f"row selections for {len(rows)} problems, {self.B} uploaded")
-        rows = [np.asarray(r) for r in rows]
-        for i, r in enumerate(rows):
+        def each(i, r, n):
             if r.ndim != 1:
                 raise ValueError(f"the row selection of problem {i} must be one-dimensional, got shape {r.shape}")
             if r.dtype.kind not in 'iu':
                 raise ValueError(f"the row selection of problem {i} must hold integers, got dtype {r.dtype}")
-            n = int(self.row_off[i + 1] - self.row_off[i])
             if r.size and (int(r.min()) < 0 or int(r.max()) >= n):
                 raise ValueError(f"the row selection of problem {i} holds an index outside [0, {n})")
+        rows, flat = self._per_problem(rows, lambda n: f"row selections for {n} problems, {self.B} uploaded", np.asarray, each,
+                                       dtype=np.int64)
         sel_off = np.zeros(self.B + 1, dtype=np.int64)
         sel_off[1:] = np.cumsum([r.size for r in rows])
-        flat = np.concatenate(rows).astype(np.int64, copy=False) if sel_off[-1] > 0 else np.zeros(1, dtype=np.int64)
-        return np.ascontiguousarray(flat), sel_off
+        return flat, sel_off
 
     def estep(self, c, b, W, stats=True, keep_lse=False, entropy_split=False, rows=None, row_weights=None):
         """One pass over all problems.  c (B, K), b (B, K, Dz), W (B, K, Dz, Dz).  Returns (list of B SuffStats, or None
@@ -169,8 +184,7 @@ class BatchedHipEngine:
         c, b, W, K = self._params(c, b, W)
         flags = ((0 if stats else _lib.F_NO_STATS) | (_lib.F_KEEP_LSE if keep_lse else 0)
                  | (_lib.F_ENTROPY_SPLIT if entropy_split else 0))
-        D = self.D
-        S = np.empty((self.B, K, 1 + D + D * D)) if stats else None
+        S = self._stats_block(K) if stats else None
         sc = np.empty((self.B, 3))
         if rows is not None:
             self._check(self._lib.mimo_estep_batched_rows(self._ctx, _ptr(c), _ptr(b), _ptr(W), K, _ptr(sel), _ptr(sel_off),
@@ -182,7 +196,7 @@ class BatchedHipEngine:
         else:
             self._check(self._lib.mimo_estep_batched(self._ctx, _ptr(c), _ptr(b), _ptr(W), K, flags,
                                                      _ptr(S) if stats else None, _ptr(sc)))
-        return ([SuffStats.from_packed(S[i], K, D) for i in range(self.B)] if stats else None), sc
+        return (self._stats_list(S, K) if stats else None), sc
 
     def _split(self, a):
         return [a[self.row_off[i]:self.row_off[i + 1]].copy() for i in range(self.B)]
@@ -193,14 +207,11 @@ class BatchedHipEngine:
         of uniforms, (N_b,) or (1, N_b) each.  Returns (list of B int32 arrays | None, list of B SuffStats | None)."""
         c, b, W, K = self._params(c, b, W)
         if u is not None:
-            u = list(u)
-            if len(u) != self.B:
-                raise ValueError(f"uniforms for {len(u)} problems, {self.B} uploaded")
-            u = [_f64(ui).reshape(-1) for ui in u]
-            for i, ui in enumerate(u):
-                if ui.shape[0] != self.row_off[i + 1] - self.row_off[i]:
+            def each(i, ui, n):
+                if ui.shape[0] != n:
                     raise ValueError("u must hold one uniform per datum")
-            u = np.ascontiguousarray(np.concatenate(u)) if self.row_off[-1] > 0 else np.zeros(1)
+            _, u = self._per_problem(u, lambda n: f"uniforms for {n} problems, {self.B} uploaded",
+                                     lambda ui: _f64(ui).reshape(-1), each)
             sd = None
         else:
             if seeds is None:
@@ -208,15 +219,14 @@ class BatchedHipEngine:
             sd = np.ascontiguousarray(np.asarray(seeds).reshape(-1).astype(np.uint64))
             if sd.shape[0] != self.B:
                 raise ValueError(f"{sd.shape[0]} seeds for {self.B} problems")
-        D = self.D
-        S = np.empty((self.B, K, 1 + D + D * D)) if stats else None
+        S = self._stats_block(K) if stats else None
         labels = np.empty(max(int(self.row_off[-1]), 1), dtype=np.int32) if return_labels else None
         self._check(self._lib.mimo_gibbs_labels_batched(
             self._ctx, _ptr(c), _ptr(b), _ptr(W), K, _ptr(sd) if sd is not None else None, int(sweep),
             _ptr(u) if u is not None else None, 0 if stats else _lib.F_NO_STATS,
             _ptr(labels) if return_labels else None, _ptr(S) if stats else None))
         return ((self._split(labels) if return_labels else None),
-                ([SuffStats.from_packed(S[i], K, D) for i in range(self.B)] if stats else None))
+                (self._stats_list(S, K) if stats else None))
 
     def label_stats(self, labels, K):
         """Statistics of hard labels: a list of B int32 arrays (N_b,), or None for the labels of the last gibbs_labels.
@@ -225,41 +235,33 @@ class BatchedHipEngine:
         if labels is None:
             p = None
         else:
-            labels = list(labels)
-            if len(labels) != self.B:
-                raise ValueError(f"labels for {len(labels)} problems, {self.B} uploaded")
-            labels = [np.asarray(z).reshape(-1) for z in labels]
-            for i, z in enumerate(labels):
-                if z.shape[0] != self.row_off[i + 1] - self.row_off[i]:
+            def each(i, z, n):
+                if z.shape[0] != n:
                     raise ValueError("labels must hold one entry per datum")
                 if z.size and (z.min() < 0 or z.max() >= K):
                     raise ValueError("labels out of range")  # mirrors the assert in one_hot (data.py:162)
-            labels = (np.ascontiguousarray(np.concatenate(labels), dtype=np.int32) if self.row_off[-1] > 0
-                      else np.zeros(1, dtype=np.int32))
+            _, labels = self._per_problem(labels, lambda n: f"labels for {n} problems, {self.B} uploaded",
+                                          lambda z: np.asarray(z).reshape(-1), each, dtype=np.int32)
             p = _ptr(labels)
-        D = self.D
-        S = np.empty((self.B, K, 1 + D + D * D))
+        S = self._stats_block(K)
         self._check(self._lib.mimo_label_stats_batched(self._ctx, p, K, 0, _ptr(S)))
-        return [SuffStats.from_packed(S[i], K, D) for i in range(self.B)]
+        return self._stats_list(S, K)
 
     def _tables(self, tables):
         """B (K, N_b) weight tables -> (the concatenated K-major blocks, K); raises ValueError before any library call."""
-        tables = list(tables)
-        if len(tables) != self.B:
-            raise ValueError(f"tables for {len(tables)} problems, {self.B} uploaded")
-        if not tables:
-            raise ValueError("no batch is uploaded")
-        tables = [_f64(t) for t in tables]
-        if any(t.ndim != 2 for t in tables):
-            raise ValueError("every problem's weights must be (K, N_b)")
-        K = tables[0].shape[0]
-        if any(t.shape[0] != K for t in tables):
-            raise ValueError(f"the problems' tables differ in K: {[t.shape[0] for t in tables]}")
-        for i, t in enumerate(tables):
-            if t.shape[1] != self.row_off[i + 1] - self.row_off[i]:
+        def before(tables):
+            if not tables:
+                raise ValueError("no batch is uploaded")
+            if any(t.ndim != 2 for t in tables):
+                raise ValueError("every problem's weights must be (K, N_b)")
+            if any(t.shape[0] != tables[0].shape[0] for t in tables):
+                raise ValueError(f"the problems' tables differ in K: {[t.shape[0] for t in tables]}")
+
+        def each(i, t, n):
+            if t.shape[1] != n:
                 raise ValueError("weights must be (K, N_b): one column per datum")
-        flat = np.concatenate([t.reshape(-1) for t in tables])
-        return (np.ascontiguousarray(flat) if flat.size else np.zeros(1)), int(K)
+        tables, flat = self._per_problem(tables, lambda n: f"tables for {n} problems, {self.B} uploaded", _f64, each, before=before)
+        return flat, int(tables[0].shape[0])
 
     def weighted_stats(self, tables=None, K=None):
         """Statistics of arbitrary weights: a list of B arrays (K, N_b), one K for all problems (taken as they are), or
@@ -272,10 +274,9 @@ class BatchedHipEngine:
         else:
             flat, K = self._tables(tables)
             p = _ptr(flat)
-        D = self.D
-        S = np.empty((self.B, K, 1 + D + D * D))
+        S = self._stats_block(K)
         self._check(self._lib.mimo_weighted_stats_batched(self._ctx, p, K, 0, _ptr(S)))
-        return [SuffStats.from_packed(S[i], K, D) for i in range(self.B)]
+        return self._stats_list(S, K)
 
     def random_resp_stats(self, K, seeds):
         """Statistics of random initial responsibilities drawn on the device, all problems in one launch: per problem what
@@ -285,11 +286,10 @@ class BatchedHipEngine:
         sd = np.ascontiguousarray(np.asarray(seeds).reshape(-1).astype(np.uint64))
         if sd.shape[0] != self.B:
             raise ValueError(f"{sd.shape[0]} seeds for {self.B} problems")
-        D = self.D
-        S = np.empty((self.B, K, 1 + D + D * D))
+        S = self._stats_block(K)
         self._check(self._lib.mimo_random_resp_stats_batched(self._ctx, K, _ptr(sd), 0, _ptr(S)))
         self._K = K
-        return [SuffStats.from_packed(S[i], K, D) for i in range(self.B)]
+        return self._stats_list(S, K)
 
     @staticmethod
     def _rows_form(a, B, d, what):
@@ -487,7 +487,7 @@ class BatchedHipEngine:
         stats = np.empty(self.B * K * (1 + D + D * D) + 3 * self.B)
         self._check(self._lib.mimo_vi_get_theta_batched(self._ctx, K, _ptr(theta), _ptr(stats)))
         S = stats[:self.B * K * (1 + D + D * D)].reshape(self.B, K, 1 + D + D * D)
-        return theta, [SuffStats.from_packed(S[i], K, D) for i in range(self.B)], stats[S.size:].reshape(self.B, 3).copy()
+        return theta, self._stats_list(S, K), stats[S.size:].reshape(self.B, 3).copy()
 
     def get_row_weights(self):
         """The resident row weights (the last weighted pass's, or those of outer_responsibilities): a list of B arrays (N_b,)."""
@@ -515,4 +515,4 @@ class BatchedHipEngine:
         """Per-problem log-normalisers of the last pass with keep_lse: a list of B arrays (N_b,)."""
         out = np.empty(max(int(self.row_off[-1]), 1))
         self._check(self._lib.mimo_get_lse(self._ctx, _ptr(out)))
-        return [out[self.row_off[i]:self.row_off[i + 1]].copy() for i in range(self.B)]
+        return self._split(out)

@@ -2,14 +2,11 @@
 // call sites each entry point replaces).  Host-side work here is O(K D^2): converting the
 // canonical (c, b, W) parameters to the feature-space MFMA operand image, and launching /
 // sequencing the gfx950 kernels of mimo_kernels.hip on the context's stream.
-#include "../../include/mimo_hip.h"
+// The batched entry points live in mimo_abi_batched.cpp; what the two files share is mimo_abi_internal.h.
+#include "mimo_abi_internal.h"
 #include "mimo_kernels.h"
 #include "mimo_extra.h"
-#include "mimo_batched.h"
-#include "mimo_predict_batched.h"
-#include "mimo_vi_batched.h"
 #include "mimo_route.h"
-#include "mimo_theta.h"
 
 #include <algorithm>
 #include <cmath>
@@ -24,6 +21,7 @@
 #include <vector>
 
 using namespace mimo;
+using namespace mimo_abi;
 
 namespace mimo_comm {      // mimo_comm.cpp (RCCL through dlopen)
 int unique_id(char* out128, char* msg, size_t msglen);
@@ -32,161 +30,8 @@ int destroy(void* comm);
 int allreduce_sum_f64(void* comm, double* buf, size_t count, hipStream_t stream, char* msg, size_t msglen);
 }
 
-struct mimo_ctx;
-static int fail(mimo_ctx* ctx, int code, const char* fmt, ...);
-
-#define HIP_TRY(ctx, expr)                                                                \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return fail(ctx, MIMO_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-  } while (0)
-
-// One owner per allocation: device memory (hipMalloc), or with Pinned its host sibling (hipHostMalloc).  Reads as the pointer it holds.
-template <typename T, bool Pinned = false>
-struct Buf {
-  T* p = nullptr;
-  size_t cap = 0;     // elements
-  Buf() = default;
-  Buf(const Buf&) = delete;
-  Buf& operator=(const Buf&) = delete;
-  ~Buf() { (void)release(); }
-  operator T*() const { return p; }
-  // free and forget in one step: the pointer is gone whatever the runtime answers, so nothing is freed twice
-  hipError_t release() {
-    T* old = p;
-    p = nullptr; cap = 0;
-    return !old ? hipSuccess : Pinned ? hipHostFree(old) : hipFree(old);
-  }
-  // room for `count` elements, at least one (an empty data set still gets an allocation).  Grows only; the contents do not survive
-  // a growth (the old block is freed before the new one is allocated); a HIP error goes to the context's error buffer.
-  int ensure(mimo_ctx* ctx, size_t count) {
-    if (count < 1) count = 1;
-    if (cap >= count && p) return MIMO_OK;
-    HIP_TRY(ctx, release());
-    if (Pinned) HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&p), count * sizeof(T), hipHostMallocDefault));
-    else HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)));
-    cap = count;
-    return MIMO_OK;
-  }
-};
-
 // cnt_d: [scan count | labels drawn on NaN rows per component (256) | content checksum of the upload (2)]
 constexpr int kCntLabels = 1, kCntChecksum = 257, kCntWords = 259;
-
-struct mimo_ctx {
-  int device = 0;
-  int num_cu = 256;       // what the grids are sized from (mimo_tune "num_cu" overrides it for tests)
-  int hw_num_cu = 256;
-  int resp_skip_log2 = 60;  // fused softmax pass: statistics skip the row blocks whose weights are all < 2^-60 (0: dense)
-  hipStream_t own_stream = nullptr;
-  ~mimo_ctx() { if (own_stream) (void)hipStreamDestroy(own_stream); }     // (the buffers below free themselves after it)
-  hipStream_t stream = nullptr;
-  char err[512] = {0};   // fixed buffer: reporting an error never allocates
-
-  // data
-  const double* Z = nullptr;  // device
-  Buf<double> Z_owned;       // the library's copy of the rows (Z points at it, or at the caller's attached rows)
-  int64_t N = 0;
-  int D = 0;
-  int64_t row0 = 0;
-
-  // feature map for the current D and structure (0: full symmetric W, 1: diagonal W)
-  int structure = 0;
-  int feat_structure = -1;
-  int feat_D = -1;
-  int F = 0, F16 = 0;
-  std::vector<uint8_t> feat_h;
-  Buf<uint8_t> feat_d;
-  Buf<uint8_t> feat_full_d;         // full map of the current D (small-shape kernel under a structure hint)
-  int feat_full_D = -1;
-
-  // parameter image
-  Buf<double> theta_d;
-  Buf<double, true> theta_h;  // pinned staging
-
-  // slot order of the components in the fused mean-field pass (mimo_set_component_order); order_K = 0: the identity
-  int block_order_on = [] { const char* e = getenv("MIMO_BLOCK_ORDER"); return !e || atoi(e) != 0; }();   // mimo_tune "block_order"
-  int order_K = 0;
-  alignas(8) int32_t order[256] = {0};                    // order[s] = the component in slot s
-  const int32_t* pass_order = nullptr;                    // the pass being launched runs under the order: its device copy (behind the Theta image)
-
-  // workspaces
-  Buf<double> partials;
-  Buf<double> reduced;
-  Buf<double> S_d;            // packed stats + 3 scalars
-  Buf<double, true> S_h;      // pinned staging
-
-  // optional device-resident tables
-  Buf<double> resp;  int resp_K = 0;  bool resp_valid = false;
-  Buf<double> logp;  int logp_K = 0;  bool logp_valid = false;
-  Buf<double> lse;   bool lse_valid = false;
-  Buf<int32_t> labels;  bool labels_valid = false;
-  Buf<double> u_d;
-  bool weights_resident = false;     // u_d holds the row weights of the last mimo_estep_weighted (not uniforms of a label pass)
-  Buf<double> win;    // staged host weights
-  Buf<int32_t> lin;   // staged host labels
-
-  // rows with missing values (NaN): zeroed in the owned copy, excluded from every statistic through the mask
-  Buf<double> row_mask;                                   // (N,) 1 = complete row
-  int64_t n_bad = 0;
-  Buf<unsigned long long> cnt_d;                          // [kCntWords]: scan count, labels drawn on NaN rows per component, content checksum of the upload
-  uint64_t data_sum[2] = {0, 0};                          // mimo_data_checksum: the rows as mimo_upload received them
-  bool data_sum_valid = false;
-  Buf<int32_t> labels_tmp;
-  Buf<uint32_t> ls_aux;                                    // label histogram + slot table of label_stats_slots_kernel
-  Buf<uint16_t> sort_list;   // tiles ranked once for a multi-launch label-statistics pass (label_tile_sort_kernel)
-  Buf<uint16_t> sort_start;
-  Buf<double> table_tmp;
-  int bad_counts_K = 0;         // > 0: cnt_d[kCntLabels ..] holds the label counts of the NaN rows of the last label pass
-
-  // batched mode (mimo_upload_batched): Z holds the rows of B problems back to back; the single-problem entry points refuse
-  bool batched = false;
-  int batch_B = 0;
-  int batch_G = 0;                                         // workgroups of the work table
-  std::vector<int64_t> batch_rows;                         // host copy of row_off [B + 1]
-  Buf<int64_t> batch_row_off_d;                            // [B + 1]
-  Buf<BatchedWork> batch_work_d;                           // [G]
-  Buf<int32_t> batch_wg_off_d;                             // [B + 1]: problem b owns the workgroups [wg_off[b], wg_off[b + 1])
-  // shared batch (mimo_upload_batched_shared): Z holds ONE block of N rows that all B problems read; every per-problem buffer
-  // (lse, labels, weights, uniforms, tables) still has row_off[B] = B N rows — table_rows() — while ctx->N counts the data rows
-  bool batch_shared = false;
-  Buf<double> batch_w;                                     // [row_off[B]] per-row weights of mimo_estep_batched_weighted / mimo_outer_resp_batched
-  bool batch_w_valid = false;
-  // S_d holds the statistics [B][K][1 + Dz + Dz^2] of a batched pass with K = batch_stats_K, its 3 B scalars behind them: set by
-  // every batched pass that reduces statistics, cleared wherever the block is handed to something else (ensure_block)
-  bool batch_stats_valid = false;
-  int batch_stats_K = 0;
-  // device-resident batched VI (mimo_vi_batched.hip); the prior block, and with it the loop state, lives from mimo_vi_prior_batched
-  // to the next upload
-  bool vi_prior_valid = false;
-  int vi_K = 0;
-  Buf<double> vi_prior;                                    // [alpha0 B K | pa B K D | pb B K | pc B K D D | pd B K | log Z B K]
-  Buf<double> vi_post;                                     // [2][B][ViLayout::count()]
-  Buf<double> vi_work;                                     // [terms B K | prior terms B | last bound B]
-  Buf<double> vi_theta;                                    // [B][K16][F16 / 4][64]: the operand images the loop's passes read
-  Buf<double> vi_loop;                                     // [words: kViWords B int32, padded to doubles | trace of the last call]
-  Buf<double, true> vi_loop_h;                             // its pinned sibling
-
-  void* comm = nullptr;         // RCCL communicator (mimo_comm_init): every pass then returns statistics summed over the ranks
-  int comm_world = 1;
-
-  // pending asynchronous call (MIMO_F_ASYNC)
-  bool pending_async = false;
-  size_t pending_slen = 0;
-  bool pending_stats = false;
-
-  // profiling: HIP events around every kernel of a pass, on the launch stream
-  bool prof = false;
-  struct ProfEvent { hipEvent_t e0, e1; int name; };
-  std::vector<ProfEvent> pending;
-  static constexpr int kProfNames = 16;
-  const char* prof_name[kProfNames] = {nullptr};
-  double prof_name_ms[kProfNames] = {0.0};
-  int64_t prof_name_n[kProfNames] = {0};
-  double prof_ms = 0.0;      // all kernels
-  int64_t prof_n = 0;        // passes (run_fused calls)
-};
 
 static char g_err[512] = {0};
 
@@ -221,7 +66,7 @@ extern "C" int mimo_debug_stamps(double* out8) {   // mean cycles per wave of ea
 }
 #endif
 
-static int fail(mimo_ctx* ctx, int code, const char* fmt, ...) {
+int mimo_abi::fail(mimo_ctx* ctx, int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -231,32 +76,16 @@ static int fail(mimo_ctx* ctx, int code, const char* fmt, ...) {
   return code;
 }
 
-// Every extern "C" entry point runs inside this guard: no C++ exception crosses the boundary (include/mimo_hip.h).
-// std::bad_alloc (the std::vector staging buffers, the event list of the profiler) -> MIMO_E_NOMEM, anything else ->
-// MIMO_E_INTERNAL; the message goes to the fixed error buffer, so the handlers themselves cannot throw.
-template <typename F>
-static int guarded(mimo_ctx* ctx, F&& f) noexcept {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return fail(ctx, MIMO_E_NOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(ctx, MIMO_E_INTERNAL, "internal error: %s", e.what());
-  } catch (...) {
-    return fail(ctx, MIMO_E_INTERNAL, "internal error: unknown exception");
-  }
-}
-
-static int bind(mimo_ctx* ctx) {
+int mimo_abi::bind(mimo_ctx* ctx) {
   if (!ctx) return fail(nullptr, MIMO_E_INVALID, "null context");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return MIMO_OK;
 }
 
 // doubles of a packed statistics block: K x (n, sum z, sum z z^T)
-static size_t packed_len(int K, int D) { return (size_t)K * (1 + D + (size_t)D * D); }
+size_t mimo_abi::packed_len(int K, int D) { return (size_t)K * (1 + D + (size_t)D * D); }
 // doubles of one workgroup's partial block: K16 row blocks of 16 components x F16 features, and the scalars behind them
-static size_t partial_stride(int K16, int F16) { return (size_t)16 * K16 * F16 + 4; }
+size_t mimo_abi::partial_stride(int K16, int F16) { return (size_t)16 * K16 * F16 + 4; }
 
 // feature table for dimension D: pairs (a,b), a <= b <= D over z~ = [z, 1]; padding -> (D+1,D+1)
 static int prepare_features(mimo_ctx* ctx, int D) {
@@ -292,7 +121,7 @@ static int prepare_features(mimo_ctx* ctx, int D) {
 
 // Rows of the per-row buffers (lse, labels, weights, uniforms, the columns of a table): the data rows, except on a shared batch,
 // whose B problems each own all N of them (row_off[B] = B N)
-static int64_t table_rows(const mimo_ctx* ctx) {
+int64_t mimo_abi::table_rows(const mimo_ctx* ctx) {
   return ctx->batched ? ctx->batch_rows[(size_t)ctx->batch_B] : ctx->N;
 }
 
@@ -342,7 +171,7 @@ static void fill_args(mimo_ctx* ctx, int K, KernelArgs* a) {
 }
 
 // Why pack_theta (mimo_theta.h) refused a parameter block, in the wording of the entry points (batched: `what`, problem p)
-static int theta_fail(mimo_ctx* ctx, const ThetaFail& f, const char* what, int p) {
+int mimo_abi::theta_fail(mimo_ctx* ctx, const ThetaFail& f, const char* what, int p) {
   switch (f.kind) {
     case ThetaFail::kBadC:
       return what ? fail(ctx, MIMO_E_INVALID, "%s: c[%d][%d] is NaN or +inf", what, p, f.k)
@@ -356,31 +185,6 @@ static int theta_fail(mimo_ctx* ctx, const ThetaFail& f, const char* what, int p
       return what ? fail(ctx, MIMO_E_INVALID, "%s: b or W of problem %d holds a NaN or an infinity", what, p)
                   : fail(ctx, MIMO_E_INVALID, "b or W holds a NaN or an infinity");
   }
-}
-
-// The images of B problems' (c, b, W) back to back in the placement `pl`, followed by `nextra` uint64 words and then `nextra2` more
-// (copied in the same transfer), on the device at ctx->theta_d.  `what`: the batched entry point (its name leads the error texts), null for a single
-// problem.  inline_img: the image goes there and nowhere else — no staging buffer to wait for, no transfer to enqueue.
-template <typename Placement>
-static int stage_theta(mimo_ctx* ctx, const Placement& pl, const double* c, const double* b, const double* W, int B,
-                       const uint64_t* extra, size_t nextra, const char* what, double* inline_img = nullptr,
-                       const uint64_t* extra2 = nullptr, size_t nextra2 = 0) {
-  const size_t D = ctx->D, K = pl.K, per = pl.count(), total = per * B + nextra + nextra2;
-  int rc;
-  if (!inline_img) {
-    if ((rc = ctx->theta_d.ensure(ctx, total))) return rc;
-    if ((rc = ctx->theta_h.ensure(ctx, total))) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));    // the staging buffer may still be in flight from the previous call on this stream
-  }
-  double* img = inline_img ? inline_img : ctx->theta_h;
-  for (int p = 0; p < B; ++p) {
-    const ThetaFail f = pack_theta(pl, ctx->structure, c + p * K, b + p * K * D, W + p * K * D * D, img + per * p);
-    if (f.kind) return theta_fail(ctx, f, what, p);
-  }
-  if (nextra) memcpy(img + per * B, extra, nextra * sizeof(uint64_t));
-  if (nextra2) memcpy(img + per * B + nextra, extra2, nextra2 * sizeof(uint64_t));
-  if (!inline_img) HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, img, total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  return MIMO_OK;
 }
 
 // The Theta image the route's kernels read (placements: mimo_theta.h), and a->theta.  The structure rules hold for every image;
@@ -470,30 +274,13 @@ static void drain_profile(mimo_ctx* ctx) {
   ctx->pending.clear();
 }
 
-static int prof_slot(mimo_ctx* ctx, const char* name) {
+int mimo_abi::prof_slot(mimo_ctx* ctx, const char* name) {
   for (int i = 0; i < mimo_ctx::kProfNames; ++i) {
     if (ctx->prof_name[i] == name) return i;
     if (!ctx->prof_name[i]) { ctx->prof_name[i] = name; return i; }
   }
   return mimo_ctx::kProfNames - 1;
 }
-
-// launch() bracketed by two events on the context's stream when profiling is on
-template <typename L>
-static int timed_launch(mimo_ctx* ctx, const char* name, L&& launch) {
-  if (!ctx->prof) return launch();
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIP_TRY(ctx, hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(ctx, MIMO_E_HIP, "hipEventCreate failed"); }
-  (void)hipEventRecord(e0, ctx->stream);
-  const int rc = launch();
-  (void)hipEventRecord(e1, ctx->stream);
-  if (rc != MIMO_OK) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
-  ctx->pending.push_back({e0, e1, prof_slot(ctx, name)});
-  return MIMO_OK;
-}
-// (a single launch under its profile name)
-#define TIMED_HIP(ctx, name, expr) timed_launch(ctx, name, [&]() -> int { HIP_TRY(ctx, expr); return MIMO_OK; })
 
 // buffers of the ranked tiles where the pass's LabelStatsPlan asks for them: several launches (Dz = 10 .. 16: windows) or the one-pass kernel.
 // Tiles of 256 rows: label_tile_sort_kernel<256> writes, and label_stats_wide_kernel / label_stats_gram_kernel read, list entries
@@ -635,7 +422,7 @@ static int launch_route(mimo_ctx* ctx, KernelArgs& a, int src, const Route& rout
 }
 
 // Room for a block of `len` doubles on the device and in its pinned host sibling
-static int ensure_block(mimo_ctx* ctx, size_t len) {
+int mimo_abi::ensure_block(mimo_ctx* ctx, size_t len) {
   ctx->batch_stats_valid = false;      // whatever the caller puts there next, it says so itself
   const int rc = ctx->S_d.ensure(ctx, len);
   return rc ? rc : ctx->S_h.ensure(ctx, len);
@@ -644,7 +431,7 @@ static int ensure_block(mimo_ctx* ctx, size_t len) {
 // The end of every host delivery.  The first `copy_len` doubles of the device block follow the kernels into the pinned buffer
 // (0: they are there already, or on their way); then wait for the stream and hand the caller `nstats` doubles from its front
 // and `nscalars` doubles from `scalars_at` on.  A null destination is skipped.
-static int hand_out(mimo_ctx* ctx, size_t copy_len, double* S, size_t nstats, double* scalars, size_t scalars_at, size_t nscalars) {
+int mimo_abi::hand_out(mimo_ctx* ctx, size_t copy_len, double* S, size_t nstats, double* scalars, size_t scalars_at, size_t nscalars) {
   if (copy_len) HIP_TRY(ctx, hipMemcpyAsync(ctx->S_h, ctx->S_d, copy_len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (S) memcpy(S, ctx->S_h, nstats * sizeof(double));
@@ -704,34 +491,6 @@ static int run_pass(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S,
   return rc ? rc : deliver(ctx, a, flags, S, scalars, route, l);
 }
 
-// What an entry point reads when the caller passes NULL for an input: the context's own copy `p` if `valid`, else MIMO_E_STATE
-// with the entry point's text `missing` (it may print K).  No `missing`: the input is optional and NULL stays NULL.
-template <typename T>
-struct Resident { const T* p = nullptr; bool valid = false; const char* missing = nullptr; };
-
-// Bring one input of `count` elements to the device and say where to read it (*dev): NULL is the resident copy, under
-// MIMO_F_DEVICE_IN the caller's pointer is the device's already, anything else is host memory and goes through `staging` (*copied
-// becomes true).  The copy is only enqueued: the source is pageable, so the entry point synchronises once all its inputs are
-// queued, and does what else follows from a fresh staging buffer there.
-// (P: const T* or T* — KernelArgs holds its tables and labels as writable pointers for the kernels that produce them)
-template <typename T, typename P>
-static int stage_input(mimo_ctx* ctx, const T* src, size_t count, int flags, Buf<T>& staging, const Resident<T>& res, int K,
-                       P* dev, bool* copied) {
-  if (!src) {
-    if (res.missing && !res.valid) return fail(ctx, MIMO_E_STATE, res.missing, K);
-    *dev = const_cast<P>(res.p);
-  } else if (flags & MIMO_F_DEVICE_IN) {
-    *dev = const_cast<P>(src);
-  } else {
-    const int rc = staging.ensure(ctx, count);
-    if (rc) return rc;
-    if (count) HIP_TRY(ctx, hipMemcpyAsync(staging, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    *dev = staging;
-    *copied = true;
-  }
-  return MIMO_OK;
-}
-
 // Every pass goes through here.  Data without NaN rows: straight to run_pass.  With NaN rows (zeroed in the library's
 // copy, ctx->row_mask = 0 there): the log-densities, tables, labels and ELBO scalars are those of the zeroed rows
 // (= the reference's normaliser-only log-density), the statistics leave those rows out —
@@ -775,6 +534,51 @@ static int run_fused(mimo_ctx* ctx, KernelArgs& a, int src, int flags, double* S
   HIP_TRY(ctx, launch_mask_table(a.resp, ctx->row_mask, ctx->table_tmp, a.K, N, ctx->stream));
   a.resp = ctx->table_tmp;
   return run_pass(ctx, a, src, flags, S, scalars, route);
+}
+
+int mimo_abi::set_data(mimo_ctx* ctx, int64_t N, int Dz) {
+  if (N < 0) return fail(ctx, MIMO_E_INVALID, "N must be >= 0");
+  if (Dz < 1 || Dz > kMaxD)
+    return fail(ctx, MIMO_E_UNSUPPORTED, "Dz = %d outside [1, %d]", Dz, kMaxD);
+  ctx->N = N; ctx->D = Dz;
+  ctx->order_K = 0;
+  ctx->batched = false;
+  ctx->batch_shared = false;
+  ctx->resp_valid = ctx->logp_valid = ctx->lse_valid = ctx->labels_valid = false;
+  ctx->weights_resident = false;
+  ctx->batch_w_valid = false;
+  ctx->batch_stats_valid = false;
+  ctx->vi_prior_valid = false;
+  return prepare_features(ctx, Dz);
+}
+
+// Replace the resident rows by N x D doubles from `src`: a host block that is copied, the caller's device rows that are borrowed,
+// or (scan_nan_rows) borrowed rows that need a copy the library may write.  ctx->Z is null from before the old copy is freed until
+// the last step has succeeded, so a failure leaves the context without data (MIMO_E_NODATA) and never with freed rows.
+int mimo_abi::set_rows(mimo_ctx* ctx, const double* src, Rows how) {
+  const size_t count = (size_t)ctx->N * ctx->D;
+  int rc;
+  ctx->Z = nullptr;
+  if (how != Rows::DeviceCopy) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // kernels of earlier calls may still read the old rows
+  HIP_TRY(ctx, ctx->Z_owned.release());
+  if (how != Rows::DeviceBorrow) {
+    if ((rc = ctx->Z_owned.ensure(ctx, count))) return rc;
+    if (how == Rows::DeviceCopy) HIP_TRY(ctx, hipMemcpyAsync(ctx->Z_owned, src, count * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    else if (count) HIP_TRY(ctx, hipMemcpy(ctx->Z_owned, src, count * sizeof(double), hipMemcpyHostToDevice));
+    src = ctx->Z_owned;
+  }
+  ctx->Z = src;
+  return MIMO_OK;
+}
+
+// The end of every getter: `bytes` of a device table to the caller, or why there is none
+int mimo_abi::copy_out(mimo_ctx* ctx, void* dst, const void* src, size_t bytes, bool valid, const char* what) {
+  int rc = bind(ctx); if (rc) return rc;
+  if (!dst) return fail(ctx, MIMO_E_INVALID, "%s: destination is NULL", what);
+  if (!valid || !src) return fail(ctx, MIMO_E_STATE, "%s: table was never produced (pass the MIMO_F_KEEP_* flag)", what);
+  HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return MIMO_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -830,42 +634,6 @@ int mimo_set_stream(mimo_ctx* ctx, void* hip_stream) {
   ctx->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx->own_stream;
   return MIMO_OK;
   });
-}
-
-static int set_data(mimo_ctx* ctx, int64_t N, int Dz) {
-  if (N < 0) return fail(ctx, MIMO_E_INVALID, "N must be >= 0");
-  if (Dz < 1 || Dz > kMaxD)
-    return fail(ctx, MIMO_E_UNSUPPORTED, "Dz = %d outside [1, %d]", Dz, kMaxD);
-  ctx->N = N; ctx->D = Dz;
-  ctx->order_K = 0;
-  ctx->batched = false;
-  ctx->batch_shared = false;
-  ctx->resp_valid = ctx->logp_valid = ctx->lse_valid = ctx->labels_valid = false;
-  ctx->weights_resident = false;
-  ctx->batch_w_valid = false;
-  ctx->batch_stats_valid = false;
-  ctx->vi_prior_valid = false;
-  return prepare_features(ctx, Dz);
-}
-
-// Replace the resident rows by N x D doubles from `src`: a host block that is copied, the caller's device rows that are borrowed,
-// or (scan_nan_rows) borrowed rows that need a copy the library may write.  ctx->Z is null from before the old copy is freed until
-// the last step has succeeded, so a failure leaves the context without data (MIMO_E_NODATA) and never with freed rows.
-enum class Rows { HostCopy, DeviceBorrow, DeviceCopy };
-static int set_rows(mimo_ctx* ctx, const double* src, Rows how) {
-  const size_t count = (size_t)ctx->N * ctx->D;
-  int rc;
-  ctx->Z = nullptr;
-  if (how != Rows::DeviceCopy) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // kernels of earlier calls may still read the old rows
-  HIP_TRY(ctx, ctx->Z_owned.release());
-  if (how != Rows::DeviceBorrow) {
-    if ((rc = ctx->Z_owned.ensure(ctx, count))) return rc;
-    if (how == Rows::DeviceCopy) HIP_TRY(ctx, hipMemcpyAsync(ctx->Z_owned, src, count * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    else if (count) HIP_TRY(ctx, hipMemcpy(ctx->Z_owned, src, count * sizeof(double), hipMemcpyHostToDevice));
-    src = ctx->Z_owned;
-  }
-  ctx->Z = src;
-  return MIMO_OK;
 }
 
 // Find the rows that hold a NaN.  `owned`: Z is the library's copy — such rows are zeroed in place and the mask written;
@@ -1276,15 +1044,6 @@ int mimo_predict_flags(mimo_ctx* ctx, const double* c, const double* b, const do
   });
 }
 
-static int copy_out(mimo_ctx* ctx, void* dst, const void* src, size_t bytes, bool valid, const char* what) {
-  int rc = bind(ctx); if (rc) return rc;
-  if (!dst) return fail(ctx, MIMO_E_INVALID, "%s: destination is NULL", what);
-  if (!valid || !src) return fail(ctx, MIMO_E_STATE, "%s: table was never produced (pass the MIMO_F_KEEP_* flag)", what);
-  HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return MIMO_OK;
-}
-
 // mimo_get_*: one of the tables a pass left on the device
 enum class Kept { Resp, Logp, Lse, Labels };
 static int get_kept(mimo_ctx* ctx, void* out, Kept which, const char* what) {
@@ -1619,738 +1378,6 @@ int mimo_plan_shape(int Dz, int K, int structure, int64_t N, int gibbs, int64_t*
   a.gibbs = gibbs ? 1 : 0;
   if (desc && desc_len > 0) desc[0] = 0;
   plan_route(&ctx, route_for(&ctx, K, {kSrcEstep, gibbs != 0}), a, K, gibbs, out8, desc, desc && desc_len > 0 ? (size_t)desc_len : 0);
-  return MIMO_OK;
-  });
-}
-
-// ------------------------------------------------------------------------------------------
-// Batched softmax pass (mimo_batched.hip)
-// ------------------------------------------------------------------------------------------
-// The upload of a batch: `N` data rows, the concatenated rows of B problems (row_off[B] = N) or, `shared`, ONE block that all B
-// problems read (row_off[b] = b N).  Both forms build the same tables from row_off.
-static int upload_batch(mimo_ctx* ctx, const double* Z_host, int64_t N, const int64_t* row_off, int B, int Dz, bool shared,
-                        const char* me) {
-  int rc;
-  if (!Z_host && N > 0) return fail(ctx, MIMO_E_INVALID, "%s: Z is NULL", me);
-  // batched mode has no NaN-row semantics: every element must be finite
-  for (int64_t i = 0; i < N * Dz; ++i)
-    if (!std::isfinite(Z_host[i]))
-      return fail(ctx, MIMO_E_INVALID, "%s: row %lld holds a NaN or an infinity", me, (long long)(i / Dz));
-  // work table: problem b's tiles in runs of batched_tiles_per_wg(N_b), a function of N_b alone
-  std::vector<BatchedWork> work;
-  std::vector<int32_t> wg_off((size_t)B + 1, 0);
-  for (int b = 0; b < B; ++b) {
-    const int64_t nb = row_off[b + 1] - row_off[b];
-    const int64_t tiles = (nb + kTile - 1) / kTile;
-    const int tpw = batched_tiles_per_wg(nb);
-    for (int64_t t = 0; t < tiles; t += tpw)
-      work.push_back(BatchedWork{b, (int32_t)t, (int32_t)std::min<int64_t>(tpw, tiles - t), 0});
-    if (work.size() > (size_t)INT32_MAX) return fail(ctx, MIMO_E_INVALID, "%s: too many rows", me);
-    wg_off[(size_t)b + 1] = (int32_t)work.size();
-  }
-  if ((rc = set_data(ctx, N, Dz))) return rc;
-  if ((rc = set_rows(ctx, Z_host, Rows::HostCopy))) return rc;
-  ctx->n_bad = 0; ctx->bad_counts_K = 0; ctx->data_sum_valid = false;
-  // the three tables are replaced wholesale: each is as long as this batch needs
-  HIP_TRY(ctx, ctx->batch_row_off_d.release());
-  HIP_TRY(ctx, ctx->batch_work_d.release());
-  HIP_TRY(ctx, ctx->batch_wg_off_d.release());
-  if ((rc = ctx->batch_row_off_d.ensure(ctx, (size_t)B + 1))) return rc;
-  if ((rc = ctx->batch_work_d.ensure(ctx, work.size()))) return rc;
-  if ((rc = ctx->batch_wg_off_d.ensure(ctx, (size_t)B + 1))) return rc;
-  HIP_TRY(ctx, hipMemcpy(ctx->batch_row_off_d, row_off, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  if (!work.empty()) HIP_TRY(ctx, hipMemcpy(ctx->batch_work_d, work.data(), work.size() * sizeof(BatchedWork), hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->batch_wg_off_d, wg_off.data(), ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  ctx->batch_rows.assign(row_off, row_off + B + 1);
-  ctx->batch_B = B;
-  ctx->batch_G = (int)work.size();
-  ctx->batched = true;
-  ctx->batch_shared = shared;
-  return MIMO_OK;
-}
-
-int mimo_upload_batched(mimo_ctx* ctx, const double* Z_host, const int64_t* row_off, int B, int Dz) {
-  return guarded(ctx, [&]() -> int {
-  int rc = bind(ctx); if (rc) return rc;
-  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
-  if (B < 1 || B > 65535 || !row_off) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: B = %d outside [1, 65535] or row_off is NULL", B);
-  if (Dz < 1 || Dz > kBatchedMaxD)
-    return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_upload_batched: Dz = %d outside [1, %d] (batched pass)", Dz, kBatchedMaxD);
-  if (row_off[0] != 0) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: row_off[0] = %lld, must be 0", (long long)row_off[0]);
-  for (int b = 0; b < B; ++b)
-    if (row_off[b + 1] < row_off[b])
-      return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched: row_off decreases at problem %d", b);
-  return upload_batch(ctx, Z_host, row_off[B], row_off, B, Dz, false, "mimo_upload_batched");
-  });
-}
-
-int mimo_upload_batched_shared(mimo_ctx* ctx, const double* Z_host, int64_t N, int B, int Dz) {
-  return guarded(ctx, [&]() -> int {
-  int rc = bind(ctx); if (rc) return rc;
-  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
-  if (B < 1 || B > 65535) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched_shared: B = %d outside [1, 65535]", B);
-  if (N < 1) return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched_shared: N = %lld, must be >= 1", (long long)N);
-  if (Dz < 1 || Dz > kBatchedMaxD)
-    return fail(ctx, MIMO_E_UNSUPPORTED, "mimo_upload_batched_shared: Dz = %d outside [1, %d] (batched pass)", Dz, kBatchedMaxD);
-  if (N > std::numeric_limits<int64_t>::max() / ((int64_t)B * kBatchedMaxK))      // B N K: the longest per-problem buffer
-    return fail(ctx, MIMO_E_INVALID, "mimo_upload_batched_shared: too many rows");
-  std::vector<int64_t> row_off((size_t)B + 1);
-  for (int b = 0; b <= B; ++b) row_off[(size_t)b] = (int64_t)b * N;
-  return upload_batch(ctx, Z_host, N, row_off.data(), B, Dz, true, "mimo_upload_batched_shared");
-  });
-}
-
-// The checks every batched pass shares (a batch, no pending call, no communicator, the full structure, a covered shape)
-static int batched_ready(mimo_ctx* ctx, int K, const char* what) {
-  if (!ctx->batched) return fail(ctx, MIMO_E_INVALID, "%s: the context holds no batch (call mimo_upload_batched)", what);
-  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
-  if (ctx->comm)
-    return fail(ctx, MIMO_E_UNSUPPORTED, "%s: a communicator is attached (mimo_comm_init); the batched pass "
-                "has no reduction over ranks", what);
-  if (K < 1) return fail(ctx, MIMO_E_INVALID, "K must be >= 1 (got %d)", K);
-  const int D = ctx->D;
-  if (ctx->structure != MIMO_STRUCT_FULL)
-    return fail(ctx, MIMO_E_UNSUPPORTED, "%s: only the full structure (symmetric W) is covered", what);
-  if (!batched_covers(K, D))
-    return fail(ctx, MIMO_E_UNSUPPORTED, "%s: K = %d, Dz = %d outside the batched kernels (K <= %d, Dz <= %d, "
-                "ceil(K/16) * ceil(F/16) <= %d with F = (Dz+1)(Dz+2)/2)", what, K, D, kBatchedMaxK, kBatchedMaxD, kBatchedMaxPairs);
-  return MIMO_OK;
-}
-
-// Stacked operand image [B][K16][NS][64] of the B problems' (c, b, W) (problem p's slice is the single-problem image of the fused
-// kernels, K16 row blocks of it), followed by `extra` uint64 words; on the device at ctx->theta_d.
-static int batched_theta(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, const uint64_t* extra,
-                         size_t nextra, const char* what, const uint64_t* extra2 = nullptr, size_t nextra2 = 0) {
-  const ThetaGeneric pl = {ctx->D, K, ctx->structure, (K + 15) / 16, ctx->F16 / 4};
-  return stage_theta(ctx, pl, c, b, W, ctx->batch_B, extra, nextra, what, nullptr, extra2, nextra2);
-}
-
-static BatchedArgs batched_args(mimo_ctx* ctx, int K) {
-  BatchedArgs a;
-  a.Z = ctx->Z; a.row_off = ctx->batch_row_off_d; a.work = ctx->batch_work_d; a.theta = ctx->theta_d; a.feat = ctx->feat_d;
-  a.partials = ctx->partials; a.lse = nullptr;
-  a.D = ctx->D; a.K = K; a.K16 = (K + 15) / 16; a.F16 = ctx->F16;
-  a.ZS = (ctx->D + 2) | 1;
-  a.do_stats = 1;
-  a.shared = ctx->batch_shared ? 1 : 0;
-  a.u = nullptr; a.seeds = nullptr; a.labels = nullptr; a.sweep = 0;
-  a.resp = nullptr;
-  a.sel = nullptr; a.sel_off = nullptr;
-  return a;
-}
-
-// The softmax pass of a batch, plain (weights = null: launch_batched) or with the device weights `weights` on the statistics
-// (launch_batched_weighted); the caller has run batched_ready and its own argument checks.
-static int batched_softmax_pass(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, const double* weights,
-                                int flags, double* S, double* scalars, const char* me) {
-  int rc;
-  if (flags & ~(MIMO_F_NO_STATS | MIMO_F_ENTROPY_SPLIT | MIMO_F_KEEP_LSE))
-    return fail(ctx, MIMO_E_INVALID, "%s: flags 0x%x: only MIMO_F_NO_STATS, MIMO_F_ENTROPY_SPLIT, MIMO_F_KEEP_LSE", me, flags);
-  const bool no_stats = (flags & MIMO_F_NO_STATS) != 0;
-  if (!c || !b || !W || !scalars || (!no_stats && !S))
-    return fail(ctx, MIMO_E_INVALID, "%s: c, b, W, scalars (and S without MIMO_F_NO_STATS) must be non-NULL", me);
-  const int D = ctx->D, B = ctx->batch_B;
-  const int F = ctx->F, F16 = ctx->F16, K16 = (K + 15) / 16;
-  if ((rc = batched_theta(ctx, c, b, W, K, nullptr, 0, me))) return rc;
-
-  const int G = ctx->batch_G;
-  if ((rc = ctx->partials.ensure(ctx, partial_stride(K16, F16) * (size_t)std::max(G, 1)))) return rc;
-  const bool keep_lse = (flags & MIMO_F_KEEP_LSE) != 0;
-  if (keep_lse && (rc = ctx->lse.ensure(ctx, (size_t)table_rows(ctx)))) return rc;
-  ctx->lse_valid = keep_lse;
-  ctx->resp_valid = ctx->logp_valid = ctx->labels_valid = false;
-  BatchedArgs a = batched_args(ctx, K);
-  a.lse = keep_lse ? ctx->lse : nullptr;
-  a.do_stats = no_stats ? 0 : 1;
-  a.u = weights;
-  HIP_TRY(ctx, weights ? launch_batched_weighted(a, G, ctx->stream) : launch_batched(a, G, ctx->stream));
-  const size_t nstats = no_stats ? 0 : packed_len(K, D) * B, out = nstats + 3 * (size_t)B;
-  if ((rc = ensure_block(ctx, out))) return rc;
-  double* sc_d = ctx->S_d + nstats;
-  const int split = (flags & (MIMO_F_ENTROPY_SPLIT | MIMO_F_KEEP_LSE)) ? 1 : 0;
-  HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, D, F, F16, split,
-                                     no_stats ? nullptr : ctx->S_d, sc_d, ctx->stream));
-  ctx->batch_stats_valid = !no_stats; ctx->batch_stats_K = K;
-  return hand_out(ctx, out, no_stats ? nullptr : S, nstats, scalars, nstats, 3 * (size_t)B);
-}
-
-int mimo_estep_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, int flags, double* S,
-                       double* scalars) {
-  return guarded(ctx, [&]() -> int {
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, "mimo_estep_batched"))) return rc;
-  return batched_softmax_pass(ctx, c, b, W, K, nullptr, flags, S, scalars, "mimo_estep_batched");
-  });
-}
-
-int mimo_estep_batched_weighted(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, const double* row_weights,
-                                int flags, double* S, double* scalars) {
-  return guarded(ctx, [&]() -> int {
-  const char* const me = "mimo_estep_batched_weighted";
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, me))) return rc;
-  const int64_t rows = table_rows(ctx);
-  if (!row_weights) {
-    if (!ctx->batch_w_valid || !ctx->batch_w)
-      return fail(ctx, MIMO_E_STATE, "%s: row_weights is NULL and no weights are resident (an earlier call or mimo_outer_resp_batched "
-                  "leaves them; an upload drops them)", me);
-  } else {
-    for (int64_t n = 0; n < rows; ++n)
-      if (!(std::isfinite(row_weights[n]) && row_weights[n] >= 0.0))
-        return fail(ctx, MIMO_E_INVALID, "%s: weight %lld is negative, NaN or an infinity", me, (long long)n);
-    ctx->batch_w_valid = false;
-    if ((rc = ctx->batch_w.ensure(ctx, (size_t)rows))) return rc;
-    if (rows > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->batch_w, row_weights, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // row_weights is pageable host memory
-    ctx->batch_w_valid = true;
-  }
-  return batched_softmax_pass(ctx, c, b, W, K, ctx->batch_w, flags, S, scalars, me);
-  });
-}
-
-int mimo_outer_resp_batched(mimo_ctx* ctx, const double* log_gating, int flags, double* out) {
-  return guarded(ctx, [&]() -> int {
-  const char* const me = "mimo_outer_resp_batched";
-  int rc = bind(ctx); if (rc) return rc;
-  if (!ctx->batched || !ctx->batch_shared)
-    return fail(ctx, MIMO_E_STATE, "%s: the context holds no shared batch (call mimo_upload_batched_shared)", me);
-  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
-  if (!ctx->lse_valid || !ctx->lse)
-    return fail(ctx, MIMO_E_STATE, "%s: no lse is resident (run mimo_estep_batched / _weighted with MIMO_F_KEEP_LSE first)", me);
-  if (flags != 0) return fail(ctx, MIMO_E_INVALID, "%s: flags 0x%x: none are defined", me, flags);
-  if (!log_gating || !out) return fail(ctx, MIMO_E_INVALID, "%s: log_gating and out must be non-NULL", me);
-  const int B = ctx->batch_B;
-  const int64_t N = ctx->N;
-  bool any = false;
-  for (int p = 0; p < B; ++p) {
-    if (std::isnan(log_gating[p]) || log_gating[p] == std::numeric_limits<double>::infinity())
-      return fail(ctx, MIMO_E_INVALID, "%s: log_gating[%d] is NaN or +inf", me, p);
-    any = any || std::isfinite(log_gating[p]);
-  }
-  if (!any) return fail(ctx, MIMO_E_INVALID, "%s: every entry of log_gating is -inf", me);
-  // log_gating goes the way the seeds of the random start go: through the operand image's pinned buffer
-  if ((rc = ctx->theta_d.ensure(ctx, (size_t)B))) return rc;
-  if ((rc = ctx->theta_h.ensure(ctx, (size_t)B))) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));    // the staging buffer may still be in flight from the previous call on this stream
-  memcpy(ctx->theta_h, log_gating, (size_t)B * sizeof(double));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, ctx->theta_h, (size_t)B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ctx->batch_w_valid = false;
-  if ((rc = ctx->batch_w.ensure(ctx, (size_t)B * (size_t)N))) return rc;
-  if ((rc = ctx->partials.ensure(ctx, outer_resp_partials(B, N)))) return rc;
-  if ((rc = ensure_block(ctx, (size_t)B + 1))) return rc;
-  HIP_TRY(ctx, launch_outer_resp(ctx->lse, ctx->theta_d, B, N, ctx->batch_w, ctx->partials, ctx->S_d, ctx->stream));
-  ctx->batch_w_valid = true;
-  return hand_out(ctx, (size_t)B + 1, out, (size_t)B + 1, nullptr, 0, 0);
-  });
-}
-
-int mimo_get_row_weights_batched(mimo_ctx* ctx, double* out) {
-  return guarded(ctx, [&]() -> int {
-  if (!ctx) return fail(nullptr, MIMO_E_INVALID, "null context");
-  if (!ctx->batched || !ctx->batch_w_valid)
-    return fail(ctx, MIMO_E_STATE, "mimo_get_row_weights_batched: no row weights are resident");
-  const size_t rows = (size_t)table_rows(ctx);
-  if (rows == 0) return MIMO_OK;
-  return copy_out(ctx, out, ctx->batch_w, rows * sizeof(double), true, "mimo_get_row_weights_batched");
-  });
-}
-
-// The minibatch pass (launch_batched_rows): the softmax pass over a selection of every problem's resident rows.  The call's own
-// work table — the selection sizes through batched_tiles_per_wg, as mimo_upload_batched builds its table from the row counts —
-// travels with the indices behind the operand image; the upload's tables are left alone.
-int mimo_estep_batched_rows(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K, const int64_t* rows,
-                            const int64_t* sel_off, int flags, double* S, double* scalars) {
-  return guarded(ctx, [&]() -> int {
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, "mimo_estep_batched_rows"))) return rc;
-  if (flags & ~(MIMO_F_NO_STATS | MIMO_F_ENTROPY_SPLIT))
-    return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: flags 0x%x: only MIMO_F_NO_STATS, MIMO_F_ENTROPY_SPLIT (a selection's "
-                "normalisers have no place in the resident lse: no MIMO_F_KEEP_LSE; the indices are host memory: no MIMO_F_DEVICE_IN)", flags);
-  const bool no_stats = (flags & MIMO_F_NO_STATS) != 0;
-  if (!c || !b || !W || !scalars || (!no_stats && !S))
-    return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: c, b, W, scalars (and S without MIMO_F_NO_STATS) must be non-NULL");
-  if (!rows || !sel_off) return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: rows and sel_off must be non-NULL");
-  const int D = ctx->D, B = ctx->batch_B;
-  const int F = ctx->F, F16 = ctx->F16, K16 = (K + 15) / 16;
-  // the kernel gathers through these indices unchecked: every one is checked here, before anything is staged or launched
-  if (sel_off[0] != 0) return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: sel_off[0] = %lld, must be 0", (long long)sel_off[0]);
-  for (int p = 0; p < B; ++p) {
-    if (sel_off[p + 1] < sel_off[p]) return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: sel_off decreases at problem %d", p);
-    const int64_t nb = ctx->batch_rows[(size_t)p + 1] - ctx->batch_rows[(size_t)p];
-    for (int64_t i = sel_off[p]; i < sel_off[p + 1]; ++i)
-      if (rows[i] < 0 || rows[i] >= nb)
-        return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: problem %d: index %lld (entry %lld of its selection) outside [0, %lld)",
-                    p, (long long)rows[i], (long long)(i - sel_off[p]), (long long)nb);
-  }
-  const size_t M = (size_t)sel_off[B];
-  // behind the operand image, in its transfer: [rows (M), straight from the caller's array | sel_off (B + 1) | work table (2 words
-  // per workgroup) | wg_off (int32, B + 1)]
-  std::vector<uint64_t> extra((size_t)B + 1);
-  memcpy(extra.data(), sel_off, ((size_t)B + 1) * sizeof(int64_t));
-  std::vector<BatchedWork> work;
-  std::vector<int32_t> wg_off((size_t)B + 2, 0);     // (an even count of int32: whole words)
-  for (int p = 0; p < B; ++p) {
-    const int64_t mb = sel_off[p + 1] - sel_off[p];
-    const int64_t tiles = (mb + kTile - 1) / kTile;
-    const int tpw = batched_tiles_per_wg(mb);
-    for (int64_t t = 0; t < tiles; t += tpw)
-      work.push_back(BatchedWork{p, (int32_t)t, (int32_t)std::min<int64_t>(tpw, tiles - t), 0});
-    if (work.size() > (size_t)INT32_MAX) return fail(ctx, MIMO_E_INVALID, "mimo_estep_batched_rows: too many rows");
-    wg_off[(size_t)p + 1] = (int32_t)work.size();
-  }
-  static_assert(sizeof(BatchedWork) == 2 * sizeof(uint64_t), "a work table entry is two words of the staged block");
-  const size_t G = work.size(), at_work = extra.size(), at_wg = at_work + 2 * G, nwg = ((size_t)B + 2) / 2;
-  extra.resize(at_wg + nwg);
-  if (G) memcpy(extra.data() + at_work, work.data(), G * sizeof(BatchedWork));
-  memcpy(extra.data() + at_wg, wg_off.data(), nwg * sizeof(uint64_t));
-  if ((rc = batched_theta(ctx, c, b, W, K, reinterpret_cast<const uint64_t*>(rows), M, "mimo_estep_batched_rows", extra.data(),
-                          extra.size()))) return rc;
-  const uint64_t* sel_d = reinterpret_cast<const uint64_t*>(ctx->theta_d.p) + (size_t)K16 * (F16 / 4) * 64 * B;
-  const uint64_t* ex = sel_d + M;      // the small tables
-
-  if ((rc = ctx->partials.ensure(ctx, partial_stride(K16, F16) * std::max<size_t>(G, 1)))) return rc;
-  // a softmax pass for the residency rule, as mimo_estep_batched without MIMO_F_KEEP_LSE
-  ctx->lse_valid = false;
-  ctx->resp_valid = ctx->logp_valid = ctx->labels_valid = false;
-  BatchedArgs a = batched_args(ctx, K);
-  a.work = reinterpret_cast<const BatchedWork*>(ex + at_work);
-  a.sel = reinterpret_cast<const int64_t*>(sel_d);
-  a.sel_off = reinterpret_cast<const int64_t*>(ex);
-  a.do_stats = no_stats ? 0 : 1;
-  HIP_TRY(ctx, launch_batched_rows(a, (int)G, ctx->stream));
-  const size_t nstats = no_stats ? 0 : packed_len(K, D) * B, out = nstats + 3 * (size_t)B;
-  if ((rc = ensure_block(ctx, out))) return rc;
-  const int split = (flags & MIMO_F_ENTROPY_SPLIT) ? 1 : 0;
-  HIP_TRY(ctx, launch_batched_reduce(ctx->partials, reinterpret_cast<const int32_t*>(ex + at_wg), B, ctx->feat_d, K, D, F, F16, split,
-                                     no_stats ? nullptr : ctx->S_d, ctx->S_d + nstats, ctx->stream));
-  ctx->batch_stats_valid = !no_stats; ctx->batch_stats_K = K;
-  return hand_out(ctx, out, no_stats ? nullptr : S, nstats, scalars, nstats, 3 * (size_t)B);
-  });
-}
-
-// The label pass of the batched Gibbs sweep (launch_batched_labels) and its statistics: the partial blocks of the launch
-// just queued are reduced per problem into S (B x K(1+Dz+Dz^2)); the scalars the reduction also writes are not returned.
-static int batched_label_stats_out(mimo_ctx* ctx, int K, double* S) {
-  const int D = ctx->D, B = ctx->batch_B;
-  const size_t nstats = packed_len(K, D) * B;
-  int rc;
-  if ((rc = ensure_block(ctx, nstats + 3 * (size_t)B))) return rc;
-  HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, D, ctx->F, ctx->F16, 0,
-                                     ctx->S_d, ctx->S_d + nstats, ctx->stream));
-  ctx->batch_stats_valid = true; ctx->batch_stats_K = K;
-  return hand_out(ctx, nstats, S, nstats, nullptr, 0, 0);
-}
-
-int mimo_gibbs_labels_batched(mimo_ctx* ctx, const double* c, const double* b, const double* W, int K,
-                              const uint64_t* seeds, uint64_t sweep, const double* u, int flags, int32_t* labels_out,
-                              double* S) {
-  return guarded(ctx, [&]() -> int {
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, "mimo_gibbs_labels_batched"))) return rc;
-  if (flags & ~MIMO_F_NO_STATS)
-    return fail(ctx, MIMO_E_INVALID, "mimo_gibbs_labels_batched: flags 0x%x: only MIMO_F_NO_STATS", flags);
-  const bool no_stats = (flags & MIMO_F_NO_STATS) != 0;
-  if (!c || !b || !W || (!no_stats && !S))
-    return fail(ctx, MIMO_E_INVALID, "mimo_gibbs_labels_batched: c, b, W (and S without MIMO_F_NO_STATS) must be non-NULL");
-  if (!u && !seeds)
-    return fail(ctx, MIMO_E_INVALID, "mimo_gibbs_labels_batched: u and seeds are both NULL (give the uniforms or one Philox "
-                "seed per problem)");
-  const int B = ctx->batch_B, G = ctx->batch_G;
-  const int64_t N = table_rows(ctx);
-  // the seeds travel behind the operand image, in its transfer
-  if ((rc = batched_theta(ctx, c, b, W, K, u ? nullptr : seeds, u ? 0 : (size_t)B, "mimo_gibbs_labels_batched"))) return rc;
-  const size_t count = (size_t)((K + 15) / 16) * (ctx->F16 / 4) * 64 * B;
-  if ((rc = ctx->labels.ensure(ctx, (size_t)N))) return rc;
-  const double* ud = nullptr;
-  bool copied = false;        // (u NULL: Philox uniforms from the seeds; the flags admit no MIMO_F_DEVICE_IN)
-  if ((rc = stage_input<double>(ctx, u, (size_t)N, flags, ctx->u_d, {}, K, &ud, &copied))) return rc;
-  if (copied) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // u is pageable host memory
-  if (copied) ctx->weights_resident = false;                     // u_d holds uniforms now
-  if ((rc = ctx->partials.ensure(ctx, partial_stride((K + 15) / 16, ctx->F16) * (size_t)std::max(G, 1)))) return rc;
-  ctx->resp_valid = ctx->logp_valid = ctx->lse_valid = false;
-  BatchedArgs a = batched_args(ctx, K);
-  a.do_stats = no_stats ? 0 : 1;
-  a.u = ud;
-  a.seeds = u ? nullptr : reinterpret_cast<const uint64_t*>(ctx->theta_d + count);
-  a.labels = ctx->labels;
-  a.sweep = sweep;
-  HIP_TRY(ctx, launch_batched_labels(a, kBatchedDraw, G, ctx->stream));
-  ctx->labels_valid = true;
-  if (!no_stats && (rc = batched_label_stats_out(ctx, K, S))) return rc;
-  if (labels_out && N > 0) {
-    HIP_TRY(ctx, hipMemcpyAsync(labels_out, ctx->labels, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return MIMO_OK;
-  });
-}
-
-int mimo_label_stats_batched(mimo_ctx* ctx, const int32_t* labels, int K, int flags, double* S) {
-  return guarded(ctx, [&]() -> int {
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, "mimo_label_stats_batched"))) return rc;
-  if (flags != 0) return fail(ctx, MIMO_E_INVALID, "mimo_label_stats_batched: flags 0x%x: none are defined", flags);
-  if (!S) return fail(ctx, MIMO_E_INVALID, "mimo_label_stats_batched: S is NULL");
-  const int64_t N = table_rows(ctx);
-  const int G = ctx->batch_G;
-  // the kernel indexes its accumulators by label: the caller's labels are checked on the host, before anything is staged
-  for (int64_t n = 0; labels && n < N; ++n)
-    if (labels[n] < 0 || labels[n] >= K)
-      return fail(ctx, MIMO_E_INVALID, "mimo_label_stats_batched: label %d of row %lld outside [0, %d)", labels[n],
-                  (long long)n, K);
-  const int32_t* lab = nullptr;
-  bool copied = false;        // (flags is 0: the labels are the resident draw or host memory)
-  if ((rc = stage_input<int32_t>(ctx, labels, (size_t)N, flags, ctx->lin,
-                                 {ctx->labels, ctx->labels_valid && ctx->labels, "mimo_label_stats_batched: labels is NULL and no batched draw is resident"},
-                                 K, &lab, &copied))) return rc;
-  if (copied) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // labels is pageable host memory
-  if ((rc = ctx->partials.ensure(ctx, partial_stride((K + 15) / 16, ctx->F16) * (size_t)std::max(G, 1)))) return rc;
-  BatchedArgs a = batched_args(ctx, K);
-  a.labels = const_cast<int32_t*>(lab);
-  HIP_TRY(ctx, launch_batched_labels(a, kBatchedGiven, G, ctx->stream));
-  return batched_label_stats_out(ctx, K, S);
-  });
-}
-
-// The table pass of a batch (launch_batched_weights over the device table `table`, the problems' K-major (K, N_b) blocks back
-// to back) and its statistics: S (B x K(1+Dz+Dz^2)), reduced like the label passes' (the scalars of the reduction are zeros
-// and are not returned).
-static int batched_table_stats(mimo_ctx* ctx, const double* table, int K, double* S) {
-  const int G = ctx->batch_G;
-  int rc;
-  if ((rc = ctx->partials.ensure(ctx, partial_stride((K + 15) / 16, ctx->F16) * (size_t)std::max(G, 1)))) return rc;
-  BatchedArgs a = batched_args(ctx, K);
-  a.resp = table;
-  HIP_TRY(ctx, launch_batched_weights(a, G, ctx->stream));
-  return batched_label_stats_out(ctx, K, S);
-}
-
-int mimo_weighted_stats_batched(mimo_ctx* ctx, const double* resp, int K, int flags, double* S) {
-  return guarded(ctx, [&]() -> int {
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, "mimo_weighted_stats_batched"))) return rc;
-  if (flags != 0) return fail(ctx, MIMO_E_INVALID, "mimo_weighted_stats_batched: flags 0x%x: none are defined", flags);
-  if (!S) return fail(ctx, MIMO_E_INVALID, "mimo_weighted_stats_batched: S is NULL");
-  const double* table = nullptr;
-  bool copied = false;        // (flags is 0: the table is the resident one or host memory; its values are taken as they are)
-  if ((rc = stage_input<double>(ctx, resp, (size_t)K * (size_t)table_rows(ctx), flags, ctx->win,
-                                {ctx->resp, ctx->resp_valid && ctx->resp_K == K && ctx->resp,
-                                 "mimo_weighted_stats_batched: resp is NULL and no (K=%d, N_total) table is resident"},
-                                K, &table, &copied))) return rc;
-  if (copied) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // resp is pageable host memory
-  return batched_table_stats(ctx, table, K, S);
-  });
-}
-
-int mimo_random_resp_stats_batched(mimo_ctx* ctx, int K, const uint64_t* seeds, int flags, double* S) {
-  return guarded(ctx, [&]() -> int {
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, "mimo_random_resp_stats_batched"))) return rc;
-  if (flags != 0) return fail(ctx, MIMO_E_INVALID, "mimo_random_resp_stats_batched: flags 0x%x: none are defined", flags);
-  if (!S || !seeds) return fail(ctx, MIMO_E_INVALID, "mimo_random_resp_stats_batched: S and seeds must be non-NULL");
-  const int B = ctx->batch_B;
-  const int64_t N = table_rows(ctx);
-  ctx->resp_valid = false;
-  if ((rc = ctx->resp.ensure(ctx, (size_t)K * (size_t)N))) return rc;
-  // the seeds go the way the label pass sends them: through the operand image's pinned buffer (there is no image here)
-  if ((rc = ctx->theta_d.ensure(ctx, (size_t)B))) return rc;
-  if ((rc = ctx->theta_h.ensure(ctx, (size_t)B))) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));    // the staging buffer may still be in flight from the previous call on this stream
-  memcpy(ctx->theta_h, seeds, (size_t)B * sizeof(uint64_t));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, ctx->theta_h, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, launch_batched_random_resp(ctx->resp, ctx->batch_row_off_d, reinterpret_cast<const uint64_t*>(ctx->theta_d.p), B, K, N,
-                                          ctx->stream));
-  ctx->resp_K = K; ctx->resp_valid = true;
-  return batched_table_stats(ctx, ctx->resp, K, S);
-  });
-}
-
-// ------------------------------------------------------------------------------------------
-// Device-resident batched VI (mimo_vi_batched.hip)
-// ------------------------------------------------------------------------------------------
-// doubles the loop's int32 words take at the front of vi_loop
-static size_t vi_words_len(int B) { return ((size_t)kViWords * B + 1) / 2; }
-
-// What the three entry points share beyond batched_ready: a prior block of this K
-static int vi_ready(mimo_ctx* ctx, int K, const char* me) {
-  if (!ctx->vi_prior_valid || !ctx->vi_prior)
-    return fail(ctx, MIMO_E_STATE, "%s: no prior block is resident (call mimo_vi_prior_batched; an upload drops it)", me);
-  if (ctx->vi_K != K)
-    return fail(ctx, MIMO_E_STATE, "%s: the resident prior block is that of K = %d, not K = %d", me, ctx->vi_K, K);
-  return MIMO_OK;
-}
-
-static ViArgs vi_args(mimo_ctx* ctx, int K) {
-  const size_t B = (size_t)ctx->batch_B, BK = B * K, D = (size_t)ctx->D;
-  ViArgs a{};
-  a.S = ctx->S_d;
-  a.scalars = ctx->S_d + packed_len(K, ctx->D) * B;
-  const double* p = ctx->vi_prior;
-  a.alpha0 = p; p += BK;
-  a.pa = p; p += BK * D;
-  a.pb = p; p += BK;
-  a.pc = p; p += BK * D * D;
-  a.pd = p; p += BK;
-  a.plz = p;
-  a.post = ctx->vi_post;
-  a.term = ctx->vi_work;
-  a.prior_terms = ctx->vi_work + BK;
-  a.last = ctx->vi_work + BK + B;
-  a.words = reinterpret_cast<int32_t*>(ctx->vi_loop.p);
-  a.theta = ctx->vi_theta;
-  a.trace = ctx->vi_loop + vi_words_len(ctx->batch_B);
-  a.B = ctx->batch_B; a.K = K; a.D = ctx->D; a.K16 = (K + 15) / 16; a.NS = ctx->F16 / 4;
-  a.tol = 0.0;
-  return a;
-}
-
-int mimo_vi_prior_batched(mimo_ctx* ctx, int K, const double* alpha0, const double* pa, const double* pb, const double* pc,
-                          const double* pd, const double* prior_logZ) {
-  return guarded(ctx, [&]() -> int {
-  const char* const me = "mimo_vi_prior_batched";
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, me))) return rc;
-  if (!alpha0 || !pa || !pb || !pc || !pd || !prior_logZ)
-    return fail(ctx, MIMO_E_INVALID, "%s: alpha0, pa, pb, pc, pd and prior_logZ must be non-NULL", me);
-  const size_t B = (size_t)ctx->batch_B, BK = B * K, D = (size_t)ctx->D;
-  const double* const parts[6] = {alpha0, pa, pb, pc, pd, prior_logZ};
-  const char* const names[6] = {"alpha0", "pa", "pb", "pc", "pd", "prior_logZ"};
-  const size_t lens[6] = {BK, BK * D, BK, BK * D * D, BK, BK};
-  for (int t = 0; t < 6; ++t)
-    for (size_t i = 0; i < lens[t]; ++i)
-      if (!std::isfinite(parts[t][i]))
-        return fail(ctx, MIMO_E_INVALID, "%s: %s of problem %d holds a NaN or an infinity", me, names[t], (int)(i / (lens[t] / B)));
-  ctx->vi_prior_valid = false;
-  const ViLayout L{K, ctx->D};
-  const size_t nprior = BK * (4 + D + D * D), npost = 2 * B * (size_t)L.count(), nwork = BK + 2 * B;
-  const size_t ntheta = B * (size_t)((K + 15) / 16) * (ctx->F16 / 4) * 64, nwords = vi_words_len(ctx->batch_B);
-  if ((rc = ctx->vi_prior.ensure(ctx, nprior))) return rc;
-  if ((rc = ctx->vi_post.ensure(ctx, npost))) return rc;
-  if ((rc = ctx->vi_work.ensure(ctx, nwork))) return rc;
-  if ((rc = ctx->vi_theta.ensure(ctx, ntheta))) return rc;
-  if ((rc = ctx->vi_loop.ensure(ctx, nwords))) return rc;
-  // the loop state: every problem active, nothing appended, status clear, slot 0 current; zero blocks, zero images (the entries no
-  // kernel writes — padded features, the b / W entries of padding components — are the zeros pack_theta leaves there)
-  std::vector<int32_t> words((size_t)kViWords * B, 0);
-  std::fill(words.begin() + (size_t)kViActive * B, words.begin() + (size_t)(kViActive + 1) * B, 1);
-  double* q = ctx->vi_prior;
-  for (int t = 0; t < 6; ++t) {
-    HIP_TRY(ctx, hipMemcpyAsync(q, parts[t], lens[t] * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    q += lens[t];
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_loop, words.data(), words.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_post, 0, npost * sizeof(double), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_work, 0, nwork * sizeof(double), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_theta, 0, ntheta * sizeof(double), ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // the sources are pageable host memory
-  ctx->vi_prior_valid = true;
-  ctx->vi_K = K;
-  return MIMO_OK;
-  });
-}
-
-int mimo_vi_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status) {
-  return guarded(ctx, [&]() -> int {
-  const char* const me = "mimo_vi_run_batched";
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, me))) return rc;
-  if (flags != 0) return fail(ctx, MIMO_E_INVALID, "%s: flags 0x%x: none are defined", me, flags);
-  if (iters < 1 || iters > 65536) return fail(ctx, MIMO_E_INVALID, "%s: iters = %d outside [1, 65536]", me, iters);
-  if (!(tol >= 0.0)) return fail(ctx, MIMO_E_INVALID, "%s: tol = %g must be >= 0", me, tol);
-  if (!trace || !n_done || !status) return fail(ctx, MIMO_E_INVALID, "%s: trace, n_done and status must be non-NULL", me);
-  if ((rc = vi_ready(ctx, K, me))) return rc;
-  if (!ctx->batch_stats_valid || !ctx->S_d)
-    return fail(ctx, MIMO_E_STATE, "%s: no statistics are resident (run a batched pass that returns statistics first; an upload and "
-                "every call that returns something else drop them)", me);
-  if (ctx->batch_stats_K != K)
-    return fail(ctx, MIMO_E_STATE, "%s: the resident statistics are those of K = %d, not K = %d", me, ctx->batch_stats_K, K);
-  const int B = ctx->batch_B, D = ctx->D, G = ctx->batch_G;
-  const int F = ctx->F, F16 = ctx->F16, K16 = (K + 15) / 16;
-  const size_t nwords = vi_words_len(B), ntrace = (size_t)iters * B, total = nwords + ntrace;
-  if (ctx->vi_loop.cap < total) {          // a longer trace than any before: the words move to the new block
-    Buf<double> grown;
-    if ((rc = grown.ensure(ctx, total))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(grown.p, ctx->vi_loop.p, nwords * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::swap(grown.p, ctx->vi_loop.p);
-    std::swap(grown.cap, ctx->vi_loop.cap);
-  }
-  if ((rc = ctx->vi_loop_h.ensure(ctx, total))) return rc;
-  if ((rc = ctx->partials.ensure(ctx, partial_stride(K16, F16) * (size_t)std::max(G, 1)))) return rc;
-  ctx->resp_valid = ctx->logp_valid = ctx->labels_valid = ctx->lse_valid = false;
-
-  ViArgs va = vi_args(ctx, K);
-  va.tol = tol;
-  BatchedArgs a = batched_args(ctx, K);
-  a.theta = ctx->vi_theta;
-  const size_t nstats = packed_len(K, D) * (size_t)B;
-  HIP_TRY(ctx, hipMemsetAsync(va.words + (size_t)kViDone * B, 0, (size_t)B * sizeof(int32_t), ctx->stream));
-  for (int it = 0; it < iters; ++it) {
-    HIP_TRY(ctx, launch_vi_update(va, ctx->stream));
-    HIP_TRY(ctx, launch_vi_gating(va, ctx->stream));
-    HIP_TRY(ctx, launch_batched(a, G, ctx->stream));
-    HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, D, F, F16, 0, ctx->S_d, ctx->S_d + nstats,
-                                       ctx->stream));
-    HIP_TRY(ctx, launch_vi_finish(va, it, ctx->stream));
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_loop_h, ctx->vi_loop, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const int32_t* words = reinterpret_cast<const int32_t*>(ctx->vi_loop_h.p);
-  memcpy(trace, ctx->vi_loop_h + nwords, ntrace * sizeof(double));
-  memcpy(n_done, words + (size_t)kViDone * B, (size_t)B * sizeof(int32_t));
-  memcpy(status, words + (size_t)kViStatus * B, (size_t)B * sizeof(int32_t));
-  return MIMO_OK;
-  });
-}
-
-int mimo_vi_get_batched(mimo_ctx* ctx, int K, double* out) {
-  return guarded(ctx, [&]() -> int {
-  const char* const me = "mimo_vi_get_batched";
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, me))) return rc;
-  if (!out) return fail(ctx, MIMO_E_INVALID, "%s: out is NULL", me);
-  if ((rc = vi_ready(ctx, K, me))) return rc;
-  const size_t B = (size_t)ctx->batch_B, per = (size_t)ViLayout{K, ctx->D}.count();
-  std::vector<double> both(2 * B * per);
-  std::vector<int32_t> words((size_t)kViWords * B);
-  HIP_TRY(ctx, hipMemcpyAsync(both.data(), ctx->vi_post, both.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(words.data(), ctx->vi_loop, words.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  for (size_t p = 0; p < B; ++p) {
-    const size_t slot = words[(size_t)kViSlot * B + p] ? 1 : 0;
-    memcpy(out + p * per, both.data() + (slot * B + p) * per, per * sizeof(double));
-  }
-  return MIMO_OK;
-  });
-}
-
-int mimo_vi_get_theta_batched(mimo_ctx* ctx, int K, double* theta, double* stats) {
-  return guarded(ctx, [&]() -> int {
-  const char* const me = "mimo_vi_get_theta_batched";
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, me))) return rc;
-  if (!theta && !stats) return fail(ctx, MIMO_E_INVALID, "%s: theta and stats are both NULL", me);
-  if ((rc = vi_ready(ctx, K, me))) return rc;
-  if (stats && (!ctx->batch_stats_valid || ctx->batch_stats_K != K || !ctx->S_d))
-    return fail(ctx, MIMO_E_STATE, "%s: no statistics of K = %d are resident", me, K);
-  const size_t B = (size_t)ctx->batch_B, count = B * ((K + 15) / 16) * (ctx->F16 / 4) * 64;
-  if (theta) HIP_TRY(ctx, hipMemcpyAsync(theta, ctx->vi_theta, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (stats)
-    HIP_TRY(ctx, hipMemcpyAsync(stats, ctx->S_d, (packed_len(K, ctx->D) + 3) * B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return MIMO_OK;
-  });
-}
-
-// ------------------------------------------------------------------------------------------
-// Batched prediction (mimo_predict_batched.hip)
-// ------------------------------------------------------------------------------------------
-// The rows are an argument: nothing of the context's data, batch or kept tables is read or written.  Buffers: the parameter,
-// transform and row_off blocks go through the operand image's pinned staging buffer in ONE transfer (theta_h -> theta_d, restaged
-// by every pass); X and y go through the staged-weights workspace `win`, as mimo_predict_flags uses it (pure staging: nothing
-// resident lives there, so nothing is invalidated); the outputs are one block of S_d / S_h (ensure_block / hand_out), which drops
-// the resident statistics of a batched pass (batch_stats_valid: mimo_vi_run_batched then asks for a new pass).
-int mimo_predict_batched(mimo_ctx* ctx, int B, const double* X, const int64_t* row_off, int64_t N_shared, int dx,
-                         const double* x_tf, const double* c, const double* b, const double* W, int K,
-                         const double* M, const double* Q, const double* Cc, int dy, int mode,
-                         const double* y, const double* y_tf, const double* P, const double* ld,
-                         double* mu, double* covar, double* nlpd, int flags) {
-  return guarded(ctx, [&]() -> int {
-  const char* const me = "mimo_predict_batched";
-  int rc = bind(ctx); if (rc) return rc;
-  if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
-  if (ctx->comm)
-    return fail(ctx, MIMO_E_UNSUPPORTED, "%s: a communicator is attached (mimo_comm_init); the batched pass has no ranks", me);
-  if (flags & ~MIMO_F_DIAG_VAR)
-    return fail(ctx, MIMO_E_INVALID, "%s: flags 0x%x: only MIMO_F_DIAG_VAR (host pointers throughout)", me, flags);
-  if (!c || !b || !W || !M || !Q || !Cc || !mu || !covar)
-    return fail(ctx, MIMO_E_INVALID, "%s: c, b, W, M, Q, Cc, mu and covar must be non-NULL", me);
-  if (B < 1 || K < 1 || (mode != 0 && mode != 1))
-    return fail(ctx, MIMO_E_INVALID, "%s: B = %d, K = %d must be >= 1 and mode = %d must be 0 or 1", me, B, K, mode);
-  if (!predict_batched_covers(dx, dy) || B > kPredictBatchedMaxB)
-    return fail(ctx, MIMO_E_UNSUPPORTED, "%s: dx = %d, dy = %d, B = %d outside the batched prediction kernel (affine experts, "
-                "1 <= dx <= %d, 1 <= dy <= %d, B <= %d)", me, dx, dy, B, kPredictBatchedMaxDx, kPredictBatchedMaxDy, kPredictBatchedMaxB);
-  if (N_shared < 0) return fail(ctx, MIMO_E_INVALID, "%s: N_shared = %lld is negative", me, (long long)N_shared);
-  if (row_off && N_shared != 0)
-    return fail(ctx, MIMO_E_INVALID, "%s: row_off and N_shared = %lld are both given (ragged form: N_shared = 0; shared form: "
-                "row_off = NULL)", me, (long long)N_shared);
-  int64_t max_rows = N_shared;
-  if (row_off) {
-    if (row_off[0] != 0) return fail(ctx, MIMO_E_INVALID, "%s: row_off[0] = %lld, must be 0", me, (long long)row_off[0]);
-    for (int p = 0; p < B; ++p) {
-      if (row_off[p + 1] < row_off[p]) return fail(ctx, MIMO_E_INVALID, "%s: row_off decreases at problem %d", me, p);
-      max_rows = std::max<int64_t>(max_rows, row_off[p + 1] - row_off[p]);
-    }
-  }
-  const bool want_nlpd = nlpd != nullptr, diag = (flags & MIMO_F_DIAG_VAR) != 0;
-  if (want_nlpd && (!y || !P || !ld)) return fail(ctx, MIMO_E_INVALID, "%s: nlpd needs y, P and ld", me);
-  if (y_tf && !y) return fail(ctx, MIMO_E_INVALID, "%s: y_tf without y", me);
-  const int dd[2] = {dx, dy};
-  const double* const tfs[2] = {x_tf, y_tf};
-  for (int t = 0; t < 2; ++t)
-    for (int p = 0; tfs[t] && p < B; ++p)
-      for (int i = 0; i < dd[t]; ++i) {
-        const double s = tfs[t][((size_t)p * 2 + 1) * dd[t] + i];
-        if (s == 0.0 || !std::isfinite(s))
-          return fail(ctx, MIMO_E_INVALID, "%s: %s of problem %d: scale[%d] = %g must be finite and nonzero", me, t ? "y_tf" : "x_tf", p, i, s);
-      }
-  const size_t n_in = (size_t)(row_off ? row_off[B] : N_shared);        // rows of X (and y)
-  const size_t n_out = row_off ? n_in : (size_t)N_shared * (size_t)B;   // rows of the outputs
-  if (max_rows == 0) return MIMO_OK;                                    // an all-empty batch: nothing to launch
-  if (!X) return fail(ctx, MIMO_E_INVALID, "%s: X is NULL", me);
-
-  // one staged block: [gate (c, b, W interleaved per component) | M | Q | Cc | P | ld | x_tf | y_tf | row_off]
-  const int dc = dx + 1;
-  const size_t BK = (size_t)B * K, gk = 1 + (size_t)dx + (size_t)dx * dx;
-  const size_t ng = BK * gk, nM = BK * dy * dc, nQ = BK * dc * dc, nC = BK * dy * dy;
-  const size_t nxt = x_tf ? (size_t)B * 2 * dx : 0, nyt = y_tf ? (size_t)B * 2 * dy : 0, nro = row_off ? (size_t)B + 1 : 0;
-  const size_t nparam = ng + nM + nQ + 2 * nC + BK + nxt + nyt + nro;
-  if ((rc = ctx->theta_d.ensure(ctx, nparam))) return rc;
-  if ((rc = ctx->theta_h.ensure(ctx, nparam))) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));    // the staging buffer may still be in flight from the previous call on this stream
-  double* q = ctx->theta_h;
-  for (size_t k = 0; k < BK; ++k) {
-    *q++ = c[k];
-    memcpy(q, b + k * dx, sizeof(double) * dx); q += dx;
-    memcpy(q, W + k * dx * dx, sizeof(double) * dx * dx); q += (size_t)dx * dx;
-  }
-  memcpy(q, M, sizeof(double) * nM); q += nM;
-  memcpy(q, Q, sizeof(double) * nQ); q += nQ;
-  memcpy(q, Cc, sizeof(double) * nC); q += nC;
-  if (want_nlpd) { memcpy(q, P, sizeof(double) * nC); memcpy(q + nC, ld, sizeof(double) * BK); }
-  else memset(q, 0, sizeof(double) * (nC + BK));
-  q += nC + BK;
-  if (nxt) { memcpy(q, x_tf, sizeof(double) * nxt); q += nxt; }
-  if (nyt) { memcpy(q, y_tf, sizeof(double) * nyt); q += nyt; }
-  if (nro) memcpy(q, row_off, sizeof(int64_t) * nro);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->theta_d, ctx->theta_h, nparam * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-
-  // the rows: X, then y
-  const size_t nX = n_in * dx, nY = want_nlpd ? n_in * dy : 0;
-  if ((rc = ctx->win.ensure(ctx, nX + nY))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->win, X, nX * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  if (nY) HIP_TRY(ctx, hipMemcpyAsync(ctx->win + nX, y, nY * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-
-  // the outputs: [mu | second output | nlpd], one block
-  const size_t ncov = diag ? 2 * (size_t)dy : (size_t)dy * dy;
-  const size_t n_mu = n_out * dy, n_cov = n_out * ncov, n_nl = want_nlpd ? n_out : 0, out = n_mu + n_cov + n_nl;
-  if ((rc = ensure_block(ctx, out))) return rc;
-
-  PredictBatchedArgs a{};
-  const double* d = ctx->theta_d;
-  a.X = ctx->win; a.N_shared = row_off ? 0 : N_shared;
-  a.B = B; a.dx = dx; a.dy = dy; a.K = K; a.mode = mode; a.diag = diag ? 1 : 0;
-  a.gate = d; a.M = d + ng; a.Q = a.M + nM; a.Cc = a.Q + nQ; a.P = a.Cc + nC; a.ld = a.P + nC;
-  const double* tail = a.ld + BK;
-  a.x_tf = nxt ? tail : nullptr; tail += nxt;
-  a.y_tf = nyt ? tail : nullptr; tail += nyt;
-  a.row_off = nro ? reinterpret_cast<const int64_t*>(tail) : nullptr;
-  a.y = want_nlpd ? ctx->win + nX : nullptr;
-  a.mu = ctx->S_d; a.covar = ctx->S_d + n_mu; a.nlpd = want_nlpd ? ctx->S_d + n_mu + n_cov : nullptr;
-  if ((rc = TIMED_HIP(ctx, "predict_batched_kernel", launch_predict_batched(a, max_rows, ctx->stream)))) return rc;
-  if (ctx->prof) ctx->prof_n += 1;
-  if ((rc = hand_out(ctx, out, mu, n_mu, covar, n_mu, n_cov))) return rc;
-  if (want_nlpd) memcpy(nlpd, ctx->S_h + n_mu + n_cov, n_nl * sizeof(double));
   return MIMO_OK;
   });
 }

@@ -15,5 +15,5 @@ for o in mimo_kernels mimo_small mimo_rowwave mimo_label_stats mimo_wide mimo_na
     objs="$objs $o.o"
   fi
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -pthread $objs mimo_abi.o mimo_comm.o mimo_host.o -ldl -o ../../tools/variants/$name.so
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -pthread $objs mimo_abi.o mimo_abi_batched.o mimo_comm.o mimo_host.o -ldl -o ../../tools/variants/$name.so
 echo built tools/variants/$name.so

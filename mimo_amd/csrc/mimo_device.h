@@ -158,12 +158,26 @@ __device__ inline double wave_sum(double v) {
 // field the integer add below cannot underflow — zero for every purpose here (sums whose largest term is 1), and
 // one v_max_f64 instead of a 64-bit compare and two selects per element.  The shift by 6 goes through an opaque
 // asm: LLVM otherwise rewrites ((n >> 6) << 20) + hi as shift, mask and a 64-bit add (3 instructions for 2).
+//
+// The argument-reduction constants of all five exponentials, named once.  The two fractions of ln2 are hex literals — the doubles
+// nearest ln2 / 64 and ln2 / 2048, the same 53 bits at two exponents — and the assertions tie every constant to ln2 =
+// 0x1.62e42fefa39efp-1 (a decimal ln2 / 2048 that was off by 1.41e-14 relative once cost the 2048-entry variants a factor of 127 in
+// their error, unseen by any whole-array comparison).  The contract — relative error ~ 2^-53 |x|, absolute error < 4e-17 — is held
+// per entry against a longdouble reference over x in [-703, 0] by tests/test_gpu_softmax_accuracy.py.
+constexpr double k64_Ln2 = 92.33248261689366;            // 64 / ln2    (0x1.71547652b82fep+6)
+constexpr double kLn2_64 = 0x1.62e42fefa39efp-7;         // ln2 / 64
+constexpr double k2048_Ln2 = 2954.639443740597;          // 2048 / ln2  (0x1.71547652b82fep+11)
+constexpr double kLn2_2048 = 0x1.62e42fefa39efp-12;      // ln2 / 2048
+static_assert(kLn2_2048 * 32 == kLn2_64, "ln2 / 2048 and ln2 / 64 must be the same bits, five exponents apart");
+static_assert(kLn2_64 * 64 == 0x1.62e42fefa39efp-1, "ln2 / 64 must be the double nearest ln2, scaled");
+static_assert(k2048_Ln2 - 32 * k64_Ln2 <= 0x1p-41 && 32 * k64_Ln2 - k2048_Ln2 <= 0x1p-41, "2048 / ln2 must be within one ulp of 32 (64 / ln2)");
+static_assert(k64_Ln2 * kLn2_64 - 1.0 <= 0x1p-51 && 1.0 - k64_Ln2 * kLn2_64 <= 0x1p-51, "64 / ln2 and ln2 / 64 must be reciprocal to two ulps");
 __device__ inline double exp_nonpos(double x, const double* __restrict__ tab) {
   x = fmax(x, -707.0);
-  const double t = fma(x, 92.33248261689366, 6755399441055744.0);
+  const double t = fma(x, k64_Ln2, 6755399441055744.0);
   const int n = __double2loint(t);
   const double nf = t - 6755399441055744.0;
-  const double r = fma(nf, -0x1.62e42fefa39efp-7, x);
+  const double r = fma(nf, -kLn2_64, x);
   double q = fma(r, 1.0 / 120.0, 1.0 / 24.0);
   q = fma(r, q, 1.0 / 6.0);
   q = fma(r, q, 0.5);
@@ -176,15 +190,17 @@ __device__ inline double exp_nonpos(double x, const double* __restrict__ tab) {
 
 // exp(x), x <= 0, with a 2048-entry table of 2^(i/2048) (16 KB of LDS, where a kernel has them to spare: the row-owner kernels, the small-shape kernel): the reduced
 // argument is <= ln2/4096, a cubic is enough (r^4/24 < 4e-17) — 13 instructions instead of the 15 of exp_nonpos, and
-// the row-owner label kernel issues 64 of them per lane and step.  Same argument clamp, same single-constant reduction (relative
-// error 1.1e-16 |x|, an absolute error below 4e-17 for every x <= 0).
+// the row-owner label kernel issues 64 of them per lane and step.  Same argument clamp, same single-constant reduction with the
+// SAME 53 bits of ln2 (kLn2_2048 = kLn2_64 / 32, asserted above): n is 32 times larger and the constant's error 32 times smaller, so
+// the reduction error is exp_nonpos's — relative error 1.1e-16 |x|, an absolute error below 4e-17 for every x <= 0.  It holds only
+// while kLn2_2048 is the double nearest ln2 / 2048: every unit in its last place costs another 1.4 * 2^-53 |x|.
 constexpr int kExpTab = 2048;
 __device__ __forceinline__ double exp_nonpos_t2048(double x, const double* __restrict__ tab) {
   x = fmax(x, -707.0);
-  const double t = fma(x, 2954.639443740597, 6755399441055744.0);          // 2048 / ln2, 1.5 * 2^52
+  const double t = fma(x, k2048_Ln2, 6755399441055744.0);                  // 1.5 * 2^52
   const int n = __double2loint(t);
   const double nf = t - 6755399441055744.0;
-  const double r = fma(nf, -3.3845077175778103e-04, x);                    // ln2 / 2048
+  const double r = fma(nf, -kLn2_2048, x);
   double q = fma(r, 1.0 / 6.0, 0.5);
   q = fma(r, q, 1.0);
   const double e = tab[n & (kExpTab - 1)] * fma(r, q, 1.0);
@@ -203,10 +219,10 @@ __device__ __forceinline__ double exp_tab_entry_c(int i) {
 }
 __device__ __forceinline__ double exp_nonpos_t2048c(double x, const double* __restrict__ tab) {
   x = fmax(x, -707.0);
-  const double t = fma(x, 2954.639443740597, 6755399441055744.0);          // 2048 / ln2, 1.5 * 2^52
+  const double t = fma(x, k2048_Ln2, 6755399441055744.0);                  // 1.5 * 2^52
   const int n = __double2loint(t);
   const double nf = t - 6755399441055744.0;
-  const double r = fma(nf, -3.3845077175778103e-04, x);                    // ln2 / 2048
+  const double r = fma(nf, -kLn2_2048, x);
   double q = fma(r, 1.0 / 6.0, 0.5);
   q = fma(r, q, 1.0);
   const double tv = tab[n & (kExpTab - 1)];
@@ -222,9 +238,9 @@ __device__ __forceinline__ double exp_nonpos_t2048c(double x, const double* __re
 //   exp_c_finish: cubic in r times the scaled table entry
 __device__ __forceinline__ void exp_c_issue(double x, double& r, int& n) {
   x = fmax(x, -707.0);
-  const double t = fma(x, 2954.639443740597, 6755399441055744.0);
+  const double t = fma(x, k2048_Ln2, 6755399441055744.0);
   n = __double2loint(t);
-  r = fma(t - 6755399441055744.0, -3.3845077175778103e-04, x);
+  r = fma(t - 6755399441055744.0, -kLn2_2048, x);
 }
 __device__ __forceinline__ double exp_c_finish(double r, int n, double tv) {
   double q = fma(r, 1.0 / 6.0, 0.5);

@@ -850,6 +850,7 @@ def test_native_rccl_communicator_one_rank(engine, ordered, monkeypatch):
             Z, c, b, W = _random_problem(rng, N, D, K)
             eng.upload(Z)
             S0, sc0 = eng.estep(c, b, W)
+            _, sc0n = eng.estep(c, b, W, stats=False)
             lab0, G0 = eng.gibbs_labels(c, b, W, seed=3, sweep=1)
             eng.comm_init(HipEngine.comm_unique_id(), 0, 1)
             S1, sc1 = eng.estep(c, b, W)
@@ -859,8 +860,12 @@ def test_native_rccl_communicator_one_rank(engine, ordered, monkeypatch):
             assert np.array_equal(S2.sxx, S0.sxx) and sc2[0] == sc0[0]
             lab1, G1 = eng.gibbs_labels(c, b, W, seed=3, sweep=1)
             assert np.array_equal(lab1, lab0) and np.array_equal(G1.sxx, G0.sxx)
+            # the pass without statistics against ITSELF without the communicator: on the small-shape kernel it sums m + log(sum e)
+            # per row where the plain pass sums m and takes one log of a product of sums — the same number up to the rounding of two
+            # tree sums of N <= 30011 terms of one sign (2 (log2 N + a few) half-ulps of the total: 64 ulps is generous), the same
+            # bits only by chance
             _, sc3 = eng.estep(c, b, W, stats=False)
-            assert sc3[0] == sc0[0]
+            assert sc3[0] == sc0n[0] and abs(sc3[0] - sc0[0]) <= 64 * np.spacing(abs(sc0[0]))
             eng.comm_destroy()
     finally:
         eng.close()

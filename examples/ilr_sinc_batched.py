@@ -14,6 +14,10 @@ every model drew — gathered on the device from the resident data — and one o
 stream is seeded like its joblib worker (0 .. fits - 1); the workers leave Python's `random`, which draws the minibatches,
 unseeded, and here each model gets a stream of its own seeded the same way, so a run is reproducible.
 
+--resident runs the coordinate-descent VI (after the Gibbs warm-up, if one is asked for) with the device-resident loop,
+meanfield_coordinate_descent_batched_ilr: the update of the three blocks, the canonical form, the bound and the stopping rule stay
+on the device between two passes; the likelihoods are drawn once, at the end.  It has no effect on --svi-iters.
+
 --predict adds what the reference job is run for (its lines 196-201): ONE batched prediction of all fitted models over the
 full input grid (meanfield_prediction_batched: the grid goes to the device once, each model's standardisation is applied in
 the kernel), then the four curves of the reference's figure — the mean and the standard deviation across models of mu and
@@ -32,8 +36,8 @@ from mimo_amd.distributions import (TruncatedStickBreaking, CategoricalWithStick
                                     StackedLinearGaussiansWithMatrixNormalWisharts)
 from mimo_amd.engine import HipEngine
 from mimo_amd.mixtures import BayesianMixtureOfLinearGaussians
-from mimo_amd.mixtures.batched import (meanfield_coordinate_descent_batched, meanfield_prediction_batched,
-                                        meanfield_stochastic_descent_batched, resample_batched)
+from mimo_amd.mixtures.batched import (meanfield_coordinate_descent_batched, meanfield_coordinate_descent_batched_ilr,
+                                        meanfield_prediction_batched, meanfield_stochastic_descent_batched, resample_batched)
 
 
 def make_model(K, engine):
@@ -60,6 +64,8 @@ def main():
     ap.add_argument("--svi-iters", type=int, default=0, help="outer iterations of stochastic VI (0: coordinate-descent VI)")
     ap.add_argument("--svi-batch", type=int, default=256, help="rows per minibatch of stochastic VI")
     ap.add_argument("--predict", action="store_true", help="one batched prediction of all models on the full input grid")
+    ap.add_argument("--resident", action="store_true",
+                    help="coordinate-descent VI with the device-resident loop (no per-iteration likelihood draws)")
     args = ap.parse_args()
     rng = np.random.default_rng(1337)
     x = rng.uniform(-10., 10., size=(args.rows, 1))
@@ -83,10 +89,11 @@ def main():
                                                     batch_size=args.svi_batch, numpy_seeds=range(args.fits),
                                                     python_seeds=range(args.fits))
     elif args.gibbs_iters > 0:
-        vlbs = meanfield_coordinate_descent_batched(models, data, randomize=False, maxiter=args.iters, tol=1e-6)
+        descent = meanfield_coordinate_descent_batched_ilr if args.resident else meanfield_coordinate_descent_batched
+        vlbs = descent(models, data, randomize=False, maxiter=args.iters, tol=1e-6)
     else:
-        vlbs = meanfield_coordinate_descent_batched(models, data, randomize=True, init_rng='philox', seeds=range(args.fits),
-                                                    maxiter=args.iters, tol=1e-6)
+        descent = meanfield_coordinate_descent_batched_ilr if args.resident else meanfield_coordinate_descent_batched
+        vlbs = descent(models, data, randomize=True, init_rng='philox', seeds=range(args.fits), maxiter=args.iters, tol=1e-6)
     wall = time.perf_counter() - t0
     final = np.array([v[-1] for v in vlbs])
     print(f"{args.fits} fits of {ntrain} rows, K = {args.experts}: best ELBO {final.max():.2f}, median {np.median(final):.2f}, "

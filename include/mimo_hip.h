@@ -498,6 +498,56 @@ int mimo_vi_get_batched(mimo_ctx* ctx, int K, double* out);
  * MIMO_E_STATE if none of this K are resident.  No reference counterpart. */
 int mimo_vi_get_theta_batched(mimo_ctx* ctx, int K, double* theta, double* stats);
 
+/* ---- device-resident batched VI for mixtures of linear-Gaussian experts ----
+ * The same loop for B BayesianMixtureOfLinearGaussians over z = [x, y], Dz = dx + dy: a basis of K Normal-Wishart blocks over x,
+ * K affine experts y | x~ = [x, 1] with matrix-normal-Wishart blocks (column_dim dc = dx + 1), and a Dirichlet or a truncated
+ * stick-breaking gating, all untied.  The pass, its reduction, the stopping rule, the status bits, the loop state and every
+ * requirement are those of mimo_vi_run_batched.  One family's prior block is resident at a time: mimo_vi_run_batched and
+ * mimo_vi_get_batched answer an ILR prior with MIMO_E_STATE (the message names the family), the ILR calls answer a GMM prior the same
+ * way, an upload drops either, and mimo_vi_get_theta_batched works after either.
+ *
+ * mimo_vi_ilr_prior_batched: the priors of the B problems, copied to the device once; resets the loop as mimo_vi_prior_batched does.
+ * Replaces: the priors' nat_param / log_partition() read by every meanfield_update and bound of the three blocks
+ *   (mimo/distributions/bayesian.py:151-159,173-176,225-230,258-265,839-844,854-858; composite.py:50-72,95-98,577-592,622-625) and the
+ *   gating prior's parameters (dirichlet.py:31-33,108-112).
+ *   gating_kind MIMO_VI_GATING_DIRICHLET: g0 (B,K) the concentrations, g1 ignored (may be NULL);
+ *   MIMO_VI_GATING_STICK_BREAKING: g0 (B,K) the gammas, g1 (B,K) the deltas.
+ *   basis: pa (B,K,dx), pb (B,K), pc (B,K,dx,dx), pd (B,K) = (kappa m, kappa, psi^-1 + kappa m m', nu - dx), basis_logZ (B,K).
+ *   experts: ma (B,K,dy,dc), mb (B,K,dc,dc), mc (B,K,dy,dy), md (B,K) = (M K, K, psi^-1 + M K M', nu - dy - 1 + dc),
+ *   experts_logZ (B,K).  Every element finite and dx, dy >= 1 with dx + dy equal to the uploaded Dz (MIMO_E_INVALID otherwise). */
+#define MIMO_VI_GATING_DIRICHLET 0
+#define MIMO_VI_GATING_STICK_BREAKING 1
+int mimo_vi_ilr_prior_batched(mimo_ctx* ctx, int K, int dx, int dy, int gating_kind, const double* g0, const double* g1,
+                              const double* pa, const double* pb, const double* pc, const double* pd, const double* basis_logZ,
+                              const double* ma, const double* mb, const double* mc, const double* md, const double* experts_logZ);
+
+/* `iters` mean-field iterations of every active problem with the contract of mimo_vi_run_batched (trace, n_done, status, tol,
+ * flags, chunked runs with identical bits).  Per iteration and (problem, component): the joint statistics block is cut as
+ * split_joint_stats cuts it; the basis block runs the Normal-Wishart update; the expert block forms a = ma + S_yx~,
+ * Kq = mb + S_x~x~, c = mc + S_yy, d = md + n, factorises Kq and C = c - a Kq^-1 a', and gives M, psi, nu = d + dy + 1 - dc, the
+ * expected statistics and the canonical form over z; the two forms are summed as embed_joint sums them and written into the
+ * operand image; then the gating update with E[log pi], the batched pass, its reduction and the bound.
+ * Replaces: per model and iteration, what meanfield_iteration runs between two data passes (mimo/mixtures/ilr.py:178-189,211-226):
+ *   meanfield_update of basis, models and gating (bayesian.py:78-83,151-159,225-230,839-844; composite.py:50-72,106-118,577-599,635-647;
+ *   wishart.py:139-143; dirichlet.py:31-33,85-87,201-204), the expected log-densities (bayesian.py:287-301,933-947), the bound's
+ *   prior terms (bayesian.py:93-96,173-176,258-265,854-858; composite.py:95-98,120-128,622-625,649-664; wishart.py:129-132;
+ *   dirichlet.py:78-97,195-214) and the stopping rule — the arithmetic of mimo_host_nw_vi and mimo_host_mnw_vi (affine), restated
+ *   for the device.
+ *   status bit 1: one of the three factorised blocks of a component (the basis' c - kappa m m', Kq, C) had a pivot that was not
+ *   positive and finite; bit 2: a joint canonical form, a term of the bound or the bound itself was not finite. */
+int mimo_vi_ilr_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status);
+
+/* The posterior blocks of the loop, per problem b at out + b * count, in this part order (dc = dx + 1, Dz = dx + dy):
+ *   gating   g0 K (alpha | gamma) | g1 K (0 | delta) | E[log pi] K
+ *   basis    qa K dx | qb K | qc K dx^2 | qd K | mus K dx | psis K dx^2 | nus K | half_logdet_psi K | cc K | bb K dx | W K dx^2 | E2 K | E4 K
+ *   experts  a K dy dc | Kq K dc^2 | c K dy^2 | d K | Ms K dy dc | psis K dy^2 | nus K | half_logdet_psi K | Kq^-1 K dc^2 |
+ *            E1 K dy dc | E2 K dc^2 | E4 K | cc K | bb K Dz | W K Dz^2
+ *   joint    c_total K | bb K Dz | W K Dz^2
+ *   bound    the gating term, the summed basis terms, the summed expert terms
+ * (mimo/distributions/composite.py:50-72,106-128,577-599,635-647; mixtures/ilr.py:178-189).  Zeros for a problem that has not
+ * finished an iteration. */
+int mimo_vi_ilr_get_batched(mimo_ctx* ctx, int K, double* out);
+
 /* Posterior-predictive mixture moments of B ILR models in one launch: per problem b what mimo_predict_flags returns on a
  * context whose resident rows are (X_b - shift_b) / scale_b, bit for bit, and the same bits whatever else is in the batch.
  * Replaces: the loop `for ilr in ilrs: ilr.meanfield_prediction(input)` of examples/ilr/evaluate_sinc_parallel.py:196-201 over

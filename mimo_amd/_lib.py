@@ -49,6 +49,9 @@ SIGNATURES = {
     "mimo_vi_run_batched": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp]),
     "mimo_vi_get_batched": (C.c_int, [_vp, C.c_int, _vp]),
     "mimo_vi_get_theta_batched": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "mimo_vi_ilr_prior_batched": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 12),
+    "mimo_vi_ilr_run_batched": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp]),
+    "mimo_vi_ilr_get_batched": (C.c_int, [_vp, C.c_int, _vp]),
     "mimo_estep_weighted": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "mimo_wait": (C.c_int, [_vp, _vp, _vp]),
     "mimo_gibbs_labels": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_uint64, C.c_uint64, _vp,

@@ -489,6 +489,106 @@ class BatchedHipEngine:
         S = stats[:self.B * K * (1 + D + D * D)].reshape(self.B, K, 1 + D + D * D)
         return theta, self._stats_list(S, K), stats[S.size:].reshape(self.B, 3).copy()
 
+    # ---- device-resident VI of mixtures of linear-Gaussian experts (mimo_vi_ilr_prior_batched / _run_ / _get_) ----
+    # gating | basis (the GMM loop's names) | experts (m_*) | joint | bound
+    VI_ILR_PARTS = ('g0', 'g1', 'e_log_pi',
+                    'qa', 'qb', 'qc', 'qd', 'mus', 'psis', 'nus', 'hld', 'cc', 'bb', 'W', 'E2', 'E4',
+                    'm_a', 'm_Kq', 'm_c', 'm_d', 'm_Ms', 'm_psis', 'm_nus', 'm_hld', 'm_Kinv', 'm_E1', 'm_E2', 'm_E4', 'm_cc',
+                    'm_bb', 'm_W',
+                    'c_total', 'j_bb', 'j_W', 'vlb')
+    VI_GATINGS = {'dirichlet': 0, 'stick-breaking': 1}
+
+    @staticmethod
+    def _vi_ilr_part_shapes(K, dx, dy):
+        dc, D = dx + 1, dx + dy
+        s, x, xx = (K,), (K, dx), (K, dx, dx)
+        return ((K,), (K,), (K,),
+                x, s, xx, s, x, xx, s, s, s, x, xx, s, s,
+                (K, dy, dc), (K, dc, dc), (K, dy, dy), s, (K, dy, dc), (K, dy, dy), s, s, (K, dc, dc), (K, dy, dc), (K, dc, dc), s, s,
+                (K, D), (K, D, D),
+                s, (K, D), (K, D, D), (3,))
+
+    def vi_ilr_set_prior(self, gating, g0, g1, basis, experts):
+        """The priors of the B problems' mixtures of linear-Gaussian experts over z = [x, y], copied to the device once.
+        gating: 'dirichlet' (g0 (B, K) the concentrations, g1 None) or 'stick-breaking' (g0 the gammas, g1 the deltas, both
+        (B, K)).  basis = (pa (B, K, dx), pb (B, K), pc (B, K, dx, dx), pd (B, K), log Z (B, K)): the Normal-Wishart natural
+        parameters over x and their log-partitions.  experts = (ma (B, K, dy, dx + 1), mb (B, K, dx + 1, dx + 1),
+        mc (B, K, dy, dy), md (B, K), log Z (B, K)): the matrix-normal-Wishart natural parameters of the affine experts.
+        dx + dy must be the uploaded Dz; everything finite.  Resets the loop as vi_set_prior does (and replaces a GMM prior
+        block: one family is resident at a time).  An upload drops the priors."""
+        if gating not in self.VI_GATINGS:
+            raise ValueError(f"gating = {gating!r} is not one of {sorted(self.VI_GATINGS)}")
+        stick = gating == 'stick-breaking'
+        if (g1 is None) == stick:
+            raise ValueError("g1 (the deltas) goes with a stick-breaking gating and with that alone")
+        if len(basis) != 5 or len(experts) != 5:
+            raise ValueError("basis and experts are 5 arrays each: the four natural parameters and the log-partitions")
+        g0 = _f64(g0)
+        if g0.ndim != 2:
+            raise ValueError(f"g0 must be (B, K), got shape {g0.shape}")
+        B, K = g0.shape
+        if B != self.B:
+            raise ValueError(f"priors for {B} problems, {self.B} uploaded")
+        g1 = _f64(g1) if stick else None
+        pa, pb, pc, pd, plz = (_f64(v) for v in basis)
+        ma, mb, mc, md, mlz = (_f64(v) for v in experts)
+        if pa.ndim != 3 or ma.ndim != 4:
+            raise ValueError(f"pa must be (B, K, dx) and ma (B, K, dy, dx + 1), got shapes {pa.shape} and {ma.shape}")
+        dx, dy = pa.shape[2], ma.shape[2]
+        if dx < 1 or dy < 1 or dx + dy != self.D:
+            raise ValueError(f"dx = {dx} and dy = {dy} must be >= 1 and add up to the uploaded Dz = {self.D}")
+        dc = dx + 1
+        want = ((B, K),) * (2 if stick else 1) + ((B, K, dx), (B, K), (B, K, dx, dx), (B, K), (B, K),
+                                                  (B, K, dy, dc), (B, K, dc, dc), (B, K, dy, dy), (B, K), (B, K))
+        parts = ((g0, g1) if stick else (g0,)) + (pa, pb, pc, pd, plz, ma, mb, mc, md, mlz)
+        got = tuple(v.shape for v in parts)
+        if got != want:
+            raise ValueError(f"prior shapes {got} do not match B={B}, K={K}, dx={dx}, dy={dy}: {want}")
+        if not all(np.all(np.isfinite(v)) for v in parts):
+            raise ValueError("the priors must be finite")
+        self._check(self._lib.mimo_vi_ilr_prior_batched(
+            self._ctx, K, dx, dy, self.VI_GATINGS[gating], _ptr(g0), _ptr(g1) if stick else None,
+            _ptr(pa), _ptr(pb), _ptr(pc), _ptr(pd), _ptr(plz), _ptr(ma), _ptr(mb), _ptr(mc), _ptr(md), _ptr(mlz)))
+        self._vi_ilr_dims = (dx, dy)
+
+    def vi_ilr_run(self, K, iters, tol):
+        """vi_run for the mixtures of linear-Gaussian experts whose priors vi_ilr_set_prior uploaded
+        (mimo_vi_ilr_run_batched): the same returns, the same stopping rule, the same persistence across calls.  Status bit
+        1: one of a component's three factorised blocks (the basis block, Kq, C) was not positive definite; bit 2: a joint
+        canonical form or a term of the bound was not finite."""
+        K, iters, tol = int(K), int(iters), float(tol)
+        if K < 1 or iters < 1:
+            raise ValueError(f"K = {K} and iters = {iters} must be >= 1")
+        if not tol >= 0.:
+            raise ValueError(f"tol = {tol} must be >= 0")
+        trace = np.empty((iters, self.B))
+        n_done = np.empty(self.B, dtype=np.int32)
+        status = np.empty(self.B, dtype=np.int32)
+        self._check(self._lib.mimo_vi_ilr_run_batched(self._ctx, K, iters, tol, 0, _ptr(trace), _ptr(n_done), _ptr(status)))
+        return trace, n_done, status
+
+    def vi_ilr_state(self, K):
+        """The posterior blocks the ILR loop holds, as a dict of arrays with a leading problem axis (VI_ILR_PARTS):
+        g0, g1 (alpha and zeros, or gammas and deltas), e_log_pi; the basis parts under the GMM loop's names (qa .. E4, over
+        x); the experts' m_a, m_Kq, m_c, m_d (natural parameters), m_Ms, m_psis, m_nus, m_hld, m_Kinv, m_E1, m_E2, m_E4 and
+        their canonical form m_cc, m_bb, m_W over z; the joint c_total, j_bb, j_W (the next pass's canonical form); vlb
+        (B, 3) = the gating term, the summed basis terms, the summed expert terms of the bound."""
+        K = int(K)
+        if K < 1:
+            raise ValueError(f"K = {K} must be >= 1")
+        dims = getattr(self, '_vi_ilr_dims', None)
+        if dims is None:
+            raise ValueError("no ILR prior block was set (vi_ilr_set_prior)")
+        shapes = self._vi_ilr_part_shapes(K, *dims)
+        sizes = [int(np.prod(s)) for s in shapes]
+        out = np.empty((self.B, sum(sizes)))
+        self._check(self._lib.mimo_vi_ilr_get_batched(self._ctx, K, _ptr(out)))
+        state, o = {}, 0
+        for name, shape, n in zip(self.VI_ILR_PARTS, shapes, sizes):
+            state[name] = out[:, o:o + n].reshape((self.B,) + shape).copy()
+            o += n
+        return state
+
     def get_row_weights(self):
         """The resident row weights (the last weighted pass's, or those of outer_responsibilities): a list of B arrays (N_b,)."""
         out = np.empty(max(int(self.row_off[-1]), 1))

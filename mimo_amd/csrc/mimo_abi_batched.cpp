@@ -27,6 +27,7 @@
 #include "mimo_kernels.h"
 #include "mimo_predict_batched.h"
 #include "mimo_vi_batched.h"
+#include "mimo_vi_ilr_batched.h"
 
 #include <algorithm>
 #include <cmath>
@@ -543,10 +544,20 @@ int mimo_random_resp_stats_batched(mimo_ctx* ctx, int K, const uint64_t* seeds, 
 // doubles the loop's int32 words take at the front of vi_loop
 static size_t vi_words_len(int B) { return ((size_t)kViWords * B + 1) / 2; }
 
-// What the three entry points share beyond batched_ready: a prior block of this K
-static int vi_ready(mimo_ctx* ctx, int K, const char* me) {
+// What the loop's entry points share beyond batched_ready: a prior block of this K and of the caller's family (0: mixtures of
+// Gaussians, 1: mixtures of linear-Gaussian experts, -1: either)
+static const char* vi_family_name(int family) {
+  return family == 1 ? "mixtures of linear-Gaussian experts (mimo_vi_ilr_prior_batched)"
+                     : "mixtures of Gaussians (mimo_vi_prior_batched)";
+}
+
+static int vi_ready(mimo_ctx* ctx, int K, const char* me, int family = 0) {
   if (!ctx->vi_prior_valid || !ctx->vi_prior)
-    return fail(ctx, MIMO_E_STATE, "%s: no prior block is resident (call mimo_vi_prior_batched; an upload drops it)", me);
+    return fail(ctx, MIMO_E_STATE, "%s: no prior block is resident (call %s; an upload drops it)", me,
+                family == 1 ? "mimo_vi_ilr_prior_batched" : "mimo_vi_prior_batched");
+  if (family >= 0 && ctx->vi_family != family)
+    return fail(ctx, MIMO_E_STATE, "%s: the resident prior block is that of %s, this call runs %s", me,
+                vi_family_name(ctx->vi_family), vi_family_name(family));
   if (ctx->vi_K != K)
     return fail(ctx, MIMO_E_STATE, "%s: the resident prior block is that of K = %d, not K = %d", me, ctx->vi_K, K);
   return MIMO_OK;
@@ -617,20 +628,24 @@ int mimo_vi_prior_batched(mimo_ctx* ctx, int K, const double* alpha0, const doub
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // the sources are pageable host memory
   ctx->vi_prior_valid = true;
   ctx->vi_K = K;
+  ctx->vi_family = 0;
   return MIMO_OK;
   });
 }
 
-int mimo_vi_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status) {
+static ViIlrArgs vi_ilr_args(mimo_ctx* ctx, int K);
+
+// The loop of both families: `family` chooses the update and the gating kernel; the pass, its reduction and the finish are shared
+static int vi_run(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status,
+                  const char* me, int family) {
   return guarded(ctx, [&]() -> int {
-  const char* const me = "mimo_vi_run_batched";
   int rc = bind(ctx); if (rc) return rc;
   if ((rc = batched_ready(ctx, K, me))) return rc;
   if (flags != 0) return fail(ctx, MIMO_E_INVALID, "%s: flags 0x%x: none are defined", me, flags);
   if (iters < 1 || iters > 65536) return fail(ctx, MIMO_E_INVALID, "%s: iters = %d outside [1, 65536]", me, iters);
   if (!(tol >= 0.0)) return fail(ctx, MIMO_E_INVALID, "%s: tol = %g must be >= 0", me, tol);
   if (!trace || !n_done || !status) return fail(ctx, MIMO_E_INVALID, "%s: trace, n_done and status must be non-NULL", me);
-  if ((rc = vi_ready(ctx, K, me))) return rc;
+  if ((rc = vi_ready(ctx, K, me, family))) return rc;
   if (!ctx->batch_stats_valid || !ctx->S_d)
     return fail(ctx, MIMO_E_STATE, "%s: no statistics are resident (run a batched pass that returns statistics first; an upload and "
                 "every call that returns something else drop them)", me);
@@ -650,14 +665,24 @@ int mimo_vi_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int flags, 
   if ((rc = ensure_partials(ctx, K, (size_t)G))) return rc;
   leaves(ctx, kPassTables, 0);
 
-  ViArgs va = vi_args(ctx, K);
+  ViIlrArgs ia{};
+  if (family == 1) {
+    ia = vi_ilr_args(ctx, K);
+    ia.loop.tol = tol;
+  }
+  ViArgs va = family == 1 ? ia.loop : vi_args(ctx, K);
   va.tol = tol;
   BatchedArgs a = batched_args(ctx, K);
   a.theta = ctx->vi_theta;
   HIP_TRY(ctx, hipMemsetAsync(va.words + (size_t)kViDone * B, 0, (size_t)B * sizeof(int32_t), ctx->stream));
   for (int it = 0; it < iters; ++it) {
-    HIP_TRY(ctx, launch_vi_update(va, ctx->stream));
-    HIP_TRY(ctx, launch_vi_gating(va, ctx->stream));
+    if (family == 1) {
+      HIP_TRY(ctx, launch_vi_ilr_update(ia, ctx->stream));
+      HIP_TRY(ctx, launch_vi_ilr_gating(ia, ctx->stream));
+    } else {
+      HIP_TRY(ctx, launch_vi_update(va, ctx->stream));
+      HIP_TRY(ctx, launch_vi_gating(va, ctx->stream));
+    }
     HIP_TRY(ctx, launch_batched(a, G, ctx->stream));
     if ((rc = batched_reduce(ctx, K, ctx->batch_wg_off_d, 0, true))) return rc;
     HIP_TRY(ctx, launch_vi_finish(va, it, ctx->stream));
@@ -672,14 +697,19 @@ int mimo_vi_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int flags, 
   });
 }
 
-int mimo_vi_get_batched(mimo_ctx* ctx, int K, double* out) {
+int mimo_vi_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status) {
+  return vi_run(ctx, K, iters, tol, flags, trace, n_done, status, "mimo_vi_run_batched", 0);
+}
+
+// Every problem's current posterior block (of `per` doubles in the family's layout) to the host
+static int vi_get(mimo_ctx* ctx, int K, double* out, const char* me, int family) {
   return guarded(ctx, [&]() -> int {
-  const char* const me = "mimo_vi_get_batched";
   int rc = bind(ctx); if (rc) return rc;
   if ((rc = batched_ready(ctx, K, me))) return rc;
   if (!out) return fail(ctx, MIMO_E_INVALID, "%s: out is NULL", me);
-  if ((rc = vi_ready(ctx, K, me))) return rc;
-  const size_t B = (size_t)ctx->batch_B, per = (size_t)ViLayout{K, ctx->D}.count();
+  if ((rc = vi_ready(ctx, K, me, family))) return rc;
+  const size_t B = (size_t)ctx->batch_B;
+  const size_t per = family == 1 ? (size_t)ViIlrLayout{K, ctx->vi_dx, ctx->vi_dy}.count() : (size_t)ViLayout{K, ctx->D}.count();
   std::vector<double> both(2 * B * per);
   std::vector<int32_t> words((size_t)kViWords * B);
   HIP_TRY(ctx, hipMemcpyAsync(both.data(), ctx->vi_post, both.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -693,13 +723,15 @@ int mimo_vi_get_batched(mimo_ctx* ctx, int K, double* out) {
   });
 }
 
+int mimo_vi_get_batched(mimo_ctx* ctx, int K, double* out) { return vi_get(ctx, K, out, "mimo_vi_get_batched", 0); }
+
 int mimo_vi_get_theta_batched(mimo_ctx* ctx, int K, double* theta, double* stats) {
   return guarded(ctx, [&]() -> int {
   const char* const me = "mimo_vi_get_theta_batched";
   int rc = bind(ctx); if (rc) return rc;
   if ((rc = batched_ready(ctx, K, me))) return rc;
   if (!theta && !stats) return fail(ctx, MIMO_E_INVALID, "%s: theta and stats are both NULL", me);
-  if ((rc = vi_ready(ctx, K, me))) return rc;
+  if ((rc = vi_ready(ctx, K, me, -1))) return rc;
   if (stats && (!ctx->batch_stats_valid || ctx->batch_stats_K != K || !ctx->S_d))
     return fail(ctx, MIMO_E_STATE, "%s: no statistics of K = %d are resident", me, K);
   const size_t B = (size_t)ctx->batch_B;
@@ -710,6 +742,115 @@ int mimo_vi_get_theta_batched(mimo_ctx* ctx, int K, double* theta, double* stats
   return MIMO_OK;
   });
 }
+
+// ------------------------------------------------------------------------------------------
+// Device-resident batched VI for mixtures of linear-Gaussian experts (mimo_vi_ilr_batched.hip)
+// ------------------------------------------------------------------------------------------
+// The loop lives in the buffers of the GMM loop (one family is resident at a time: vi_family):
+//   vi_prior  [g0 B K | g1 B K | basis pa B K dx | pb B K | pc B K dx^2 | pd B K | log Z B K |
+//              experts ma B K dy dc | mb B K dc^2 | mc B K dy^2 | md B K | log Z B K]
+//   vi_post   [2][B][ViIlrLayout::count()]
+//   vi_work   [basis terms B K | expert terms B K | prior terms B | last bound B]
+static ViIlrArgs vi_ilr_args(mimo_ctx* ctx, int K) {
+  const size_t B = (size_t)ctx->batch_B, BK = B * K;
+  const size_t dx = (size_t)ctx->vi_dx, dy = (size_t)ctx->vi_dy, dc = dx + 1;
+  ViIlrArgs a{};
+  const double* p = ctx->vi_prior;
+  a.g0 = p; p += BK;
+  a.g1 = p; p += BK;
+  a.pa = p; p += BK * dx;
+  a.pb = p; p += BK;
+  a.pc = p; p += BK * dx * dx;
+  a.pd = p; p += BK;
+  a.plz = p; p += BK;
+  a.ma = p; p += BK * dy * dc;
+  a.mb = p; p += BK * dc * dc;
+  a.mc = p; p += BK * dy * dy;
+  a.md = p; p += BK;
+  a.mlz = p;
+  a.term_b = ctx->vi_work;
+  a.term_m = ctx->vi_work + BK;
+  a.dx = ctx->vi_dx; a.dy = ctx->vi_dy; a.gating = ctx->vi_gating;
+  ViArgs& l = a.loop;
+  l.S = ctx->S_d;
+  l.scalars = ctx->S_d + batch_stats_len(ctx, K);
+  l.alpha0 = a.g0; l.pa = a.pa; l.pb = a.pb; l.pc = a.pc; l.pd = a.pd; l.plz = a.plz;      // (vi_finish_kernel reads none of them)
+  l.post = ctx->vi_post;
+  l.term = a.term_b;
+  l.prior_terms = ctx->vi_work + 2 * BK;
+  l.last = ctx->vi_work + 2 * BK + B;
+  l.words = reinterpret_cast<int32_t*>(ctx->vi_loop.p);
+  l.theta = ctx->vi_theta;
+  l.trace = ctx->vi_loop + vi_words_len(ctx->batch_B);
+  l.B = ctx->batch_B; l.K = K; l.D = ctx->D; l.K16 = (K + 15) / 16; l.NS = ctx->F16 / 4;
+  l.tol = 0.0;
+  return a;
+}
+
+int mimo_vi_ilr_prior_batched(mimo_ctx* ctx, int K, int dx, int dy, int gating_kind, const double* g0, const double* g1,
+                              const double* pa, const double* pb, const double* pc, const double* pd, const double* basis_logZ,
+                              const double* ma, const double* mb, const double* mc, const double* md, const double* experts_logZ) {
+  return guarded(ctx, [&]() -> int {
+  const char* const me = "mimo_vi_ilr_prior_batched";
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, me))) return rc;
+  if (gating_kind != MIMO_VI_GATING_DIRICHLET && gating_kind != MIMO_VI_GATING_STICK_BREAKING)
+    return fail(ctx, MIMO_E_INVALID, "%s: gating_kind = %d is neither MIMO_VI_GATING_DIRICHLET nor MIMO_VI_GATING_STICK_BREAKING", me,
+                gating_kind);
+  if (dx < 1 || dy < 1 || dx + dy != ctx->D)
+    return fail(ctx, MIMO_E_INVALID, "%s: dx = %d and dy = %d must be >= 1 and add up to the uploaded Dz = %d", me, dx, dy, ctx->D);
+  const bool stick = gating_kind == MIMO_VI_GATING_STICK_BREAKING;
+  if (!g0 || (stick && !g1) || !pa || !pb || !pc || !pd || !basis_logZ || !ma || !mb || !mc || !md || !experts_logZ)
+    return fail(ctx, MIMO_E_INVALID, "%s: g0, (stick-breaking: g1,) the basis' pa, pb, pc, pd, basis_logZ and the experts' ma, mb, mc, "
+                "md, experts_logZ must be non-NULL", me);
+  const size_t B = (size_t)ctx->batch_B, BK = B * K, sx = (size_t)dx, sy = (size_t)dy, sc = sx + 1;
+  const std::vector<double> zeros(stick ? 0 : BK, 0.0);
+  const double* const parts[12] = {g0, stick ? g1 : zeros.data(), pa, pb, pc, pd, basis_logZ, ma, mb, mc, md, experts_logZ};
+  const char* const names[12] = {"g0", "g1", "pa", "pb", "pc", "pd", "basis_logZ", "ma", "mb", "mc", "md", "experts_logZ"};
+  const size_t lens[12] = {BK, BK, BK * sx, BK, BK * sx * sx, BK, BK, BK * sy * sc, BK * sc * sc, BK * sy * sy, BK, BK};
+  size_t nprior = 0;
+  for (int t = 0; t < 12; ++t) {
+    nprior += lens[t];
+    for (size_t i = 0; i < lens[t]; ++i)
+      if (!std::isfinite(parts[t][i]))
+        return fail(ctx, MIMO_E_INVALID, "%s: %s of problem %d holds a NaN or an infinity", me, names[t], (int)(i / (lens[t] / B)));
+  }
+  ctx->vi_prior_valid = false;
+  const ViIlrLayout L{K, dx, dy};
+  const size_t npost = 2 * B * (size_t)L.count(), nwork = 2 * BK + 2 * B;
+  const size_t ntheta = image_len(ctx, K), nwords = vi_words_len(ctx->batch_B);
+  if ((rc = ctx->vi_prior.ensure(ctx, nprior))) return rc;
+  if ((rc = ctx->vi_post.ensure(ctx, npost))) return rc;
+  if ((rc = ctx->vi_work.ensure(ctx, nwork))) return rc;
+  if ((rc = ctx->vi_theta.ensure(ctx, ntheta))) return rc;
+  if ((rc = ctx->vi_loop.ensure(ctx, nwords))) return rc;
+  // the loop state of mimo_vi_prior_batched: every problem active, nothing appended, status clear, slot 0 current; zero blocks,
+  // zero images
+  std::vector<int32_t> words((size_t)kViWords * B, 0);
+  std::fill(words.begin() + (size_t)kViActive * B, words.begin() + (size_t)(kViActive + 1) * B, 1);
+  double* q = ctx->vi_prior;
+  for (int t = 0; t < 12; ++t) {
+    HIP_TRY(ctx, hipMemcpyAsync(q, parts[t], lens[t] * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    q += lens[t];
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_loop, words.data(), words.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_post, 0, npost * sizeof(double), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_work, 0, nwork * sizeof(double), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_theta, 0, ntheta * sizeof(double), ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // the sources are pageable host memory
+  ctx->vi_prior_valid = true;
+  ctx->vi_K = K;
+  ctx->vi_family = 1;
+  ctx->vi_dx = dx; ctx->vi_dy = dy; ctx->vi_gating = stick ? kViGatingStick : kViGatingDirichlet;
+  return MIMO_OK;
+  });
+}
+
+int mimo_vi_ilr_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status) {
+  return vi_run(ctx, K, iters, tol, flags, trace, n_done, status, "mimo_vi_ilr_run_batched", 1);
+}
+
+int mimo_vi_ilr_get_batched(mimo_ctx* ctx, int K, double* out) { return vi_get(ctx, K, out, "mimo_vi_ilr_get_batched", 1); }
 
 // ------------------------------------------------------------------------------------------
 // Batched prediction (mimo_predict_batched.hip)

@@ -157,6 +157,10 @@ struct mimo_ctx {
   // to the next upload
   bool vi_prior_valid = false;
   int vi_K = 0;
+  // which family's prior block is resident: 0 mixtures of Gaussians (the layouts below), 1 mixtures of linear-Gaussian experts
+  // (mimo_vi_ilr_batched.h: ViIlrArgs / ViIlrLayout in the same buffers), with its dx, dy and gating kind
+  int vi_family = 0;
+  int vi_dx = 0, vi_dy = 0, vi_gating = 0;
   Buf<double> vi_prior;                                    // [alpha0 B K | pa B K D | pb B K | pc B K D D | pd B K | log Z B K]
   Buf<double> vi_post;                                     // [2][B][ViLayout::count()]
   Buf<double> vi_work;                                     // [terms B K | prior terms B | last bound B]

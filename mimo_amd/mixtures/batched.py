@@ -220,6 +220,136 @@ def meanfield_coordinate_descent_batched(models, data, randomize=True, maxiter=2
     return vlbs
 
 
+def _ilr_resident_reason(model):
+    """Why the device-resident ILR loop does not take this model (None: it does) -> (reason, gating kind): affine, untied
+    matrix-normal-Wishart experts, an untied Normal-Wishart basis, a Dirichlet or a stick-breaking gating, within the batched
+    pass's own limits."""
+    from mimo_amd.distributions.bayesian import (CategoricalWithDirichlet, CategoricalWithStickBreaking,
+                                                 StackedGaussiansWithNormalWisharts,
+                                                 StackedLinearGaussiansWithMatrixNormalWisharts)
+    from mimo_amd.distributions.composite import StackedMatrixNormalWisharts, StackedNormalWisharts
+    from mimo_amd.distributions.gating import Dirichlet, TruncatedStickBreaking
+    if type(model) is not BayesianMixtureOfLinearGaussians:
+        return f"{type(model).__name__} is not a BayesianMixtureOfLinearGaussians", None
+    gating, basis, experts = model.gating, model.basis, model.models
+    kind = None
+    if type(gating) is CategoricalWithDirichlet and type(gating.prior) is Dirichlet and type(gating.posterior) is Dirichlet:
+        kind = 'dirichlet'
+    elif type(gating) is CategoricalWithStickBreaking and type(gating.prior) is TruncatedStickBreaking\
+            and type(gating.posterior) is TruncatedStickBreaking:
+        kind = 'stick-breaking'
+    if kind is None:
+        return "the gating is neither a CategoricalWithDirichlet (Dirichlet) nor a CategoricalWithStickBreaking "\
+               "(TruncatedStickBreaking)", None
+    if type(basis) is not StackedGaussiansWithNormalWisharts or type(basis.prior) is not StackedNormalWisharts\
+            or type(basis.posterior) is not StackedNormalWisharts:
+        return f"the basis is {type(basis).__name__} with {type(basis.prior).__name__} (tied or other blocks), not "\
+               "StackedGaussiansWithNormalWisharts with StackedNormalWisharts", kind
+    if type(experts) is not StackedLinearGaussiansWithMatrixNormalWisharts\
+            or type(experts.prior) is not StackedMatrixNormalWisharts or type(experts.posterior) is not StackedMatrixNormalWisharts:
+        return f"the experts are {type(experts).__name__} with {type(experts.prior).__name__} (tied or other blocks), not "\
+               "StackedLinearGaussiansWithMatrixNormalWisharts with StackedMatrixNormalWisharts", kind
+    if not model.affine or experts.prior.column_dim != model.input_dim + 1:
+        return "the experts are not affine (column_dim = input_dim + 1)", kind
+    dx, dy, K = model.input_dim, model.output_dim, model.size
+    if dx < 1 or dy < 1 or dx + dy > 16 or not 1 <= K <= 128:
+        return f"input_dim = {dx}, output_dim = {dy}, size = {K} are outside dx, dy >= 1, dx + dy <= 16, K <= 128", kind
+    return None, kind
+
+
+def meanfield_coordinate_descent_batched_ilr(models, data, randomize=True, maxiter=250, tol=1e-8, init_rng='host', seeds=None,
+                                             engine=None, chunk=8):
+    """Mean-field coordinate descent of B BayesianMixtureOfLinearGaussians with everything between two passes on the device
+    (BatchedHipEngine.vi_ilr_run): the update of the basis, of the experts and of the gating from the resident joint
+    statistics, the joint canonical form, the prior terms of the bound and the stopping rule, `chunk` iterations per call.
+    What meanfield_coordinate_descent_batched(models, data, sample_likelihood=False) computes with a host step per model and
+    iteration; models / data / randomize / init_rng / seeds / engine as there.  The start is the same (upload, then the random
+    start or one plain pass); then the priors go up once, the loop runs in chunks, and the posteriors come back once and are
+    written into the models as the host route leaves them (gating, basis, experts with their memos; then one
+    _refresh_likelihoods() per model).  Returns the B ELBO traces.
+
+    Covered: affine, untied experts (StackedLinearGaussiansWithMatrixNormalWisharts over StackedMatrixNormalWisharts with
+    column_dim = input_dim + 1), an untied Normal-Wishart basis, and one gating kind for the whole batch, Dirichlet or
+    stick-breaking; input_dim + output_dim <= 16, size <= 128.  Anything else raises ValueError naming the model and the
+    reason before anything is uploaded or drawn.  A problem one of whose blocks is not positive definite raises
+    numpy.linalg.LinAlgError naming the problem; one whose canonical form or bound is not finite raises FloatingPointError."""
+    from mimo_amd.utils.abstraction import Statistics as Stats
+    models, data = list(models), list(data)
+    B = len(models)
+    if B == 0 or len(data) != B:
+        raise ValueError(f"{B} models and {len(data)} data sets")
+    kinds = []
+    for i, m in enumerate(models):
+        why, kind = _ilr_resident_reason(m)
+        if why is not None:
+            raise ValueError(f"the resident ILR loop does not cover model {i}: {why}")
+        kinds.append(kind)
+    if any(k != kinds[0] for k in kinds):
+        raise ValueError(f"the resident ILR loop takes one gating kind per batch, got {kinds}")
+    models, data, _ = _check_models(models, data)
+    seeds = _per_model(seeds, B, 0, "seeds")
+    maxiter, chunk = int(maxiter), int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk = {chunk} < 1")
+    if init_rng not in ('host', 'philox'):
+        raise ValueError(init_rng)
+    if engine is None:
+        engine = BatchedHipEngine(getattr(models[0].engine, 'device', 0))
+    engine.upload([_rows(m, d) for m, d in zip(models, data)])
+    K, stick = models[0].size, kinds[0] == 'stick-breaking'
+    if randomize:
+        _random_start(engine, K, init_rng, seeds)
+    else:
+        engine.estep(*_stack([m.canonical_expected() for m in models]))
+    vlbs = [[] for _ in range(B)]
+    if maxiter <= 0:
+        return vlbs
+
+    arr = lambda v: np.asarray(v, dtype=float)
+    bblocks = [_native_sweep._prior_block(m.basis.prior) for m in models]
+    mblocks = [_native_sweep._prior_block(m.models.prior) for m in models]
+    engine.vi_ilr_set_prior(kinds[0],
+                            np.stack([arr(m.gating.prior.gammas if stick else m.gating.prior.alphas) for m in models]),
+                            np.stack([arr(m.gating.prior.deltas) for m in models]) if stick else None,
+                            tuple(np.stack([blk[j] for blk in bblocks]) for j in range(5)),
+                            tuple(np.stack([blk[j] for blk in mblocks]) for j in range(5)))
+    left, stopped = maxiter, np.zeros(B, dtype=bool)
+    while left > 0 and not stopped.all():
+        n = min(chunk, left)
+        trace, n_done, status = engine.vi_ilr_run(K, n, tol)
+        left -= n
+        for i in np.flatnonzero(status):
+            if status[i] & 1:
+                raise np.linalg.LinAlgError(f"problem {int(i)}: Matrix is not positive definite (a block of a component's "
+                                            "posterior: the basis' c - kappa m m', the experts' K or c - M K M')")
+            raise FloatingPointError(f"problem {int(i)}: the canonical form or the bound of its posterior is not finite")
+        for i in range(B):
+            vlbs[i].extend(float(v) for v in trace[:int(n_done[i]), i])
+            stopped[i] = n_done[i] < n or (len(vlbs[i]) > 1 and abs(vlbs[i][-1] - vlbs[i][-2]) < tol)
+    state = engine.vi_ilr_state(K)
+    part = lambda name, i: np.ascontiguousarray(state[name][i])
+    for i, m in enumerate(models):
+        if not vlbs[i]:
+            continue
+        if stick:
+            m.gating.posterior.gammas, m.gating.posterior.deltas = part('g0', i), part('g1', i)
+        else:
+            m.gating.posterior.alphas = part('g0', i)
+        post = m.basis.posterior
+        qb, bb, W = part('qb', i), part('bb', i), part('W', i)
+        post.params = (part('mus', i), qb, part('psis', i), part('nus', i))
+        post._set_memo(nat=Stats([part('qa', i), qb, part('qc', i), part('qd', i)]), hld=part('hld', i),
+                       estats=(bb, part('E2', i), - 0.5 * W, part('E4', i)), canon=(part('cc', i), bb, W), native=True)
+        post = m.models.posterior
+        Kq, psis, nus = part('m_Kq', i), part('m_psis', i), part('m_nus', i)
+        post.params = (part('m_Ms', i), Kq, psis, nus)
+        post._set_memo(nat=Stats([part('m_a', i), Kq, part('m_c', i), part('m_d', i)]), hld=part('m_hld', i),
+                       estats=(part('m_E1', i), part('m_E2', i), - 0.5 * nus[:, None, None] * psis, part('m_E4', i)),
+                       canon_affine=(part('m_cc', i), part('m_bb', i), part('m_W', i)))
+        m._refresh_likelihoods()
+    return vlbs
+
+
 def _nested_setup(model, obs, engine):
     """The shared batch of a mixture of mixtures: its M inner mixtures over ONE copy of obs -> (inner mixtures, engine)."""
     from mimo_amd.mixtures.hgmm import BayesianMixtureOfMixtureOfGaussians

@@ -2,7 +2,7 @@
 data resident), on the same inputs, after warm-up; wall time per pass (each call returns synchronised host results) and the
 largest relative difference of the outputs.  Writes <out>/bench_batched.json.
 
-    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3] [--start-only | --no-start | --svi | --predict | --nested | --resident]
+    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3] [--start-only | --no-start | --svi | --predict | --nested | --resident | --resident-ilr]
 
 Also times one iteration of meanfield_coordinate_descent_batched against B solo meanfield_iteration calls at shape 1
 (24 ILR models, K = 100, dx = dy = 1), split into host time and pass time.
@@ -46,6 +46,15 @@ start are outside the clock), the difference / iters is the repetition's figure,
 traces, and the device / host error ratios of one update on tests/golden/vi_update_hp.npz (tests/vi_update_fixture.py).
 Resident shapes (--shapes 1,2,3): 1. shape 2 (B = 64, N_b = 1e4, Dz = 2, K = 4); 2. a GMM at the size of shape 1 (B = 24,
 N_b = 1600, Dz = 2, K = 100); 3. shape 3 as GMM (B = 8, N_b = 2.5e5, Dz = 12, K = 64).
+
+Resident ILR leg (--resident-ilr, on its own; writes <out>/batched_resident_ilr_vi.json): the resident leg's scheme for mixtures of
+linear-Gaussian experts — meanfield_coordinate_descent_batched_ilr against the host route
+meanfield_coordinate_descent_batched(resident=False, sample_likelihood=False) on the same ILR models and the same Philox start,
+alternated, 1 and 1 + iters iterations clocked from the return of the start pass; median, minimum and maximum of the
+repetitions' figures (use --reps 7), the largest relative difference of the traces, and the device / host error ratios of one
+update on tests/golden/vi_ilr_update_hp.npz.  Shapes (--shapes 1,2,3): 1. B = 24, N_b = 1600, dx = dy = 1, K = 100, stick-breaking
+(the reference's parallel job); 2. B = 64, N_b = 1e4, dx = dy = 1, K = 4, Dirichlet; 3. B = 8, N_b = 2.5e5, dx = 8, dy = 4, K = 64,
+stick-breaking.
 
 Shapes: 1. B = 24, N_b = 1600, Dz = 2, K = 100 (the reference's parallel ILR example); 2. B = 64, N_b = 1e4, Dz = 2, K = 4
 (restarts of the toy GMM); 3. B = 8, N_b = 2.5e5, Dz = 12, K = 64 (C4 per model)."""
@@ -714,6 +723,121 @@ def run_resident_shape(sid, reps, iters=10):
     return res
 
 
+# (B, N_b, dx, dy, K, gating): 1. the reference's parallel ILR job (examples/ilr/evaluate_sinc_parallel.py); 2., 3. shapes 2 and 3 as ILR
+RESIDENT_ILR_SHAPES = {1: (24, 1600, 1, 1, 100, 'stick-breaking'), 2: (64, 10000, 1, 1, 4, 'dirichlet'),
+                       3: (8, 250000, 8, 4, 64, 'stick-breaking')}
+
+
+def ilr_resident_models(B, N, dx, dy, K, gating, engine, seed):
+    """B mixtures of affine linear-Gaussian experts (untied blocks) on piecewise-linear data -> (build, data)."""
+    from mimo_amd.distributions import (Dirichlet, CategoricalWithDirichlet, TruncatedStickBreaking, CategoricalWithStickBreaking,
+                                        StackedNormalWisharts, StackedGaussiansWithNormalWisharts, StackedMatrixNormalWisharts,
+                                        StackedLinearGaussiansWithMatrixNormalWisharts)
+    from mimo_amd.mixtures import BayesianMixtureOfLinearGaussians
+    rng = np.random.default_rng(seed)
+    dc = dx + 1
+    data = []
+    for _ in range(B):
+        centres = rng.standard_normal((K, dx)) * 4.0
+        lab = rng.integers(K, size=N)
+        x = centres[lab] + rng.standard_normal((N, dx))
+        A = rng.standard_normal((K, dy, dc))
+        y = np.einsum('nij,nj->ni', A[lab], np.hstack([x - centres[lab], np.ones((N, 1))])) + 0.1 * rng.standard_normal((N, dy))
+        data.append((np.ascontiguousarray(x), np.ascontiguousarray(y)))
+
+    def build():
+        models = []
+        for _ in range(B):
+            if gating == 'dirichlet':
+                gate = CategoricalWithDirichlet(dim=K, prior=Dirichlet(dim=K, alphas=np.ones(K)))
+            else:
+                gate = CategoricalWithStickBreaking(K, TruncatedStickBreaking(K, np.ones(K), 10. * np.ones(K)))
+            bp = StackedNormalWisharts(K, dx, np.zeros((K, dx)), 1e-2 * np.ones(K), np.stack(K * [np.eye(dx)]), (dx + 2.) * np.ones(K))
+            mp = StackedMatrixNormalWisharts(K, dc, dy, np.zeros((K, dy, dc)), np.stack(K * [1e-2 * np.eye(dc)]),
+                                             np.stack(K * [np.eye(dy)]), (dy + 2.) * np.ones(K))
+            models.append(BayesianMixtureOfLinearGaussians(K, dx, dy, gate, StackedGaussiansWithNormalWisharts(K, dx, bp, engine=engine),
+                                                           StackedLinearGaussiansWithMatrixNormalWisharts(K, dc, dy, mp, engine=engine),
+                                                           engine=engine))
+        return models
+    return build, data
+
+
+def run_resident_ilr_shape(sid, reps, iters=10):
+    """run_resident_shape for ILR models: meanfield_coordinate_descent_batched_ilr against the host route
+    meanfield_coordinate_descent_batched(resident=False, sample_likelihood=False), with the spread of the repetitions."""
+    from mimo_amd.mixtures.batched import meanfield_coordinate_descent_batched, meanfield_coordinate_descent_batched_ilr
+    B, N, dx, dy, K, gating = RESIDENT_ILR_SHAPES[sid]
+    solo_engine, beng = HipEngine(0), BatchedHipEngine(0)
+    build, data = ilr_resident_models(B, N, dx, dy, K, gating, solo_engine, 400 + sid)
+    kw = dict(randomize=True, init_rng='philox', seeds=list(range(B)), tol=0.)
+
+    def leg(resident, engine=beng):
+        def run(n, out=None):
+            models = build()
+            clock = _StartClock(engine)
+            if resident:
+                vlbs = meanfield_coordinate_descent_batched_ilr(models, data, maxiter=n, engine=clock, chunk=8, **kw)
+            else:
+                vlbs = meanfield_coordinate_descent_batched(models, data, maxiter=n, engine=clock, sample_likelihood=False, **kw)
+            dt = time.perf_counter() - clock.t0
+            if out is not None:
+                out.append(vlbs)
+            return dt
+        return run
+    legs = {"host": leg(False), "resident": leg(True)}
+    kept = {name: [] for name in legs}
+    for name, fn in legs.items():                        # warm-up, and the traces that are compared
+        fn(1)
+        fn(1 + iters, kept[name])
+    per = {name: [] for name in legs}
+    for _ in range(reps):                                # the legs alternate within a repetition
+        for name, fn in legs.items():
+            per[name].append((fn(1 + iters) - fn(1)) / iters)
+    h, r = np.array(kept["host"][0]), np.array(kept["resident"][0])
+    res = {"resident_ilr_shape": sid, "B": B, "N_b": N, "dx": dx, "dy": dy, "K": K, "gating": gating, "iters_per_figure": iters,
+           "reps": reps, "chunk": 8, "max_rel_trace_diff": float(np.max(np.abs(r - h) / np.abs(h)))}
+    for name in legs:
+        ms = np.array(per[name]) * 1e3
+        res[name + "_ms_per_iteration"] = float(np.median(ms))
+        res[name + "_ms_per_iteration_min_max"] = [float(ms.min()), float(ms.max())]
+        res[name + "_ms_per_iteration_all"] = [float(v) for v in ms]
+    res["speedup"] = res["host_ms_per_iteration"] / res["resident_ms_per_iteration"]
+    teng = _TimedEngine(beng)
+    t0 = time.perf_counter()
+    leg(False, teng)(1 + iters)
+    total = time.perf_counter() - t0 - teng.upload_s
+    res["host_route_pass_ms_per_iteration"] = float(np.sum(teng.pass_s)) / (1 + iters) * 1e3
+    res["host_route_host_ms_per_iteration_with_start"] = (total - float(np.sum(teng.pass_s))) / (1 + iters) * 1e3
+    solo_engine.close()
+    beng.close()
+    return res
+
+
+def resident_ilr_error_ratios():
+    """One device update on every shape of tests/golden/vi_ilr_update_hp.npz: per shape and output block the largest error of the
+    device and of the host route against the 50-digit values, and their ratio."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import vi_ilr_update_fixture as fx
+    beng = BatchedHipEngine(0)
+    out = []
+    for shape in fx.shapes():
+        pr = shape["prior"]
+        beng.upload(shape["rows"])
+        beng.weighted_stats(shape["tables"])
+        beng.vi_ilr_set_prior(pr["gating"], pr["g0"], pr["g1"], pr["basis"], pr["experts"])
+        beng.vi_ilr_run(shape["K"], 1, 0.)
+        dev, host = fx.block_errors(beng.vi_ilr_state(shape["K"]), shape), fx.block_errors(fx.host_state(shape), shape)
+        blocks = {}
+        for name in fx.BLOCKS:
+            d, h = float(dev[name].max()), float(host[name].max())
+            blocks[name] = {"device": d, "host": h, "ratio": (d / h) if h > 0. else (1.0 if d == 0. else None)}
+        out.append({"B": shape["B"], "dx": shape["dx"], "dy": shape["dy"], "K": shape["K"], "gating": shape["gating"], "blocks": blocks,
+                    "worst_device": max(v["device"] for v in blocks.values()),
+                    "worst_ratio": max(v["ratio"] for v in blocks.values() if v["ratio"] is not None)})
+    beng.close()
+    return out
+
+
 def resident_error_ratios():
     """One device update on every shape of tests/golden/vi_update_hp.npz: per shape and output block the largest error of the
     device and of the host-native route against the 50-digit values, and their ratio."""
@@ -753,7 +877,21 @@ def main():
     ap.add_argument("--trace-predict", type=int, default=0, metavar="SHAPE", help="only run the batched and the solo predictions of SHAPE")
     ap.add_argument("--nested", action="store_true", help="only the nested leg (nested VI driver against the solo mixture of mixtures)")
     ap.add_argument("--resident", action="store_true", help="only the resident leg (device-resident VI loop against the host route)")
+    ap.add_argument("--resident-ilr", action="store_true",
+                    help="only the resident ILR leg (device-resident loop for mixtures of linear-Gaussian experts against the host route)")
     args = ap.parse_args()
+    if args.resident_ilr:
+        os.makedirs(args.out, exist_ok=True)
+        res = {"timings": [], "update_error_vs_50_digits": resident_ilr_error_ratios()}
+        print(json.dumps([{k: e[k] for k in ("dx", "dy", "K", "worst_device", "worst_ratio")} for e in res["update_error_vs_50_digits"]]))
+        path = os.path.join(args.out, "batched_resident_ilr_vi.json")
+        for s in args.shapes.split(","):
+            if int(s) in RESIDENT_ILR_SHAPES:
+                res["timings"].append(run_resident_ilr_shape(int(s), args.reps))
+                print(json.dumps({k: v for k, v in res["timings"][-1].items() if not k.endswith("_all")}), flush=True)
+                with open(path, "w") as f:               # (after every shape: a long run leaves what it has)
+                    json.dump(res, f, indent=1)
+        return
     if args.resident:
         os.makedirs(args.out, exist_ok=True)
         res = {"timings": [run_resident_shape(int(s), args.reps) for s in args.shapes.split(",") if int(s) in RESIDENT_SHAPES],

@@ -192,9 +192,17 @@ int mimo_abi::theta_fail(mimo_ctx* ctx, const ThetaFail& f, const char* what, in
 // never route one there).
 static int upload_theta_for(mimo_ctx* ctx, const Route& route, const double* c, const double* b, const double* W, int K, KernelArgs* a) {
   const int D = ctx->D, F16 = ctx->F16, st = ctx->structure, ZS = route_zs(K, D);
+  // a label pass over components switched off by c = -inf: the draw's relabel table (draw_label, mimo_device.h) rides behind the
+  // image, in its transfer.  (An image in the kernel arguments is the small-shape kernel with ONE lane per row: one sequential
+  // scan, whose count cannot stop on a component that adds nothing.)
+  int32_t relabel[256] = {0};
+  const bool off = a->gibbs && draw_relabel(c, K, relabel);
   auto stage = [&](const auto& pl, double* inline_img = nullptr) {
-    const int rc = stage_theta(ctx, pl, c, b, W, 1, nullptr, 0, nullptr, inline_img);
+    const bool table = off && !inline_img;
+    const int rc = stage_theta(ctx, pl, c, b, W, 1, table ? reinterpret_cast<const uint64_t*>(relabel) : nullptr, table ? (size_t)(K + 1) / 2 : 0,
+                               nullptr, inline_img);
     a->theta = ctx->theta_d;
+    a->relabel = table ? reinterpret_cast<const int32_t*>(ctx->theta_d + pl.count()) : nullptr;
     return rc;
   };
   switch (route.image) {

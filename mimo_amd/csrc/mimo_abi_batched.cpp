@@ -196,7 +196,7 @@ static BatchedArgs batched_args(mimo_ctx* ctx, int K) {
   a.ZS = (ctx->D + 2) | 1;
   a.do_stats = 1;
   a.shared = ctx->batch_shared ? 1 : 0;
-  a.u = nullptr; a.seeds = nullptr; a.labels = nullptr; a.sweep = 0;
+  a.u = nullptr; a.seeds = nullptr; a.labels = nullptr; a.sweep = 0; a.relabel = nullptr;
   a.resp = nullptr;
   a.sel = nullptr; a.sel_off = nullptr;
   return a;
@@ -434,8 +434,21 @@ int mimo_gibbs_labels_batched(mimo_ctx* ctx, const double* c, const double* b, c
     return fail(ctx, MIMO_E_INVALID, "%s: u and seeds are both NULL (give the uniforms or one Philox seed per problem)", me);
   const int B = ctx->batch_B, G = ctx->batch_G;
   const int64_t N = table_rows(ctx);
-  // the seeds travel behind the operand image, in its transfer
-  if ((rc = batched_theta(ctx, c, b, W, K, u ? nullptr : seeds, u ? 0 : (size_t)B, me))) return rc;
+  // problems with components switched off by c = -inf: the draw's relabel table of every problem (draw_label, mimo_device.h)
+  std::vector<int32_t> relabel;
+  for (int p = 0; p < B; ++p) {
+    int32_t row[kBatchedMaxK];
+    if (!draw_relabel(c + (size_t)p * K, K, row)) continue;
+    if (relabel.empty()) {
+      relabel.resize(((size_t)B * K + 1) / 2 * 2);
+      for (size_t i = 0; i < (size_t)B * K; ++i) relabel[i] = (int32_t)(i % K);
+    }
+    memcpy(&relabel[(size_t)p * K], row, (size_t)K * sizeof(int32_t));
+  }
+  // the seeds and the relabel table travel behind the operand image, in its transfer
+  const size_t nseeds = u ? 0 : (size_t)B;
+  if ((rc = batched_theta(ctx, c, b, W, K, u ? nullptr : seeds, nseeds, me, reinterpret_cast<const uint64_t*>(relabel.data()),
+                          relabel.size() / 2))) return rc;
   if ((rc = ctx->labels.ensure(ctx, (size_t)N))) return rc;
   const double* ud = nullptr;
   bool copied = false;        // (u NULL: Philox uniforms from the seeds; the flags admit no MIMO_F_DEVICE_IN)
@@ -450,6 +463,7 @@ int mimo_gibbs_labels_batched(mimo_ctx* ctx, const double* c, const double* b, c
   a.seeds = u ? nullptr : reinterpret_cast<const uint64_t*>(ctx->theta_d + image_len(ctx, K));
   a.labels = ctx->labels;
   a.sweep = sweep;
+  if (!relabel.empty()) a.relabel = reinterpret_cast<const int32_t*>(ctx->theta_d + image_len(ctx, K) + nseeds);
   HIP_TRY(ctx, launch_batched_labels(a, kBatchedDraw, G, ctx->stream));
   leaves(ctx, kLabels, kLabels);
   if (!no_stats && (rc = batched_stats_out(ctx, K, S))) return rc;

@@ -44,6 +44,7 @@ struct BatchedArgs {
   const uint64_t* seeds;      // [B] (Philox draw)
   int32_t* labels;            // (N_total,): the labels drawn (kBatchedDraw) or given (kBatchedGiven)
   uint64_t sweep;
+  const int32_t* relabel;     // [B][K] or null: KernelArgs::relabel of every problem (some problem has components switched off by c = -inf)
   // table mode (launch_batched_weights) only
   const double* resp;         // the problems' K-major (K, N_b) weight tables back to back: problem b's starts at element K row_off[b]
   // row-selection mode (launch_batched_rows) only

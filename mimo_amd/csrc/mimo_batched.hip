@@ -125,6 +125,7 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
   // the draw reads the problem's slices of the uniforms and labels, or its Philox key, with local rows (row0 = 0)
   KernelArgs ka;
   ka.u = nullptr;
+  ka.relabel = nullptr;
   ka.labels = nullptr;
   ka.seed = 0; ka.sweep = 0; ka.row0 = 0;
   if constexpr (LM == kBatchedDraw) {
@@ -132,6 +133,7 @@ __global__ __launch_bounds__(kWG, 1) void batched_kernel(const BatchedArgs a) {
     ka.labels = a.labels + rbeg;
     ka.seed = a.u ? 0 : a.seeds[prob];
     ka.sweep = a.sweep;
+    ka.relabel = a.relabel ? a.relabel + (size_t)prob * K : nullptr;
   }
   if constexpr (WEIGHTED) ka.u = a.u + rbeg;   // the generic normalise mode scales the weights it writes back by u[local row]
 

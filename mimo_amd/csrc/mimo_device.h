@@ -51,6 +51,18 @@ __host__ __device__ inline double philox_uniform(uint64_t seed, uint64_t row, ui
   return ((double)(c0 >> 5) * 67108864.0 + (double)(c1 >> 6)) * (1.0 / 9007199254740992.0);
 }
 
+// The label of an inverse-CDF draw from `cnt`, the number of cumulative sums below the threshold u cum_K (label = #{k : u cum_K >
+// cum_k}, capped at the last component: u < 1 never exceeds cum_K, its rounding may).  A component switched off by c_k = -inf has
+// cum_k == cum_{k-1} and cannot be drawn with u > 0 — but the kernels compare u cum_K - (prefix of the lanes, chunks or row
+// blocks in front) with LOCAL cumulative sums, and where a switched-off component opens a lane's or a chunk's slots, or closes
+// the row, the prefix scans' last bit can leave the count on it.  `relabel` (KernelArgs::relabel; null when every component is
+// live) sends such a count to the nearest live component below: the crossing lies within rounding of that one's upper boundary.
+// (u = 0 draws component 0 whatever its weight, as the reference's rule does.)
+__device__ __forceinline__ int draw_label(int cnt, int K, const int32_t* __restrict__ relabel, double u) {
+  const int label = cnt < K ? cnt : K - 1;
+  return (relabel && u > 0.0) ? relabel[label] : label;
+}
+
 // One column of the random initial responsibilities (random_resp_kernel of mimo_small.hip, batched_random_resp_kernel of
 // mimo_batched.hip): out[k stride] = v_k / sum_j v_j, v_k = the Philox uniform of key `seed`, counter (row, k), moved to
 // (0, 1] (a column of zeros cannot happen).  The sum runs over k ascending, then ONE reciprocal, then v inv: both kernels

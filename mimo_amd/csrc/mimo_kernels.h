@@ -57,6 +57,8 @@ struct KernelArgs {
   int fuse_hist;          // gibbs_rowwave_kernel counts the labels it draws into aux[0 .. 255] (no label_hist_kernel behind it)
   int resp_skip;          // fused softmax pass: rows whose 16 weights of a row block are all < 2^-resp_skip skip that block's
                           // statistics (0: dense; mimo_tune "resp_skip_log2")
+  const int32_t* relabel; // label draws: null, or [K] for a Theta with components switched off by c_k = -inf: relabel[k] = k for a
+                          // live k, else the nearest live component below k (none below: the first live one) — draw_label, mimo_device.h
 };
 
 // feature count helpers (z~ = [z,1]; features = upper-triangular pairs of z~)
@@ -143,6 +145,20 @@ struct PredictArgs {
 constexpr int kMaxPredictDy = 8;
 constexpr double kPadLogDensity = -1e300;   // c_k of the padding components k in [K, 16*K16)
 constexpr double kOffLogDensity = -1e299;   // l below this: a padding or switched-off component (its l is -1e300 to the last bit)
+// relabel[] of KernelArgs for the K offsets c (switched off: c_k = -inf, which the Theta images hold as kPadLogDensity); false (and
+// relabel untouched) when every component is live or none is
+inline bool draw_relabel(const double* c, int K, int32_t* relabel) {
+  int first = -1, off = 0;
+  for (int k = 0; k < K; ++k) {
+    if (c[k] > kPadLogDensity) { if (first < 0) first = k; } else ++off;
+  }
+  if (!off || first < 0) return false;
+  for (int k = 0, last = first; k < K; ++k) {
+    if (c[k] > kPadLogDensity) last = k;
+    relabel[k] = last;
+  }
+  return true;
+}
 hipError_t launch_predict(const PredictArgs& a, hipStream_t stream, bool* unsupported);
 bool launch_predict_reg(const PredictArgs& a, hipStream_t stream, hipError_t* err);      // mimo_predict.hip: dx <= 8 with the affine column
 

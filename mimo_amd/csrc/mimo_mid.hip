@@ -214,7 +214,7 @@ __global__ __launch_bounds__(64 * NW, MODE == 1 ? 2 : mid_wgs_per_cu(DT, KB)) vo
         for (int r = 0; r < 4; ++r) cnt += tl > acc[rb][r] ? 1 : 0;
       cnt = butterfly_sum<LX, 16>(cnt);
       cnt = butterfly_sum<LX, 32>(cnt);
-      if (q == 0 && valid) a.labels[n] = cnt < K ? cnt : K - 1;
+      if (q == 0 && valid) a.labels[n] = draw_label(cnt, K, a.relabel, uu);
       __builtin_amdgcn_s_setprio(0);
       continue;
     }

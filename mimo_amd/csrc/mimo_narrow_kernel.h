@@ -496,7 +496,7 @@ __global__ __launch_bounds__(kNarrowWG, narrow_waves(V, NSF, MODE)) void narrow_
       }
       cnt += quad_i32<kQuadXor1>(cnt);
       cnt += quad_i32<kQuadXor2>(cnt);
-      const int label = cnt < K ? cnt : K - 1;
+      const int label = draw_label(cnt, K, a.relabel, uu);
       if (lo == 0 && valid) {
         a.labels[n1] = label;
         if constexpr (MODE == 1)

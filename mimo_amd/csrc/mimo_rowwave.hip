@@ -216,7 +216,7 @@ __global__ __launch_bounds__(kRowWaveWG, 1) void gibbs_rowwave_kernel(const Kern
     }
     cnt = butterfly_sum<gibbs_rowwave_lane_regs(KB, NS4), 16>(cnt);
     cnt = butterfly_sum<gibbs_rowwave_lane_regs(KB, NS4), 32>(cnt);
-    const int label = cnt < K ? cnt : K - 1;
+    const int label = draw_label(cnt, K, a.relabel, uu);
     if (q == 0 && valid) {
       a.labels[n] = label;
       if (a.fuse_hist) atomicAdd(&hloc[label], 1u);
@@ -434,7 +434,7 @@ __global__ __launch_bounds__(kRowWaveWG, 1) void gibbs_stream_kernel(const Kerne
     }
     cnt = butterfly_sum<true, 16>(cnt);
     cnt = butterfly_sum<true, 32>(cnt);
-    const int label = cnt < K ? cnt : K - 1;
+    const int label = draw_label(cnt, K, a.relabel, uu);
     if (q == 0 && valid) a.labels[n] = label;
     __builtin_amdgcn_s_setprio(0);
   }

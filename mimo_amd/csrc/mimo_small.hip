@@ -259,7 +259,7 @@ void small_kernel(const KernelArgs a) {
 #pragma unroll
         for (int c = 0; c < KL; ++c) cnt += tl > E[c] ? 1 : 0;
         cnt = group_sum<small_lane_regs(DZ, KL, G, MODE), G>(cnt);
-        const int label = cnt < K ? cnt : K - 1;
+        const int label = draw_label(cnt, K, a.relabel, uu);
         if (g == 0 && valid && a.labels) a.labels[n] = label;
 #pragma unroll
         for (int c = 0; c < KL; ++c) r[c] = (valid && label == g * KL + c) ? 1.0 : 0.0;

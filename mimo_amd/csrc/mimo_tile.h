@@ -284,7 +284,7 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
           cnt = butterfly_sum<LX, 8>(cnt);
           cnt = butterfly_sum<LX, 16>(cnt);
           cnt = butterfly_sum<LX, 32>(cnt);
-          const int label = cnt < K ? cnt : K - 1;
+          const int label = draw_label(cnt, K, a.relabel, uu);
           if (part == 0) {
             labs[pt] = valid ? label : -1;      // the statistics phase builds its one-hot operand from this
             if (valid && a.labels) a.labels[n] = label;
@@ -466,7 +466,7 @@ __device__ __forceinline__ void normalise_tile_chunked(const KernelArgs& a, doub
     cnt = butterfly_sum<LX, 8>(cnt);
     cnt = butterfly_sum<LX, 16>(cnt);
     cnt = butterfly_sum<LX, 32>(cnt);
-    const int label = cnt < K ? cnt : K - 1;
+    const int label = draw_label(cnt, K, a.relabel, uu);
     if (part == 0) {
       labs[pt] = valid ? label : -1;
       if (valid && a.labels) a.labels[n] = label;

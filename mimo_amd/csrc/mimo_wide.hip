@@ -640,7 +640,7 @@ __global__ __launch_bounds__(kWG, 2) void wide_estep_kernel(const KernelArgs a) 
             int tot = cred[16 * c + j];
 #pragma unroll
             for (int w = 1; w < NW; ++w) tot += cred[w * T + 16 * c + j];
-            if (a.labels) a.labels[n] = tot < K ? tot : K - 1;
+            if (a.labels) a.labels[n] = draw_label(tot, K, a.relabel, ured[16 * c + j]);
             const double lse = m[c] + log(ctot[c]);
             sc_lse += lse;
             sc_rl += ssel[c] / ctot[c];

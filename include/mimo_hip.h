@@ -658,6 +658,19 @@ int mimo_host_gmm_vi_bound(int K, int D, int tied, const double* alpha0, const d
  * or mass; MIMO_E_UNSUPPORTED for K > 256.  No reference counterpart (the order of the components is ours to choose). */
 int mimo_host_block_order(int K, int D, const double* means, const double* mass, int block, int32_t* order);
 
+/* Constants of the per-row E-step certificates (mimo_tune "estep_cert"): how far the K log-densities of the current parameters
+ * (c, b, W) can lie from those of a reference pass (c0, b0, W0), per component in the reference's whitened coordinates.
+ *   out  : [c^0 K | c^ K | rho K | rho_bar K | d K | min c^0, max c^, min rho, max d] — the peaks c + b'W^-1 b / 2 of both, an
+ *          enclosure rho <= lambda_min, rho_bar >= lambda_max of L^-1 W L^-T (W0 = L L'; from a fixed grid, by Cholesky tests of
+ *          W - s W0 and W0 - s W), and d = |mu - mu0| in the norm of W0
+ *   table: NULL, or [alpha_0, beta_0, alpha_1, beta_1 | gamma K | delta K], the coefficients of the test the certified pass
+ *          evaluates per row, with `margin` (ln tau - eps) added to gamma.
+ * A pure function of its arguments, about as long as mimo_host_block_order times ten at K = 64, D = 16.  MIMO_E_INVALID for a NULL pointer
+ * (table excepted), a NaN or an infinity, or a W that is not positive definite; MIMO_E_UNSUPPORTED for K > 256 or D > 32.
+ * No reference counterpart. */
+int mimo_host_estep_certificate(int K, int D, const double* c0, const double* b0, const double* W0, const double* c, const double* b,
+                                const double* W, double margin, double* out, double* table);
+
 /* K blocks of variates from numpy.random's LEGACY stream (RandomState over MT19937), bit for bit what the reference's
  * per-component calls consume and return: per block k, n_before x normal(), then standard_gamma(shapes[k][i]) for i < n_gamma
  * (chisquare(df) = 2 standard_gamma(df / 2), gamma(a, scale) = scale standard_gamma(a): the caller scales), then n_after x
@@ -803,6 +816,14 @@ int mimo_data_checksum(mimo_ctx* ctx, uint64_t out[2]);
  *                  created, so that a program which never calls mimo_tune can be run both ways) 0: mimo_set_component_order
  *                  becomes a no-op and an order in force is dropped, so one library runs a driver that sets orders with
  *                  and without them.
+ *   "estep_cert"   (per context; default 1, or the environment variable MIMO_ESTEP_CERT at creation) per-row certificates of the
+ *                  mean-field pass that runs under "resp_skip_log2" > 0 and a component order at 48 < K <= 64, Dz >= 14: once the
+ *                  order's partition into row blocks has stood for two passes, a reference pass records for every row its largest
+ *                  log-density, where it is, and the largest outside that row block; the passes after it contract, per wave and tile,
+ *                  only the rows those numbers do not prove dead in the wave's block.  Every delivered number is bit for bit what
+ *                  0 delivers.  Dropped by an upload / attach, another K, structure or "resp_skip_log2", an order whose blocks are
+ *                  other sets of components; renewed after 16 certified passes.  0: off — the passes run as if there were none; certificates
+ *                  in force stay (they speak of the rows, which have not changed) and serve again once the key is 1.
  *   "sorted_range" (process-wide) cap on the 256-row tiles per range of label_stats_gram_kernel (default and maximum 80;
  *                  0 restores it): with a low cap a workgroup takes several ranges ("first range writes, later ranges add").
  *   "mid_min_d", "mid_narrow_k" (process-wide) 0 / 0: the mid kernels (mimo_mid.hip) run where they measured fastest.  Otherwise
@@ -814,6 +835,12 @@ int mimo_data_checksum(mimo_ctx* ctx, uint64_t out[2]);
  * Results do not depend on the geometry keys beyond the documented summation order of the partial blocks.  MIMO_E_INVALID for
  * an unknown key or a value out of range.  The reference has no counterpart (launch geometry is ours). */
 int mimo_tune(mimo_ctx* ctx, const char* key, int64_t value);
+
+/* What the per-row E-step certificates did (mimo_tune "estep_cert"): out6 = [kind of the last mimo_estep on this context — 0 plain,
+ * 1 reference pass (it wrote the certificates), 2 certified pass (it read them); 1 if certificates are in force; certified passes since
+ * the reference pass; then, summed over all certified passes of the context: rows proven dead outside their row block, (tile, wave)
+ * pairs that contracted one column group, (tile, wave) pairs].  Waits for the stream.  Reads nothing else and changes nothing. */
+int mimo_estep_cert_info(mimo_ctx* ctx, int64_t* out6);
 
 /* Test hook for the no-exception contract: throws, INSIDE the guarded boundary, kind 1: std::bad_alloc,
  * 2: std::runtime_error, 3: a non-std exception; returns the code the guard maps it to (MIMO_E_NOMEM,

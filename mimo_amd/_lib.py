@@ -73,6 +73,7 @@ SIGNATURES = {
     "mimo_host_gmm_vi_sweep": (C.c_int, [C.c_int, C.c_int, C.c_int] + [_vp] * 26),
     "mimo_host_gmm_vi_bound": (C.c_int, [C.c_int, C.c_int, C.c_int] + [_vp] * 21),
     "mimo_host_block_order": (C.c_int, [C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
+    "mimo_host_estep_certificate": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
     "mimo_host_mnw_vi": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 15),
     "mimo_host_nw_gibbs": (C.c_int, [C.c_int, C.c_int] + [_vp] * 10),
     "mimo_host_digamma": (C.c_double, [C.c_double]),
@@ -101,6 +102,7 @@ SIGNATURES = {
     "mimo_comm_init": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int]),
     "mimo_comm_destroy": (C.c_int, [_vp]),
     "mimo_tune": (C.c_int, [_vp, C.c_char_p, C.c_int64]),
+    "mimo_estep_cert_info": (C.c_int, [_vp, _vp]),
     "mimo_data_checksum": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "mimo_debug_fault": (C.c_int, [_vp, C.c_int]),
     "mimo_host_debug_fault": (C.c_int, [C.c_int]),

@@ -151,6 +151,68 @@ static bool order_applies(const mimo_ctx* ctx, const Route& route, const KernelA
          a.do_stats && !a.gibbs && !a.split && !a.resp && !a.logp && !a.lse && !a.u && ctx->n_bad == 0;
 }
 
+// Per-row certificates of the fused mean-field E-step ("E-step certificates"): the kind of this pass — it runs
+// under the context's component order (order_applies) — and, for a certified pass, the table it reads.  The policy is a function
+// of the sequence of (K, order, parameters) the context has seen and of nothing the device reports, so every rank of a sharded
+// run takes the same kind, and no delivered number depends on it:
+//   certificates in force, whose partition into row blocks is this pass's, fewer than kCertRenew certified passes old -> certified
+//   else the partition is the one of the previous such pass (it has stood for two passes)                             -> reference
+//   else                                                                                                              -> plain
+// (while the partition still moves, the clusters have not separated and a reference pass would be thrown away by the next one).
+// kCertRenew: on the benchmark's fit a certificate proves 99.6 % of the rows one pass later and 94 % sixteen passes later
+// (tests/test_estep_certificate_cpu.py); a reference pass costs what a plain pass costs.
+static constexpr int kCertRenew = 16;
+static constexpr double kCertEps = 1e-3;
+static int cert_plan(mimo_ctx* ctx, const KernelArgs& a, const double* c, const double* b, const double* W, double* tab, int* kind) {
+  *kind = kCertNone;
+  const int K = a.K, D = ctx->D;
+  if (!ctx->cert_on || a.resp_skip <= 0 || a.K16 != 4 || D < 14 || D > kMaxFusedD || ctx->structure != 0 || ctx->N < 1) return MIMO_OK;
+  uint64_t part[4] = {0, 0, 0, 0};
+  int32_t slot_of[64];
+  for (int s = 0; s < K; ++s) { part[s >> 4] |= 1ull << ctx->order[s]; slot_of[ctx->order[s]] = s; }
+  std::sort(part, part + 4);
+  const bool stood = ctx->cert_prev_K == K && !memcmp(part, ctx->cert_prev_part, sizeof part);
+  memcpy(ctx->cert_prev_part, part, sizeof part);
+  ctx->cert_prev_K = K;
+  if (ctx->cert_valid && (ctx->cert_K != K || ctx->cert_skip != a.resp_skip || memcmp(part, ctx->cert_part, sizeof part))) ctx->cert_valid = false;
+  const size_t KD = (size_t)K * D, KDD = KD * D;
+  if (ctx->cert_valid && ctx->cert_age < kCertRenew) {
+    double out[5 * 64 + 4], t[4 + 2 * 64];
+    const double* r = ctx->cert_ref.data();
+    if (mimo_host_estep_certificate(K, D, r, r + K, r + K + KD, c, b, W, -0.6931471805599453 * a.resp_skip - kCertEps, out, t) == MIMO_OK) {
+      memcpy(tab, t, 4 * sizeof(double));
+      uint8_t* blk = reinterpret_cast<uint8_t*>(tab + 4 + 128);
+      for (int s = 0; s < 64; ++s) {          // by the slot of the REFERENCE pass, which is what the rows' certificates name
+        const int k = s < K ? ctx->cert_order[s] : -1;
+        tab[4 + s] = k < 0 ? -1e300 : t[4 + k];
+        tab[4 + 64 + s] = k < 0 ? 0.0 : t[4 + K + k];
+        blk[s] = k < 0 ? 0 : (uint8_t)(slot_of[k] >> 4);
+      }
+      ctx->cert_age += 1;
+      *kind = kCertCertified;
+      return MIMO_OK;
+    }
+    ctx->cert_valid = false;                  // (a precision that is not positive definite: nothing to certify against)
+  }
+  if (!stood) return MIMO_OK;
+  int rc;
+  if ((rc = ctx->cert_k.ensure(ctx, (size_t)ctx->N)) || (rc = ctx->cert_m.ensure(ctx, (size_t)ctx->N)) || (rc = ctx->cert_a.ensure(ctx, (size_t)ctx->N))) return rc;
+  if (!ctx->cert_cnt.p) {
+    if ((rc = ctx->cert_cnt.ensure(ctx, 4))) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->cert_cnt, 0, 4 * sizeof(unsigned long long), ctx->stream));
+  }
+  ctx->cert_ref.resize(K + KD + KDD);
+  memcpy(ctx->cert_ref.data(), c, K * sizeof(double));
+  memcpy(ctx->cert_ref.data() + K, b, KD * sizeof(double));
+  memcpy(ctx->cert_ref.data() + K + KD, W, KDD * sizeof(double));
+  memcpy(ctx->cert_order, ctx->order, K * sizeof(int32_t));
+  memcpy(ctx->cert_part, part, sizeof part);
+  ctx->cert_K = K; ctx->cert_skip = a.resp_skip; ctx->cert_age = 0;
+  ctx->cert_valid = true;
+  *kind = kCertReference;
+  return MIMO_OK;
+}
+
 static void fill_args(mimo_ctx* ctx, int K, KernelArgs* a) {
   memset(a, 0, sizeof *a);
   a->Z = ctx->Z; a->N = ctx->N; a->D = ctx->D; a->K = K; a->K16 = (K + 15) / 16;
@@ -234,9 +296,20 @@ static int upload_theta_for(mimo_ctx* ctx, const Route& route, const double* c, 
   int32_t slot_of[64];
   for (int s = 0; s < K; ++s) slot_of[ctx->order[s]] = s;
   pl.slot_of = slot_of;
-  const int rc = stage_theta(ctx, pl, c, b, W, 1, reinterpret_cast<const uint64_t*>(ctx->order), (size_t)(K + 1) / 2, nullptr);
+  // ... and behind the order, for a certified pass, its table
+  double tab[kCertTabLen];
+  int kind = kCertNone, rc;
+  if ((rc = cert_plan(ctx, *a, c, b, W, tab, &kind))) return rc;
+  const size_t nord = (size_t)(K + 1) / 2;
+  rc = stage_theta(ctx, pl, c, b, W, 1, reinterpret_cast<const uint64_t*>(ctx->order), nord, nullptr, nullptr,
+                   kind == kCertCertified ? reinterpret_cast<const uint64_t*>(tab) : nullptr, kind == kCertCertified ? (size_t)kCertTabLen : 0);
   a->theta = ctx->theta_d;
   ctx->pass_order = reinterpret_cast<const int32_t*>(ctx->theta_d + pl.count());
+  a->cert = kind;
+  if (kind != kCertNone) {
+    a->cert_k = ctx->cert_k; a->cert_m = ctx->cert_m; a->cert_a = ctx->cert_a; a->cert_cnt = ctx->cert_cnt;
+    a->cert_tab = ctx->theta_d + pl.count() + nord;
+  }
   return rc;
 }
 
@@ -550,6 +623,7 @@ int mimo_abi::set_data(mimo_ctx* ctx, int64_t N, int Dz) {
     return fail(ctx, MIMO_E_UNSUPPORTED, "Dz = %d outside [1, %d]", Dz, kMaxD);
   ctx->N = N; ctx->D = Dz;
   ctx->order_K = 0;
+  ctx->cert_valid = false; ctx->cert_prev_K = 0;
   ctx->batched = false;
   ctx->batch_shared = false;
   ctx->resp_valid = ctx->logp_valid = ctx->lse_valid = ctx->labels_valid = false;
@@ -720,6 +794,7 @@ int mimo_set_structure(mimo_ctx* ctx, int structure) {
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));    // the feature table may be in use
   ctx->structure = structure;
   ctx->order_K = 0;
+  ctx->cert_valid = false; ctx->cert_prev_K = 0;
   return ctx->D > 0 ? prepare_features(ctx, ctx->D) : MIMO_OK;
   });
 }
@@ -789,8 +864,11 @@ int mimo_estep(mimo_ctx* ctx, const double* c, const double* b, const double* W,
   a.do_stats = (no_stats && !route.promoted) ? 0 : 1;
   a.split = (flags & MIMO_F_ENTROPY_SPLIT) ? 1 : 0;
   if ((rc = keep_tables(ctx, K, flags, &a))) return rc;
-  if ((rc = upload_theta_for(ctx, route, c, b, W, K, &a))) return rc;
-  return run_fused(ctx, a, kSrcEstep, flags, no_stats ? nullptr : S, scalars, route);
+  ctx->cert_last = kCertNone;
+  if ((rc = upload_theta_for(ctx, route, c, b, W, K, &a))) { ctx->cert_valid = false; return rc; }
+  if ((rc = run_fused(ctx, a, kSrcEstep, flags, no_stats ? nullptr : S, scalars, route))) { ctx->cert_valid = false; return rc; }
+  ctx->cert_last = a.cert;
+  return MIMO_OK;
   });
 }
 
@@ -1218,7 +1296,7 @@ int mimo_tune(mimo_ctx* ctx, const char* key, int64_t value) {
     if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
     RouteTunables& t = g_route_tunables;     // process-wide, as sorted_range and narrow_big_vi (include/mimo_hip.h)
     const struct { const char* key; int max; int* knob; } keys[] = {
-        {"num_cu", 4096, nullptr}, {"resp_skip_log2", 1000, &ctx->resp_skip_log2}, {"block_order", 1, &ctx->block_order_on}, {"sorted_range", 80, nullptr}, {"narrow_big_vi", 256, nullptr},
+        {"num_cu", 4096, nullptr}, {"resp_skip_log2", 1000, &ctx->resp_skip_log2}, {"block_order", 1, &ctx->block_order_on}, {"estep_cert", 1, &ctx->cert_on}, {"sorted_range", 80, nullptr}, {"narrow_big_vi", 256, nullptr},
         {"mid_labels_narrow_k", 64, &t.mid_labels_narrow_k}, {"mid_labels_min_d", 64, &t.mid_labels_min_d},
         {"mid_narrow_k", 64, &t.mid_narrow_k}, {"mid_min_d", 64, &t.mid_min_d}};
     for (const auto& m : keys) {
@@ -1234,6 +1312,22 @@ int mimo_tune(mimo_ctx* ctx, const char* key, int64_t value) {
       return MIMO_OK;
     }
     return fail(ctx, MIMO_E_INVALID, "mimo_tune: unknown key '%s'", key);
+  });
+}
+
+int mimo_estep_cert_info(mimo_ctx* ctx, int64_t* out6) {
+  return guarded(ctx, [&]() -> int {
+    int rc = bind(ctx); if (rc) return rc;
+    if (!out6) return fail(ctx, MIMO_E_INVALID, "mimo_estep_cert_info: out is NULL");
+    if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    if (ctx->cert_cnt.p) {
+      HIP_TRY(ctx, hipMemcpyAsync(cnt, ctx->cert_cnt, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    out6[0] = ctx->cert_last; out6[1] = ctx->cert_valid ? 1 : 0; out6[2] = ctx->cert_age;
+    out6[3] = (int64_t)cnt[0]; out6[4] = (int64_t)cnt[1]; out6[5] = (int64_t)cnt[2];
+    return MIMO_OK;
   });
 }
 

@@ -107,6 +107,22 @@ struct mimo_ctx {
   alignas(8) int32_t order[256] = {0};                    // order[s] = the component in slot s
   const int32_t* pass_order = nullptr;                    // the pass being launched runs under the order: its device copy (behind the Theta image)
 
+  // per-row certificates of the fused mean-field E-step ("E-step certificates"; mimo_tune "estep_cert").  They
+  // exist for the pass that runs the skipping kernel under a component order at K16 = 4, and are allocated by its first reference pass.
+  int cert_on = [] { const char* e = getenv("MIMO_ESTEP_CERT"); return !e || atoi(e) != 0; }();
+  bool cert_valid = false;                                // cert_k / cert_m / cert_a hold a reference pass of the resident rows, and:
+  int cert_K = 0, cert_skip = 0;                          //   its K and resp_skip_log2
+  int cert_age = 0;                                       //   certified passes since
+  std::vector<double> cert_ref;                           //   its parameters [c K | b K D | W K D D]
+  int32_t cert_order[64] = {0};                           //   its slot order
+  uint64_t cert_part[4] = {0, 0, 0, 0};                   //   its partition into row blocks: the blocks' component sets, ascending
+  uint64_t cert_prev_part[4] = {0, 0, 0, 0};              // the partition of the last eligible pass, and its K (0: none)
+  int cert_prev_K = 0;
+  int cert_last = 0;                                      // kind of the last mimo_estep (mimo::Cert)
+  Buf<uint8_t> cert_k;                                    // (N,) the three per-row arrays (KernelArgs)
+  Buf<double> cert_m, cert_a;
+  Buf<unsigned long long> cert_cnt;                       // [4] running totals of the certified passes (KernelArgs::cert_cnt)
+
   // workspaces
   Buf<double> partials;
   Buf<double> reduced;

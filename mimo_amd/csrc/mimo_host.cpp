@@ -1093,6 +1093,166 @@ int mimo_host_block_order(int K, int D, const double* means, const double* mass,
   });
 }
 
+// Constants of the per-row certificates of the fused mean-field E-step ("E-step certificates"): how far the K
+// log-densities l_k(x) = c_k + b_k.x - x'W_k x / 2 = c^_k - |x - mu_k|^2_{W_k} / 2 of the current pass can lie from those of the
+// reference pass (c0, b0, W0), in the reference's own whitened coordinates.  Per component, with W0_k = L L':
+//   c^0_k, c^_k   the peaks c + b'W^-1 b / 2;      d_k = |L'(mu_k - mu0_k)|;
+//   rho_k <= lambda_min(L^-1 W_k L^-T),  rho_bar_k >= lambda_max(L^-1 W_k L^-T).
+// The two eigenvalue bounds are enclosures, not estimates: lambda_min >= s exactly when W_k - s W0_k is positive definite, and
+// lambda_max <= 1 / s exactly when W0_k - s W_k is; rho_k is the largest s of kCertGrid for which the Cholesky factorisation
+// of W_k - s W0_k runs through with every pivot above 1e-10 of its diagonal entry (0 when none does), 1 / rho_bar_k the largest for
+// W0_k - s W_k (rho_bar = +inf when none does); W_k = W0_k to the bit gives 1 and 1.  (Gershgorin discs and norm bounds of
+// L^-1 W L^-T - I are cheaper and useless here: a component that holds one row changes its precision several-fold between two
+// passes, its bound on lambda_min turns negative, and it takes its whole class of components with it.)
+// out: [c^0 K | c^ K | rho K | rho_bar K | d K | min c^0, max c^, min rho, max d].
+// table (may be null), what the certified pass reads — the test of row n with certificate (k*, m0 = l0_k*(x_n), a0 = the largest l0
+// outside the row block of k*) is   max_c (alpha_c + beta_c a0) <= gamma_k* + delta_k* m0,   free of square roots:
+//   (sqrt q + d)^2 <= (1 + e) q + (1 + 1 / e) d^2  and  (sqrt q - d)_+^2 >= (1 - e) q - (1 / e - 1) d^2  for every 0 < e (< 1),
+// with q >= 2 (min_c c^0 - a0) for the components of class c outside the block and q = 2 (c^0_k* - m0) for k* itself:
+//   beta_c = rho_min,c (1 - e_c), alpha_c = max_c c^ - beta_c min_c c^0 + rho_min,c (1 / e_c - 1) d_max,c^2 / 2,   e_c = d_max,c / 20
+//   delta_k = rho_bar_k (1 + e_k), gamma_k = c^_k - delta_k c^0_k - rho_bar_k (1 + 1 / e_k) d_k^2 / 2 + margin,    e_k = d_k / 4
+// (20 and 4: the square roots of a typical q outside the block and at the own component; any value is sound).  The two classes:
+// the components split at the widest gap of their sorted c^0 — those that hold no data sit at the prior's peak, hundreds of
+// nats under the rest, and one set of constants over all K would prove nothing.  margin = ln tau - eps.
+// table: [alpha_0, beta_0, alpha_1, beta_1 | gamma K | delta K]; a component without a bound (rho_bar = inf) gets delta = 0,
+// gamma = -1e300: its rows are unproven.
+namespace {
+constexpr double kCertGrid[] = {0.98, 0.95, 0.9, 0.8, 0.65, 0.5, 0.3, 0.1};
+
+// upper Cholesky factor U'U of FOUR symmetric matrices at once, one per SIMD lane (as spd_inverse4: the matrices are too narrow
+// for row-wise vectorisation, but K of them are independent), in place on the upper triangle of M (n x n, row-major).  Bit l of
+// the result: a pivot of lane l was not above 1e-10 of its diagonal entry (the lane goes on with a pivot of 1; its factor is void).
+unsigned cert_chol4(v4d* __restrict__ M, int n) {
+  unsigned bad = 0;
+  v4d d0[32];
+  for (int j = 0; j < n; ++j) d0[j] = M[j * n + j];
+  for (int j = 0; j < n; ++j) {
+    v4d* mj = M + (size_t)j * n;
+    v4d d = mj[j], piv;
+    for (int l = 0; l < 4; ++l) {
+      if (!(d[l] > 1e-10 * std::fabs(d0[j][l]))) { bad |= 1u << l; d[l] = 1.0; }
+      piv[l] = std::sqrt(d[l]);
+    }
+    const v4d inv = 1.0 / piv;
+    for (int c = j; c < n; ++c) mj[c] *= inv;
+    for (int i = j + 1; i < n; ++i) {
+      const v4d f = mj[i];
+      v4d* mi = M + (size_t)i * n;
+      for (int c = i; c < n; ++c) mi[c] -= f * mj[c];
+    }
+  }
+  return bad;
+}
+}  // namespace
+
+int mimo_host_estep_certificate(int K, int D, const double* c0, const double* b0, const double* W0, const double* c, const double* b,
+                                const double* W, double margin, double* out, double* table) {
+  return guarded_host([&]() -> int {
+  if (K < 1 || D < 1 || !c0 || !b0 || !W0 || !c || !b || !W || !out) return MIMO_E_INVALID;
+  if (K > 256 || D > 32) return MIMO_E_UNSUPPORTED;
+  const size_t DD = (size_t)D * D;
+  for (size_t i = 0; i < (size_t)K; ++i) if (!std::isfinite(c0[i]) || !std::isfinite(c[i])) return MIMO_E_INVALID;
+  for (size_t i = 0; i < (size_t)K * D; ++i) if (!std::isfinite(b0[i]) || !std::isfinite(b[i])) return MIMO_E_INVALID;
+  for (size_t i = 0; i < (size_t)K * DD; ++i) if (!std::isfinite(W0[i]) || !std::isfinite(W[i])) return MIMO_E_INVALID;
+  double *ch0 = out, *ch = out + K, *rho = out + 2 * (size_t)K, *rhob = out + 3 * (size_t)K, *dk = out + 4 * (size_t)K, *cons = out + 5 * (size_t)K;
+  std::vector<v4d> work(5 * DD);
+  v4d *A0 = work.data(), *A1 = A0 + DD, *U0 = A1 + DD, *U1 = U0 + DD, *T = U1 + DD;
+  v4d y[32], mu0[32], mu1[32];
+  // mu = (U'U)^-1 rhs; returns rhs'(U'U)^-1 rhs = |U^-T rhs|^2
+  auto solve = [&](const v4d* U, const double* const rhs[4], v4d* mu) {
+    v4d yy = {0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < D; ++i) {
+      v4d s = {rhs[0][i], rhs[1][i], rhs[2][i], rhs[3][i]};
+      for (int r = 0; r < i; ++r) s -= U[r * D + i] * y[r];
+      y[i] = s / U[i * D + i];
+      yy += y[i] * y[i];
+    }
+    for (int i = D - 1; i >= 0; --i) {
+      v4d s = y[i];
+      for (int r = i + 1; r < D; ++r) s -= U[i * D + r] * mu[r];
+      mu[i] = s / U[i * D + i];
+    }
+    return yy;
+  };
+  for (int k0 = 0; k0 < K; k0 += 4) {
+    int kk[4];                                    // (a last group short of four repeats its last component)
+    for (int l = 0; l < 4; ++l) kk[l] = std::min(k0 + l, K - 1);
+    const double *a0[4], *a1[4], *r0[4], *r1[4];
+    for (int l = 0; l < 4; ++l) { a0[l] = W0 + kk[l] * DD; a1[l] = W + kk[l] * DD; r0[l] = b0 + (size_t)kk[l] * D; r1[l] = b + (size_t)kk[l] * D; }
+    for (int i = 0; i < D; ++i)
+      for (int j = i; j < D; ++j) {
+        const size_t e = (size_t)i * D + j;
+        U0[e] = A0[e] = v4d{a0[0][e], a0[1][e], a0[2][e], a0[3][e]};
+        U1[e] = A1[e] = v4d{a1[0][e], a1[1][e], a1[2][e], a1[3][e]};
+      }
+    if (cert_chol4(U0, D) | cert_chol4(U1, D)) return MIMO_E_INVALID;               // a precision that is not positive definite
+    const v4d q0 = solve(U0, r0, mu0), q1 = solve(U1, r1, mu1);
+    v4d d2 = {0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < D; ++i) {                 // |U0 (mu - mu0)|^2
+      v4d s = {0.0, 0.0, 0.0, 0.0};
+      for (int r = i; r < D; ++r) s += U0[i * D + r] * (mu1[r] - mu0[r]);
+      d2 += s * s;
+    }
+    unsigned same = 0;                            // W = W0 to the bit: both eigenvalue bounds are 1
+    for (int l = 0; l < 4; ++l) if (!memcmp(a0[l], a1[l], DD * sizeof(double))) same |= 1u << l;
+    double lo[4] = {0.0, 0.0, 0.0, 0.0}, hi[4] = {HUGE_VAL, HUGE_VAL, HUGE_VAL, HUGE_VAL};
+    for (int side = 0; side < 2; ++side) {        // 0: rho from W - s W0, 1: 1 / rho_bar from W0 - s W
+      const v4d *P = side ? A0 : A1, *Q = side ? A1 : A0;
+      unsigned pending = 0xFu & ~same;
+      for (const double s : kCertGrid) {
+        if (!pending) break;
+        for (int i = 0; i < D; ++i)
+          for (int j = i; j < D; ++j) T[i * D + j] = P[i * D + j] - s * Q[i * D + j];
+        const unsigned ok = pending & ~cert_chol4(T, D);
+        for (int l = 0; l < 4; ++l) if (ok >> l & 1u) { if (side) hi[l] = 1.0 / s; else lo[l] = s; }
+        pending &= ~ok;
+      }
+    }
+    for (int l = 0; l < 4 && k0 + l < K; ++l) {
+      const int k = k0 + l;
+      ch0[k] = c0[k] + 0.5 * q0[l];
+      ch[k] = c[k] + 0.5 * q1[l];
+      dk[k] = std::sqrt(d2[l]);
+      rho[k] = (same >> l & 1u) ? 1.0 : lo[l];
+      rhob[k] = (same >> l & 1u) ? 1.0 : hi[l];
+    }
+  }
+  cons[0] = ch0[0]; cons[1] = ch[0]; cons[2] = rho[0]; cons[3] = dk[0];
+  for (int k = 1; k < K; ++k) {
+    cons[0] = std::min(cons[0], ch0[k]); cons[1] = std::max(cons[1], ch[k]);
+    cons[2] = std::min(cons[2], rho[k]); cons[3] = std::max(cons[3], dk[k]);
+  }
+  if (!table) return MIMO_OK;
+  // the two classes: above / not above the lower end of the widest gap of the sorted c^0 (ties: the lowest gap)
+  std::vector<double> srt(ch0, ch0 + K);
+  std::sort(srt.begin(), srt.end());
+  double cut = HUGE_VAL, widest = 0.0;            // (no gap: every component in class 0)
+  for (int i = 0; i + 1 < K; ++i) if (srt[i + 1] - srt[i] > widest) { widest = srt[i + 1] - srt[i]; cut = srt[i]; }
+  for (int cl = 0; cl < 2; ++cl) {
+    double c0min = HUGE_VAL, cmax = -HUGE_VAL, rmin = HUGE_VAL, dmax = 0.0;
+    bool any = false;
+    for (int k = 0; k < K; ++k) {
+      if ((ch0[k] > cut) != (cl == 1)) continue;
+      any = true;
+      c0min = std::min(c0min, ch0[k]); cmax = std::max(cmax, ch[k]); rmin = std::min(rmin, rho[k]); dmax = std::max(dmax, dk[k]);
+    }
+    if (!any) { table[2 * cl] = -HUGE_VAL; table[2 * cl + 1] = 0.0; continue; }      // an empty class bounds nothing
+    const double e = std::min(std::max(dmax, 1e-12) / 20.0, 0.5);
+    const double beta = rmin * (1.0 - e);
+    table[2 * cl] = cmax - beta * c0min + 0.5 * rmin * (1.0 / e - 1.0) * dmax * dmax;
+    table[2 * cl + 1] = beta;
+  }
+  double *gam = table + 4, *del = table + 4 + K;
+  for (int k = 0; k < K; ++k) {
+    if (!(rhob[k] < HUGE_VAL)) { gam[k] = -1e300; del[k] = 0.0; continue; }
+    const double e = std::min(std::max(dk[k], 1e-12) / 4.0, 1.0);
+    del[k] = rhob[k] * (1.0 + e);
+    gam[k] = ch[k] - del[k] * ch0[k] - 0.5 * rhob[k] * (1.0 + 1.0 / e) * dk[k] * dk[k] + margin;
+  }
+  return MIMO_OK;
+  });
+}
+
 double mimo_host_digamma(double x) { return digamma(x); }
 
 int mimo_host_debug_fault(int kind) {

@@ -59,7 +59,18 @@ struct KernelArgs {
                           // statistics (0: dense; mimo_tune "resp_skip_log2")
   const int32_t* relabel; // label draws: null, or [K] for a Theta with components switched off by c_k = -inf: relabel[k] = k for a
                           // live k, else the nearest live component below k (none below: the first live one) — draw_label, mimo_device.h
+  // per-row certificates of the skipping softmax pass at K16 = 4 ("E-step certificates").  cert = kCertReference:
+  // the pass writes them; kCertCertified: it reads them and contracts, per wave and tile, only the rows they do not prove dead in
+  // the wave's row block.
+  int cert;
+  uint8_t* cert_k;        // (N,) slot of the row's largest log-density in the reference pass
+  double* cert_m;         // (N,) that log-density
+  double* cert_a;         // (N,) the largest log-density of the reference pass outside the row block of that slot
+  const double* cert_tab; // kCertTabLen doubles behind the Theta image: [alpha0, beta0, alpha1, beta1 | gamma[64] | delta[64] | row block of slot s: 64 bytes]
+  unsigned long long* cert_cnt;   // [0] rows proven, [1] wave-tiles on one column group, [2] wave-tiles, summed over the certified passes
 };
+enum Cert : int { kCertNone = 0, kCertReference = 1, kCertCertified = 2 };
+constexpr int kCertTabLen = 4 + 64 + 64 + 8;
 
 // feature count helpers (z~ = [z,1]; features = upper-triangular pairs of z~)
 inline int feat_count(int D) { return (D + 1) * (D + 2) / 2; }

@@ -102,11 +102,20 @@ constexpr bool fused_lane_regs(int NCB, int RBW, int MODE, int DS, int SPLIT, bo
   return true;
 }
 
-template <int NCB, int RBW, int MODE, int DS = 0, int SPLIT = 0, bool SKIP = false>
+// CERT (SKIP at Dz >= 14, launched for K16 = 4; DESIGN section 4, "E-step certificates"): two more instantiations of the SKIP
+// kernel, not branches inside it.  kCertReference is the SKIP kernel whose normalise phase also stores each row's certificate.
+// kCertCertified reads them: per tile every wave tests the 32 rows (row lane & 31 on every lane: one fused multiply-add per
+// class of components, one for the row's own bound, a compare), ballots the rows proven dead outside their row block, and
+// contracts step 3 over the rows it has to — the unproven ones and the proven ones of its own block.  At most 16 of them: ONE
+// column group over the compacted rows (NS MFMAs instead of 2 NS; lane (q, j) reads Phi[row_j][4 s + q] and stores
+// Lt[row_j][16 wave + q + 4 r], an empty slot reads a valid row and stores nothing).  More: the SKIP kernel's two groups, on a
+// wave-uniform branch.  Everything delivered is bit for bit what the SKIP kernel delivers (normalise_tile, mimo_tile.h).
+template <int NCB, int RBW, int MODE, int DS = 0, int SPLIT = 0, bool SKIP = false, int CERT = 0>
 __global__ __launch_bounds__(kWG, (RBW == 1 ? 2 : (MODE <= kGeneric && RBW == 2) ? 2 : (MODE <= kGeneric && NCB <= 3) ? MIMO_RBW4_ESTEP_WGS
                                    : (MODE > kGeneric && RBW * NCB <= 12) ? 2 : 1))
 void fused_kernel(const KernelArgs a) {
   static_assert(!SKIP || (MODE == kFastVI && RBW == 1 && SPLIT == 0), "responsibility skip: fast VI, RBW = 1, not split");
+  static_assert(CERT == kCertNone || (SKIP && DS >= 14), "certificates: the skipping pass at Dz >= 14");
   constexpr int SRC = MODE == kModeWeights ? kSrcWeights : MODE == kModeLabels ? kSrcLabels : kSrcEstep;
   // flags fold to constants in the two fast modes
   const bool gibbs = MODE == kFastVI ? false : MODE == kFastGibbs ? true : a.gibbs != 0;
@@ -300,6 +309,29 @@ void fused_kernel(const KernelArgs a) {
   load_z(blockIdx.x);
   store_z(blockIdx.x);
   load_z((int64_t)blockIdx.x + gridDim.x);
+  // kCertCertified: the certificate of row (lane & 31) of the tile.  Like the z~ rows it is fetched two tiles ahead, at the end of
+  // a tile, and handed on one tile later: a load issued in front of step 3 would sit in front of the Theta ring's loads, whose
+  // counted waits then wait for its HBM round trip too.  The per-slot coefficients and row blocks are a 136-double table in
+  // LDS, the two classes' coefficients scalars.
+  int ck = 0, nk = 0;
+  double cm = 0.0, ca = 0.0, nm = 0.0, na = 0.0;
+  auto load_cert = [&](int64_t t, int& k, double& m, double& av) {
+    const int64_t n = t * T + (lane & 31);
+    const bool in = n < N;                    // (tiles past the data, which the prefetch reaches, read nothing)
+    k = in ? (int)a.cert_k[n] & 63 : 0;       // (a slot of the 64: the index of the table reads below)
+    m = in ? a.cert_m[n] : 0.0;
+    av = in ? a.cert_a[n] : 0.0;
+  };
+  double ctab[4] = {0.0, 0.0, 0.0, 0.0};
+  double* const ctl = reinterpret_cast<double*>(fe + 2 * F16);      // [64] gamma | [64] delta | 64 bytes: row block of the slot
+  uint32_t cnt_proven = 0, cnt_one = 0, cnt_all = 0;
+  if constexpr (CERT == kCertCertified) {
+    load_cert(blockIdx.x, ck, cm, ca);
+    load_cert((int64_t)blockIdx.x + gridDim.x, nk, nm, na);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ctab[i] = a.cert_tab[i];
+    for (int e = tid; e < kCertTabLen - 4; e += kWG) ctl[e] = a.cert_tab[4 + e];   // (in LDS by the barrier in front of the tile loop)
+  }
 
   // feature build: thread (row = tid & 31, g = tid >> 5) produces the 2*NCB consecutive features
   // [g*2*NCB, (g+1)*2*NCB); their (a,b) byte pairs are NCB consecutive 32-bit words of the table.
@@ -400,6 +432,30 @@ void fused_kernel(const KernelArgs a) {
       // ---- 3. L tile = Theta . Phi' ------------------------------------------------------
       // B operand: lane (kk = q, col = j) holds Phi[row 16 g + j][4 s + q].
       // C/D layout of v_mfma_f64_16x16x4_f64: reg r of lane (q, j) = row q + 4 r, col j.
+      // kCertCertified: need = the rows this wave contracts (all 32 bits: the two-group code), computed = per lane, the rows whose
+      // slots of the lane's row block (lane >> 4) some wave contracts.  Every wave derives all four waves' sets from the same
+      // three ballots, on the scalar side.  A row past N is unproven.
+      uint32_t need = 0xFFFFFFFFu, computed = 0xFFFFFFFFu;
+      if constexpr (CERT == kCertCertified) {
+        const bool in = n0 + (lane & 31) < N;
+        const double cgam = ctl[ck], cdel = ctl[64 + ck];            // the row's own coefficients and row block, by its slot
+        const int cblk = reinterpret_cast<const uint8_t*>(ctl + 128)[ck];
+        const double ub = fmax(fma(ctab[1], ca, ctab[0]), fma(ctab[3], ca, ctab[2]));
+        const bool proven = in && ub <= fma(cdel, cm, cgam);
+        const uint32_t pm = (uint32_t)__builtin_amdgcn_ballot_w64(proven);
+        const uint32_t b0 = (uint32_t)__builtin_amdgcn_ballot_w64((cblk & 1) != 0), b1 = (uint32_t)__builtin_amdgcn_ballot_w64((cblk & 2) != 0);
+        uint32_t eff[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          const uint32_t nd = ~pm | (((w & 1) ? b0 : ~b0) & ((w & 2) ? b1 : ~b1));
+          eff[w] = __builtin_popcount(nd) <= 16 ? nd : 0xFFFFFFFFu;
+        }
+        need = wave == 0 ? eff[0] : wave == 1 ? eff[1] : wave == 2 ? eff[2] : eff[3];
+        computed = lane < 16 ? eff[0] : lane < 32 ? eff[1] : lane < 48 ? eff[2] : eff[3];
+        if (wave == 0) cnt_proven += __builtin_popcount(pm);
+        cnt_one += need != 0xFFFFFFFFu ? 1u : 0u;
+        cnt_all += 1u;
+      }
       if constexpr (is_split) {
         if (sidx < 2) {                     // column group sidx of row block srb
           gptr_t th = (gptr_t)(a.theta + (size_t)srb * NSI * 64);
@@ -432,6 +488,45 @@ void fused_kernel(const KernelArgs a) {
         if constexpr (SEED_TILE) load_seed(thw);   // (behind the opaque base: not hoisted back out of the tile loop)
         const double* p0 = Ph + j * RS + q;
         const double* p1 = Ph + (16 + j) * RS + q;
+        bool one_group = false;
+        if constexpr (CERT == kCertCertified) one_group = need != 0xFFFFFFFFu;      // (scalar)
+        if (one_group) {
+          if constexpr (CERT == kCertCertified) {
+            // slot jj of the column group takes the jj-th row of `need`, ascending (a scalar walk over its bits); the slots past
+            // the last one repeat the first row (none at all: row 0) and store nothing
+            const int cnt = __builtin_popcount(need);
+            int rj = need ? __builtin_ctz(need) : 0;
+            {
+              uint32_t mleft = need;
+              for (int jj = 0; mleft; ++jj) {                 // (scalar loop: a compare and a select per row)
+                rj = j == jj ? __builtin_ctz(mleft) : rj;
+                mleft &= mleft - 1;
+              }
+            }
+            int p_off = rj * RS + q;
+            asm volatile("" : "+v"(p_off));
+            const double* pc = Ph + p_off;
+            d4 acc = SEED ? d4{cseed[0], cseed[1], cseed[2], cseed[3]} : d4{0.0, 0.0, 0.0, 0.0};
+            double bq[3];
+            bq[0] = pc[0];
+            if (NS > 1) bq[1] = pc[4];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+              if (s + 2 < NS) bq[(s + 2) % 3] = pc[4 * (s + 2)];
+              __builtin_amdgcn_sched_barrier(0);
+              const double av = ring[s % PF];
+              ring[s % PF] = theta_slice((s + PF) % NEP);
+              acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bq[s % 3], acc, 0, 0, 0);
+            }
+            if (j < cnt) {
+              int lw_off = rj * LS + 16 * wave + q;
+              asm volatile("" : "+v"(lw_off));
+              double* lw = Lt + lw_off;
+#pragma unroll
+              for (int r = 0; r < 4; ++r) lw[4 * r] = acc[r];
+            }
+          }
+        } else {
 #pragma unroll
         for (int h = 0; h < RBW / RP; ++h) {       // RP row blocks per pass bound the live accumulators
           if (RBW == 1 || wave + 4 * h * RP < K16) {   // scalar: the pass has at least one live row block
@@ -482,6 +577,7 @@ void fused_kernel(const KernelArgs a) {
             }
           }
         }
+        }
 #pragma unroll
         for (int e = NE; e < NEP; ++e) ring[e % PF] = theta_slice((e + PF) % NEP);   // stream padding
       }
@@ -492,9 +588,9 @@ void fused_kernel(const KernelArgs a) {
       // ---- 4. normalise over k: 8 lanes per datum, 2*K16 consecutive components per lane ----------
       __builtin_amdgcn_s_setprio(2);
       if constexpr (RBW == 1)
-        normalise_tile<RBW, MODE, E2K, SKIP, LX>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
-                                             out_lse, sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T, lnt,
-                                             live);
+        normalise_tile<RBW, MODE, E2K, SKIP, LX, CERT>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
+                                                   out_lse, sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T, lnt,
+                                                   live, computed);
       else
         normalise_tile_chunked<RBW, MODE, LX>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
                                           out_lse, sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T);
@@ -720,6 +816,10 @@ void fused_kernel(const KernelArgs a) {
     // ---- 1'. stage the next tile's z~ rows (Zs was last read before the barrier after step 2)
     store_z(t + gridDim.x);
     load_z(t + 2 * (int64_t)gridDim.x);
+    if constexpr (CERT == kCertCertified) {
+      ck = nk; cm = nm; ca = na;
+      load_cert(t + 2 * (int64_t)gridDim.x, nk, nm, na);
+    }
     STAMP(7);
 #ifdef MIMO_STAMPS
     if (st_trace) st_tr[3] = st_prev;
@@ -754,6 +854,13 @@ void fused_kernel(const KernelArgs a) {
           for (int r = 0; r < 4; ++r)
             P[(size_t)(16 * rb + q + 4 * r) * FT + 16 * cb + j] = sacc[i][cb][r];
       }
+    }
+  }
+  if constexpr (CERT == kCertCertified) {
+    if (lane == 0) {
+      if (wave == 0) atomicAdd(a.cert_cnt, (unsigned long long)cnt_proven);
+      atomicAdd(a.cert_cnt + 1, (unsigned long long)cnt_one);
+      atomicAdd(a.cert_cnt + 2, (unsigned long long)cnt_all);
     }
   }
   if constexpr (MODE == kFastVI || MODE == kFastGibbs) sc_lse += log(sc_prod);
@@ -1241,7 +1348,8 @@ __global__ void unpack_stats(const double* __restrict__ red, const uint8_t* __re
 // (src = kSrcEstep at Dz = 14 .. 16 with K <= 64 on the full map: the instantiations with the 2048-entry exp table, fused_kernel E2K)
 size_t fused_lds_bytes(const KernelArgs& a, int src) {
   const bool e2k = src == kSrcEstep && !a.diag && a.D >= 14 && a.D <= kMaxFusedD && a.K16 <= 4;
-  return sizeof(double) * ((size_t)kTile * (a.ZS + a.RS + a.LS) + 16 + (e2k ? kExpTab : 64)) + (size_t)a.F16 * 2;
+  const size_t cert = src == kSrcEstep && a.cert == kCertCertified ? sizeof(double) * (kCertTabLen - 4) : 0;     // its table, behind the feature bytes
+  return sizeof(double) * ((size_t)kTile * (a.ZS + a.RS + a.LS) + 16 + (e2k ? kExpTab : 64)) + (size_t)a.F16 * 2 + cert;
 }
 
 // row blocks per wave: the fused E-step kernels exist for 1 and 4; the statistics modes and the chunked
@@ -1272,13 +1380,17 @@ constexpr int ncb_of(int D) { return ((D + 1) * (D + 2) / 2 + 15) / 16; }
 
 // E-step modes: one instantiation per Dz (compile-time feature map)
 template <int D, int RBW>
-static fused_fn pick_estep_mode(int mode, bool skip) {
+static fused_fn pick_estep_mode(int mode, bool skip, int cert) {
   switch (mode) {
     case kFastVI:
       // SKIP only where it costs no occupancy: at Dz >= 14 the LDS (feature tile + 2048-entry exp table) holds the
       // kernel at two workgroups per CU whatever its registers.  Below, the skip's extra VGPRs cost a workgroup per CU
       // (Dz = 12: 3 -> 2, Dz = 6 .. 8: 4 -> 3), which a pass with dense responsibilities would pay in full.
-      if constexpr (RBW == 1 && D >= 14) if (skip) return fused_kernel<ncb_of(D), 1, kFastVI, D, 0, true>;
+      if constexpr (RBW == 1 && D >= 14) {
+        if (skip && cert == kCertReference) return fused_kernel<ncb_of(D), 1, kFastVI, D, 0, true, kCertReference>;
+        if (skip && cert == kCertCertified) return fused_kernel<ncb_of(D), 1, kFastVI, D, 0, true, kCertCertified>;
+        if (skip) return fused_kernel<ncb_of(D), 1, kFastVI, D, 0, true>;
+      }
       return fused_kernel<ncb_of(D), RBW, kFastVI, D>;
     case kFastGibbs: return fused_kernel<ncb_of(D), RBW, kFastGibbs, D>;
     case kGeneric: return fused_kernel<ncb_of(D), RBW, kGeneric, D>;
@@ -1287,28 +1399,28 @@ static fused_fn pick_estep_mode(int mode, bool skip) {
 }
 
 template <int RBW>
-static fused_fn pick_estep(int D, int mode, bool skip = false) {
+static fused_fn pick_estep(int D, int mode, bool skip = false, int cert = kCertNone) {
   switch (D) {
-    case 1: return pick_estep_mode<1, RBW>(mode, skip);
-    case 2: return pick_estep_mode<2, RBW>(mode, skip);
-    case 3: return pick_estep_mode<3, RBW>(mode, skip);
-    case 4: return pick_estep_mode<4, RBW>(mode, skip);
-    case 5: return pick_estep_mode<5, RBW>(mode, skip);
-    case 6: return pick_estep_mode<6, RBW>(mode, skip);
-    case 7: return pick_estep_mode<7, RBW>(mode, skip);
-    case 8: return pick_estep_mode<8, RBW>(mode, skip);
-    case 9: return pick_estep_mode<9, RBW>(mode, skip);
+    case 1: return pick_estep_mode<1, RBW>(mode, skip, cert);
+    case 2: return pick_estep_mode<2, RBW>(mode, skip, cert);
+    case 3: return pick_estep_mode<3, RBW>(mode, skip, cert);
+    case 4: return pick_estep_mode<4, RBW>(mode, skip, cert);
+    case 5: return pick_estep_mode<5, RBW>(mode, skip, cert);
+    case 6: return pick_estep_mode<6, RBW>(mode, skip, cert);
+    case 7: return pick_estep_mode<7, RBW>(mode, skip, cert);
+    case 8: return pick_estep_mode<8, RBW>(mode, skip, cert);
+    case 9: return pick_estep_mode<9, RBW>(mode, skip, cert);
     default: break;
   }
   if constexpr (RBW == 1) {
     switch (D) {
-      case 10: return pick_estep_mode<10, 1>(mode, skip);
-      case 11: return pick_estep_mode<11, 1>(mode, skip);
-      case 12: return pick_estep_mode<12, 1>(mode, skip);
-      case 13: return pick_estep_mode<13, 1>(mode, skip);
-      case 14: return pick_estep_mode<14, 1>(mode, skip);
-      case 15: return pick_estep_mode<15, 1>(mode, skip);
-      case 16: return pick_estep_mode<16, 1>(mode, skip);
+      case 10: return pick_estep_mode<10, 1>(mode, skip, cert);
+      case 11: return pick_estep_mode<11, 1>(mode, skip, cert);
+      case 12: return pick_estep_mode<12, 1>(mode, skip, cert);
+      case 13: return pick_estep_mode<13, 1>(mode, skip, cert);
+      case 14: return pick_estep_mode<14, 1>(mode, skip, cert);
+      case 15: return pick_estep_mode<15, 1>(mode, skip, cert);
+      case 16: return pick_estep_mode<16, 1>(mode, skip, cert);
     }
   }
   return nullptr;
@@ -1397,7 +1509,7 @@ static fused_fn resolve_fused(const KernelArgs& a, int src) {
     static const bool rbw2 = [] { const char* e = getenv("MIMO_ESTEP_RBW2"); return !e || atoi(e) != 0; }();   // tuning knob
     if (rbw2 && a.K16 > 4 && a.K16 <= 8) if (fused_fn f = pick_estep<2>(a.D, mode)) return f;
     if (rbw2 && a.K16 > 8 && a.K16 <= 12) if (fused_fn f = pick_estep<3>(a.D, mode)) return f;     // 128 < K <= 192: three
-    return rbw_for(a.K16) == 1 ? pick_estep<1>(a.D, mode, a.resp_skip > 0) : pick_estep<4>(a.D, mode);
+    return rbw_for(a.K16) == 1 ? pick_estep<1>(a.D, mode, a.resp_skip > 0, a.K16 == 4 ? a.cert : kCertNone) : pick_estep<4>(a.D, mode);
   }
   if (a.K16 <= 2 && ncb >= 3) {   // K <= 32: split distribution of the statistics column blocks (see fused_kernel, SPLIT)
     static const bool on = [] { const char* e = getenv("MIMO_SPLIT_STATS"); return !e || atoi(e) != 0; }();   // tuning knob

@@ -112,8 +112,26 @@ __device__ __forceinline__ void build_features_static(const double (&zl)[D + 2],
 // writes byte w of every word (its rows 8w .. 8w+7), so the words need no clearing between tiles.
 // LX: the butterfly stages (lane ^ 8, ^ 16, ^ 32) of the maximum, the sums and the label count exchange lanes in registers
 // (lane_xor_max / lane_xor_sum, mimo_device.h) instead of through __shfl_xor; the caller says which, same bits either way.
+// CERT (SKIP at K16 = 4, DESIGN section 4 "E-step certificates"), everything delivered bit for bit what CERT = 0 delivers:
+//   kCertReference  also stores, per row < N, the slot of the largest l, that l, and the largest l outside its row block.  The
+//                   block maxima exist after the lane ^ 8 stage; the stages ^ 16 and ^ 32 then carry the pair (largest,
+//                   second largest block maximum): the second largest IS the largest outside the winner's block.  One lane
+//                   per row stores: of the lanes whose own maximum equals the row's, the lowest.
+//   kCertCertified  bit pt of `computed` says whether this lane's 8 slots of row pt were contracted this tile; a lane whose slots
+//                   were not loads -inf instead of the stale tile.  Such a lane belongs to a row proven dead in its block: the
+//                   maximum lies elsewhere, its exponentials are 0 where CERT = 0 has values below 2^-60 (48 of them at most:
+//                   under half an ulp of a sum >= 1, which they meet only at the ^ 16 and ^ 32 stages), its live bit is clear
+//                   either way, and nothing reads the weights it writes back.
 // ------------------------------------------------------------------------------------------
-template <int RBW, int MODE, bool E2K = false, bool SKIP = false, bool LX = false>
+// {max, min} of v and the value of lane ^ MASK (MASK 16 or 32: the swap hands them over in lane-dependent order)
+template <int MASK>
+__device__ __forceinline__ void lane_xor_maxmin(double v, double& hi, double& lo) {
+  const LanePair l = lane_xor_pair<MASK>(__double2loint(v)), h = lane_xor_pair<MASK>(__double2hiint(v));
+  const double x = __hiloint2double(h.a, l.a), y = __hiloint2double(h.b, l.b);
+  hi = fmax(x, y);
+  lo = fmin(x, y);
+}
+template <int RBW, int MODE, bool E2K = false, bool SKIP = false, bool LX = false, int CERT = 0>
 __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __restrict__ Lt, const int LS,
                                                const double* __restrict__ etab, const int K, const int K16,
                                                const int64_t N, const int64_t n0, const int wave, const int lane,
@@ -121,9 +139,10 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
                                                double* const out_lse, double& sc_lse, double& sc_rl, double& sc_prod,
                                                int* __restrict__ labs, PhiloxBatch& pb,
                                                const int64_t tstride, const double lnt = 0.0,
-                                               uint32_t* __restrict__ live = nullptr) {
+                                               uint32_t* __restrict__ live = nullptr, const uint32_t computed = 0) {
         static_assert(RBW == 1, "register variant: at most 8 components per lane");
         static_assert(!SKIP || MODE == kFastVI, "responsibility skip: softmax of the fast VI mode only");
+        static_assert(CERT == 0 || (SKIP && LX), "certificates: the skipping softmax pass, lane exchanges in registers");
         const int pt = 8 * wave + (lane & 7), part = lane >> 3;
         const int CPP = 2 * K16, k0 = part * CPP;
         const int64_t n = n0 + pt;
@@ -138,8 +157,14 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
         auto ok = [&](int c) { return FULL || c < CPP; };
         // x[] holds l, then exp(l - max), then the weight written back — one register array
         double x[8], lsave[8];
+        if constexpr (CERT == kCertCertified && FULL) {
+          const bool have = (computed >> pt) & 1u;
 #pragma unroll
-        for (int c = 0; c < 8; ++c) x[c] = ok(c) ? row[c] : -INFINITY;
+          for (int c = 0; c < 8; ++c) x[c] = have ? row[c] : -INFINITY;
+        } else {
+#pragma unroll
+          for (int c = 0; c < 8; ++c) x[c] = ok(c) ? row[c] : -INFINITY;
+        }
         if (out_logp && valid) {
 #pragma unroll
           for (int c = 0; c < 8; ++c)
@@ -147,8 +172,27 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
         }
         const double ml = tree_max8(x);     // the lane's own maximum (SKIP, FULL: kept for the live mask)
         double m = butterfly_max<LX, 8>(ml);
-        m = butterfly_max<LX, 16>(m);
-        m = butterfly_max<LX, 32>(m);
+        if constexpr (CERT == kCertReference && FULL) {
+          double m16, s16, s32, t32, u32;
+          lane_xor_maxmin<16>(m, m16, s16);         // (largest, second largest) of this pair of row blocks
+          lane_xor_maxmin<32>(m16, m, t32);         // m: fmax of the same two values as below, the same bits
+          lane_xor_maxmin<32>(s16, s32, u32);
+          const double second = fmax(t32, s32);     // the largest block maximum but one = the largest l outside the winner's block
+          const bool cand = valid && ml == m;
+          const uint64_t bal = __builtin_amdgcn_ballot_w64(cand);
+          const uint64_t mine = (bal >> (lane & 7)) & 0x0101010101010101ull;      // bit 8 p: part p of this row is a candidate
+          if (cand && (mine & ((1ull << (8 * part)) - 1ull)) == 0) {              // the lowest candidate part of the row stores
+            int cs = 7;
+#pragma unroll
+            for (int c = 6; c >= 0; --c) cs = x[c] == ml ? c : cs;
+            a.cert_k[n] = (uint8_t)(k0 + cs);
+            a.cert_m[n] = m;
+            a.cert_a[n] = second;
+          }
+        } else {
+          m = butterfly_max<LX, 16>(m);
+          m = butterfly_max<LX, 32>(m);
+        }
 
         if constexpr (SKIP) {
           uint32_t bytes = 0;               // byte b: the live rows of this wave in row block b

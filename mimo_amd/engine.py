@@ -257,8 +257,17 @@ class HipEngine(BoundDataGuard):
     def tune(self, key, value):
         """Launch-geometry override for tests and experiments (mimo_tune): 'num_cu' (0: the device's own), 'sorted_range',
         'resp_skip_log2' (statistics skip weights below 2^-value, default 60; 0: dense), 'block_order' (0: set_component_order
-        becomes a no-op, default 1)."""
+        becomes a no-op, default 1), 'estep_cert' (0: no per-row E-step certificates, default 1)."""
         self._check(self._lib.mimo_tune(self._ctx, key.encode(), int(value)))
+
+    def estep_cert_info(self):
+        """What the per-row E-step certificates did (mimo_estep_cert_info): kind of the last pass ('plain', 'reference',
+        'certified'), whether certificates are in force, certified passes since the reference pass, and the context's running
+        totals over its certified passes: rows proven, wave-tiles on one column group, wave-tiles."""
+        out = np.zeros(6, dtype=np.int64)
+        self._check(self._lib.mimo_estep_cert_info(self._ctx, _ptr(out)))
+        return {"kind": ("plain", "reference", "certified")[int(out[0])], "valid": bool(out[1]), "age": int(out[2]),
+                "proven_rows": int(out[3]), "one_group": int(out[4]), "wave_tiles": int(out[5])}
 
     def profile(self, enable=True):
         self._check(self._lib.mimo_profile(self._ctx, 1 if enable else 0))

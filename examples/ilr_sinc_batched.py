@@ -16,7 +16,10 @@ unseeded, and here each model gets a stream of its own seeded the same way, so a
 
 --resident runs the coordinate-descent VI (after the Gibbs warm-up, if one is asked for) with the device-resident loop,
 meanfield_coordinate_descent_batched_ilr: the update of the three blocks, the canonical form, the bound and the stopping rule stay
-on the device between two passes; the likelihoods are drawn once, at the end.  It has no effect on --svi-iters.
+on the device between two passes; the likelihoods are drawn once, at the end.  Together with --svi-iters it runs the stochastic
+flow with the device-resident SVI loop instead (meanfield_stochastic_descent_batched(resident=True,
+sample_likelihood=False)): the natural-gradient step of every model runs on the device too, the minibatch indices are still
+drawn on each model's Python stream.
 
 --predict adds what the reference job is run for (its lines 196-201): ONE batched prediction of all fitted models over the
 full input grid (meanfield_prediction_batched: the grid goes to the device once, each model's standardisation is applied in
@@ -65,7 +68,8 @@ def main():
     ap.add_argument("--svi-batch", type=int, default=256, help="rows per minibatch of stochastic VI")
     ap.add_argument("--predict", action="store_true", help="one batched prediction of all models on the full input grid")
     ap.add_argument("--resident", action="store_true",
-                    help="coordinate-descent VI with the device-resident loop (no per-iteration likelihood draws)")
+                    help="the device-resident loop of coordinate-descent VI, or with --svi-iters of stochastic VI (no "
+                         "per-iteration likelihood draws)")
     args = ap.parse_args()
     rng = np.random.default_rng(1337)
     x = rng.uniform(-10., 10., size=(args.rows, 1))
@@ -85,9 +89,10 @@ def main():
         gibbs = time.perf_counter() - t0
         print(f"Gibbs warm-up: {args.gibbs_iters} sweeps of {args.fits} models in {gibbs:.2f} s")
     if args.svi_iters > 0:
+        resident = dict(resident=True, sample_likelihood=False) if args.resident else {}
         vlbs = meanfield_stochastic_descent_batched(models, data, randomize=False, maxiter=args.svi_iters, step_size=0.5,
                                                     batch_size=args.svi_batch, numpy_seeds=range(args.fits),
-                                                    python_seeds=range(args.fits))
+                                                    python_seeds=range(args.fits), **resident)
     elif args.gibbs_iters > 0:
         descent = meanfield_coordinate_descent_batched_ilr if args.resident else meanfield_coordinate_descent_batched
         vlbs = descent(models, data, randomize=False, maxiter=args.iters, tol=1e-6)

@@ -67,6 +67,7 @@ typedef struct mimo_ctx mimo_ctx;
 #define MIMO_F_ENTROPY_SPLIT  0x40  /* also produce scalars[1], scalars[2] (see above)             */
 #define MIMO_F_ASYNC          0x80  /* enqueue only; fetch the host results with mimo_wait()       */
 #define MIMO_F_DIAG_VAR       0x200 /* mimo_predict_flags: the second output is (N, dy) variances followed by (N, dy) standard deviations */
+#define MIMO_F_SVI_RESIDENT_START 0x400 /* mimo_svi_run_batched: the first step runs on the statistics already resident */
 #define MIMO_F_WEIGHTS_RESIDENT 0x100 /* mimo_estep_weighted: reuse the row weights the previous weighted call uploaded
                                          (the hierarchical drivers pass the same vector every iteration: N doubles less
                                          over PCIe per call); `row_weights` is ignored                                */
@@ -547,6 +548,61 @@ int mimo_vi_ilr_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int fla
  * (mimo/distributions/composite.py:50-72,106-128,577-599,635-647; mixtures/ilr.py:178-189).  Zeros for a problem that has not
  * finished an iteration. */
 int mimo_vi_ilr_get_batched(mimo_ctx* ctx, int K, double* out);
+
+/* ---- device-resident batched SVI: the natural-gradient step between two passes, on the device ----
+ * Stochastic variational inference of the two families above without a host step per model and iteration: the loop state, the
+ * prior blocks, the posterior blocks (mimo_vi_get_batched / mimo_vi_ilr_get_batched), the test hook mimo_vi_get_theta_batched, the
+ * status bits and the determinism rule are those of the VI loops.  Call order: upload, the family's *_prior_batched, the family's
+ * state call, then any number of run calls.
+ *
+ * mimo_svi_state_batched / mimo_svi_ilr_state_batched: the starting posterior of every problem, as natural parameters.
+ * Replaces: the posterior a model brings into meanfield_stochastic_descent (mimo/mixtures/gmm.py:300-326, ilr.py:245-277) — its
+ *   nat_param read by the first meanfield_sgd (mimo/distributions/bayesian.py:85-91,161-172,232-238,846-852) and its expected
+ *   log-densities read by the first minibatch pass.
+ *   GMM: alpha (B,K) the Dirichlet concentrations; qa (B,K,Dz), qb (B,K), qc (B,K,Dz,Dz), qd (B,K) the Normal-Wishart natural
+ *   parameters.  ILR: g0, g1 (B,K) the concentrations (g1 ignored, may be NULL) or the gammas and deltas; qa (B,K,dx), qb, qc
+ *   (B,K,dx,dx), qd of the basis; ma (B,K,dy,dc), mKq (B,K,dc,dc), mc (B,K,dy,dy), md (B,K) of the experts.  Every element finite
+ *   (MIMO_E_INVALID names the part and the problem).  The call resets the loop as the prior call does, writes the parts into the
+ *   current posterior block and runs the update and the gating kernel in their init mode: the standard parameters, the canonical
+ *   form into the operand image and the prior terms of the bound of exactly these natural parameters (no statistics are read).
+ *   status (B): the VI loop's bits for a posterior whose blocks do not factorise or whose canonical form is not finite; such a
+ *   problem is skipped by every later run.  MIMO_E_STATE when the family's prior block is not resident.  The iteration counter of
+ *   the index draws restarts at 0. */
+int mimo_svi_state_batched(mimo_ctx* ctx, int K, const double* alpha, const double* qa, const double* qb, const double* qc,
+                           const double* qd, int32_t* status);
+int mimo_svi_ilr_state_batched(mimo_ctx* ctx, int K, const double* g0, const double* g1, const double* qa, const double* qb,
+                               const double* qc, const double* qd, const double* ma, const double* mKq, const double* mc,
+                               const double* md, int32_t* status);
+
+/* `iters` SVI iterations of every problem, enqueued without a host synchronisation: per iteration the softmax pass over a
+ * minibatch of every problem's resident rows (the selection pass of mimo_estep_batched_rows) on the current image, its reduction,
+ * the update and the gating kernel in their blend mode,
+ *     eta_new = (1 - step_size) eta_cur + step_size (eta_prior + (1 / scale_b) S),
+ * on every part of the posterior (Normal-Wishart qa qb qc qd; experts a Kq c d; Dirichlet on alpha - 1; stick-breaking gamma and
+ * delta, delta from the counts of the later sticks) in the host's operation order with no product fused into a sum, then
+ * everything the VI loop derives from eta, a plain pass over ALL rows without statistics, and vlb = prior terms + sum lse.
+ * Replaces: per model and iteration, the body of meanfield_stochastic_descent (mimo/mixtures/gmm.py:300-326, ilr.py:245-277):
+ *   the minibatch E-step, meanfield_sgd of the blocks and the gating (mimo/distributions/bayesian.py:85-91,161-172,232-238,
+ *   846-852), the full-data E-step and the bound.
+ *   step_size in (0, 1]; scale (B): batch size / N_b of every problem, each finite and > 0 (in (0, 1] for a minibatch without
+ *   replacement; above 1 only where the device draws more slots than the problem has rows).
+ *   sel_off (B+1): problem b's minibatch is the slots [sel_off[b], sel_off[b+1]) of every iteration's selection (one work table
+ *   per call).  rows non-NULL: n_sel x sel_off[B] local row indices on the host, iteration-major; every one is checked against
+ *   N_b before anything is enqueued (MIMO_E_INVALID names the iteration, the problem and the index).  rows NULL, seeds (B)
+ *   non-NULL: drawn on the device with replacement, slot j of problem b at iteration t being
+ *   min((int64)(mimo_philox_uniform(seeds[b], j, t) N_b), N_b - 1), t counted from the state call across run calls.
+ *   n_sel = iters, or iters - 1 under MIMO_F_SVI_RESIDENT_START: the call's first iteration then runs no selection pass and steps
+ *   on the statistics already resident (those of the random start's table pass; MIMO_E_STATE if none of this K are valid).
+ *   trace (iters, B), n_done (B), status (B): as mimo_vi_run_batched; SVI has no stopping rule, so every problem whose status is
+ *   clear appends `iters` bounds.  A problem whose status gets set keeps its last complete block; the others are not affected; the
+ *   call returns MIMO_OK.  1 <= iters <= 65536; any other flag is MIMO_E_INVALID.  MIMO_E_STATE without the family's prior block
+ *   or without a state call since.
+ * The statistics of the last minibatch stay resident, the scalars behind them are those of the last plain pass. */
+int mimo_svi_run_batched(mimo_ctx* ctx, int K, int iters, double step_size, const double* scale, const int64_t* rows,
+                         const int64_t* sel_off, const uint64_t* seeds, int flags, double* trace, int32_t* n_done, int32_t* status);
+int mimo_svi_ilr_run_batched(mimo_ctx* ctx, int K, int iters, double step_size, const double* scale, const int64_t* rows,
+                             const int64_t* sel_off, const uint64_t* seeds, int flags, double* trace, int32_t* n_done,
+                             int32_t* status);
 
 /* Posterior-predictive mixture moments of B ILR models in one launch: per problem b what mimo_predict_flags returns on a
  * context whose resident rows are (X_b - shift_b) / scale_b, bit for bit, and the same bits whatever else is in the batch.

@@ -17,6 +17,7 @@ E_INVALID, E_HIP, E_NODATA, E_UNSUPPORTED, E_STATE, E_NOMEM, E_INTERNAL = -1, -2
 F_KEEP_RESP, F_KEEP_LOGP, F_KEEP_LSE, F_NO_STATS, F_DEVICE_OUT, F_DEVICE_IN, F_ENTROPY_SPLIT, F_ASYNC = 1, 2, 4, 8, 0x10, 0x20, 0x40, 0x80
 F_WEIGHTS_RESIDENT = 0x100
 F_DIAG_VAR = 0x200
+F_SVI_RESIDENT_START = 0x400
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -52,6 +53,10 @@ SIGNATURES = {
     "mimo_vi_ilr_prior_batched": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 12),
     "mimo_vi_ilr_run_batched": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp]),
     "mimo_vi_ilr_get_batched": (C.c_int, [_vp, C.c_int, _vp]),
+    "mimo_svi_state_batched": (C.c_int, [_vp, C.c_int] + [_vp] * 6),
+    "mimo_svi_ilr_state_batched": (C.c_int, [_vp, C.c_int] + [_vp] * 11),
+    "mimo_svi_run_batched": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "mimo_svi_ilr_run_batched": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "mimo_estep_weighted": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "mimo_wait": (C.c_int, [_vp, _vp, _vp]),
     "mimo_gibbs_labels": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_uint64, C.c_uint64, _vp,

@@ -589,6 +589,138 @@ class BatchedHipEngine:
             o += n
         return state
 
+    # ---- device-resident SVI (mimo_svi_state_batched / mimo_svi_run_batched and their _ilr_ forms) ----
+    def _svi_status(self, call, *args):
+        status = np.empty(self.B, dtype=np.int32)
+        self._check(getattr(self._lib, call)(self._ctx, *args, _ptr(status)))
+        return status
+
+    def svi_set_state(self, alpha, qa, qb, qc, qd):
+        """The starting posterior of the B mixtures of Gaussians whose priors vi_set_prior uploaded, as natural parameters:
+        alpha (B, K) the Dirichlet concentrations, qa (B, K, Dz), qb (B, K), qc (B, K, Dz, Dz), qd (B, K), all finite.  Resets
+        the loop, then derives on the device what the first minibatch pass and the first bound need: standard parameters,
+        canonical form, operand image, prior terms (mimo_svi_state_batched).  Returns status (B,), vi_run's bits."""
+        alpha, qa, qb, qc, qd = (_f64(v) for v in (alpha, qa, qb, qc, qd))
+        if alpha.ndim != 2:
+            raise ValueError(f"alpha must be (B, K), got shape {alpha.shape}")
+        B, K = alpha.shape
+        if B != self.B:
+            raise ValueError(f"a state for {B} problems, {self.B} uploaded")
+        D = self.D
+        want = ((B, K), (B, K, D), (B, K), (B, K, D, D), (B, K))
+        got = tuple(v.shape for v in (alpha, qa, qb, qc, qd))
+        if got != want:
+            raise ValueError(f"state shapes {got} do not match B={B}, K={K}, Dz={D}: {want}")
+        if not all(np.all(np.isfinite(v)) for v in (alpha, qa, qb, qc, qd)):
+            raise ValueError("the state must be finite")
+        return self._svi_status('mimo_svi_state_batched', K, _ptr(alpha), _ptr(qa), _ptr(qb), _ptr(qc), _ptr(qd))
+
+    def svi_ilr_set_state(self, g0, g1, basis, experts):
+        """svi_set_state for the mixtures of linear-Gaussian experts whose priors vi_ilr_set_prior uploaded: g0, g1 (B, K) the
+        gating's concentrations and None, or its gammas and deltas; basis = (qa (B, K, dx), qb (B, K), qc (B, K, dx, dx),
+        qd (B, K)); experts = (a (B, K, dy, dx + 1), Kq (B, K, dx + 1, dx + 1), c (B, K, dy, dy), d (B, K))
+        (mimo_svi_ilr_state_batched).  Returns status (B,)."""
+        dims = getattr(self, '_vi_ilr_dims', None)
+        if dims is None:
+            raise ValueError("no ILR prior block was set (vi_ilr_set_prior)")
+        if len(basis) != 4 or len(experts) != 4:
+            raise ValueError("basis and experts are 4 arrays each: the natural parameters")
+        dx, dy = dims
+        dc = dx + 1
+        g0 = _f64(g0)
+        if g0.ndim != 2:
+            raise ValueError(f"g0 must be (B, K), got shape {g0.shape}")
+        B, K = g0.shape
+        if B != self.B:
+            raise ValueError(f"a state for {B} problems, {self.B} uploaded")
+        parts = (g0,) + ((_f64(g1),) if g1 is not None else ()) + tuple(_f64(v) for v in tuple(basis) + tuple(experts))
+        want = ((B, K),) * (2 if g1 is not None else 1) + ((B, K, dx), (B, K), (B, K, dx, dx), (B, K),
+                                                           (B, K, dy, dc), (B, K, dc, dc), (B, K, dy, dy), (B, K))
+        got = tuple(v.shape for v in parts)
+        if got != want:
+            raise ValueError(f"state shapes {got} do not match B={B}, K={K}, dx={dx}, dy={dy}: {want}")
+        if not all(np.all(np.isfinite(v)) for v in parts):
+            raise ValueError("the state must be finite")
+        rest = parts[2:] if g1 is not None else parts[1:]
+        return self._svi_status('mimo_svi_ilr_state_batched', K, _ptr(g0), _ptr(parts[1]) if g1 is not None else None,
+                                *(_ptr(v) for v in rest))
+
+    def _svi_run(self, call, K, iters, step_size, scale, batch_sizes, rows, seeds, resident_start):
+        K, iters, step_size = int(K), int(iters), float(step_size)
+        if K < 1 or iters < 1:
+            raise ValueError(f"K = {K} and iters = {iters} must be >= 1")
+        if not 0. < step_size <= 1.:
+            raise ValueError(f"step_size = {step_size} outside (0, 1]")
+        scale = _f64(scale).reshape(-1)
+        if scale.shape != (self.B,):
+            raise ValueError(f"scale must hold one factor per problem ({self.B}), got {scale.size}")
+        if not np.all(np.isfinite(scale) & (scale > 0.)):
+            raise ValueError(f"every scale must be finite and > 0, got {scale}")
+        sizes = np.asarray(batch_sizes)
+        if sizes.shape != (self.B,) or sizes.dtype.kind not in 'iu' or np.any(sizes < 0):
+            raise ValueError(f"batch_sizes must hold one count >= 0 per problem ({self.B}), got {batch_sizes!r}")
+        sel_off = np.zeros(self.B + 1, dtype=np.int64)
+        sel_off[1:] = np.cumsum(sizes)
+        per, n_sel = int(sel_off[-1]), iters - (1 if resident_start else 0)
+        nrows = np.diff(self.row_off)
+        flat = sd = None
+        if rows is not None:
+            if seeds is not None:
+                raise ValueError("rows and seeds: give the indices or the Philox seeds, not both")
+            rows = list(rows)
+            if len(rows) != n_sel:
+                raise ValueError(f"{len(rows)} selections for {iters} iterations"
+                                 + (" after a resident start" if resident_start else "") + f": {n_sel} are needed")
+            flat = np.empty((max(n_sel, 1), max(per, 1)), dtype=np.int64)
+            for t, sel in enumerate(rows):
+                if isinstance(sel, np.ndarray) and sel.ndim == 1 and sel.size == per:
+                    sel = np.split(sel, sel_off[1:-1])
+                sel = [np.asarray(r) for r in sel]
+                if len(sel) != self.B:
+                    raise ValueError(f"selection {t} holds the rows of {len(sel)} problems, {self.B} uploaded")
+                for i, r in enumerate(sel):
+                    if r.shape != (int(sizes[i]),) or (r.size and r.dtype.kind not in 'iu'):
+                        raise ValueError(f"selection {t} of problem {i} must be {int(sizes[i])} integers, got shape {r.shape}, "
+                                         f"dtype {r.dtype}")
+                    if r.size and (int(r.min()) < 0 or int(r.max()) >= int(nrows[i])):
+                        raise ValueError(f"selection {t} of problem {i} holds an index outside [0, {int(nrows[i])})")
+                    flat[t, sel_off[i]:sel_off[i + 1]] = r
+        elif seeds is not None:
+            sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+            if sd.shape != (self.B,):
+                raise ValueError(f"seeds must hold one Philox seed per problem ({self.B}), got {sd.size}")
+            if n_sel > 0 and np.any((sizes > 0) & (nrows < 1)):
+                raise ValueError("a problem without rows cannot draw a minibatch")
+        elif n_sel > 0 and per > 0:
+            raise ValueError("rows and seeds are both None: give the indices or one Philox seed per problem")
+        trace = np.empty((iters, self.B))
+        n_done = np.empty(self.B, dtype=np.int32)
+        status = np.empty(self.B, dtype=np.int32)
+        self._check(getattr(self._lib, call)(
+            self._ctx, K, iters, step_size, _ptr(scale), _ptr(flat) if flat is not None else None, _ptr(sel_off),
+            _ptr(sd) if sd is not None else None, _lib.F_SVI_RESIDENT_START if resident_start else 0, _ptr(trace), _ptr(n_done),
+            _ptr(status)))
+        return trace, n_done, status
+
+    def svi_run(self, K, iters, step_size, scale, batch_sizes, rows=None, seeds=None, resident_start=False):
+        """`iters` SVI iterations of every problem on the device (mimo_svi_run_batched), from the state svi_set_state
+        uploaded or the last call left: minibatch pass, natural-gradient step
+        eta <- (1 - step_size) eta + step_size (eta_prior + S / scale_b), canonical form, pass over all rows, bound.
+        scale (B,): batch size / N_b, finite and > 0 (above 1 only for device draws of more slots than rows).
+        batch_sizes (B,): the slots of problem b's minibatch, the same in every iteration.  rows: one selection per
+        iteration, each a list of B integer arrays (or their concatenation), problem b's holding batch_sizes[b] local rows in
+        [0, N_b); or seeds (B,): the indices are drawn on the device, slot j of problem b at iteration t =
+        min(int(philox_uniform(seeds[b], j, t) * N_b), N_b - 1), t counted from svi_set_state.
+        resident_start: the call's first iteration steps on the statistics already resident and takes no selection (rows
+        then holds iters - 1).  Returns (trace (iters, B), n_done (B,), status (B,)) as vi_run; there is no stopping rule."""
+        return self._svi_run('mimo_svi_run_batched', K, iters, step_size, scale, batch_sizes, rows, seeds, resident_start)
+
+    def svi_ilr_run(self, K, iters, step_size, scale, batch_sizes, rows=None, seeds=None, resident_start=False):
+        """svi_run for the mixtures of linear-Gaussian experts of vi_ilr_set_prior / svi_ilr_set_state
+        (mimo_svi_ilr_run_batched)."""
+        return self._svi_run('mimo_svi_ilr_run_batched', K, iters, step_size, scale, batch_sizes, rows, seeds,
+                             resident_start)
+
     def get_row_weights(self):
         """The resident row weights (the last weighted pass's, or those of outer_responsibilities): a list of B arrays (N_b,)."""
         out = np.empty(max(int(self.row_off[-1]), 1))

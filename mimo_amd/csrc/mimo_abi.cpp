@@ -631,6 +631,7 @@ int mimo_abi::set_data(mimo_ctx* ctx, int64_t N, int Dz) {
   ctx->batch_w_valid = false;
   ctx->batch_stats_valid = false;
   ctx->vi_prior_valid = false;
+  ctx->svi_state_valid = false;
   return prepare_features(ctx, Dz);
 }
 

@@ -21,6 +21,10 @@
 //   mimo_random_resp_stats_batched       resp (K); statistics                  —
 //   mimo_vi_prior_batched                the priors and the loop state (K)     —
 //   mimo_vi_run_batched                  statistics (of the last iteration)    resp, logp, labels, lse
+//   mimo_svi_state_batched, _ilr_        the starting posterior of the SVI     the loop's trace and status (reset)
+//                                        loop (K), its image and prior terms
+//   mimo_svi_run_batched, _ilr_          statistics (of the last minibatch),   resp, logp, labels, lse
+//                                        scalars (of the last plain pass)
 //   mimo_predict_batched                 —                                     statistics (the outputs take the result block)
 //   the getters                          —                                     —
 #include "mimo_abi_internal.h"
@@ -618,6 +622,7 @@ int mimo_vi_prior_batched(mimo_ctx* ctx, int K, const double* alpha0, const doub
       if (!std::isfinite(parts[t][i]))
         return fail(ctx, MIMO_E_INVALID, "%s: %s of problem %d holds a NaN or an infinity", me, names[t], (int)(i / (lens[t] / B)));
   ctx->vi_prior_valid = false;
+  ctx->svi_state_valid = false;
   const ViLayout L{K, ctx->D};
   const size_t nprior = BK * (4 + D + D * D), npost = 2 * B * (size_t)L.count(), nwork = BK + 2 * B;
   const size_t ntheta = image_len(ctx, K), nwords = vi_words_len(ctx->batch_B);
@@ -649,6 +654,37 @@ int mimo_vi_prior_batched(mimo_ctx* ctx, int K, const double* alpha0, const doub
 
 static ViIlrArgs vi_ilr_args(mimo_ctx* ctx, int K);
 
+// Room for the loop's words and the trace of a call of `iters` iterations, on the device and in the pinned sibling; *total: their
+// doubles.  A longer trace than any before: the words move to the new block.
+static int vi_loop_room(mimo_ctx* ctx, int iters, size_t* total) {
+  const int B = ctx->batch_B;
+  const size_t nwords = vi_words_len(B);
+  int rc;
+  *total = nwords + (size_t)iters * B;
+  if (ctx->vi_loop.cap < *total) {
+    Buf<double> grown;
+    if ((rc = grown.ensure(ctx, *total))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(grown.p, ctx->vi_loop.p, nwords * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::swap(grown.p, ctx->vi_loop.p);
+    std::swap(grown.cap, ctx->vi_loop.cap);
+  }
+  return ctx->vi_loop_h.ensure(ctx, *total);
+}
+
+// The end of a loop call: the words and the trace to the host in one copy behind everything queued, then the caller's arrays
+static int vi_loop_out(mimo_ctx* ctx, int iters, size_t total, double* trace, int32_t* n_done, int32_t* status) {
+  const int B = ctx->batch_B;
+  const size_t nwords = vi_words_len(B);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_loop_h, ctx->vi_loop, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const int32_t* words = reinterpret_cast<const int32_t*>(ctx->vi_loop_h.p);
+  if (trace) memcpy(trace, ctx->vi_loop_h + nwords, (size_t)iters * B * sizeof(double));
+  if (n_done) memcpy(n_done, words + (size_t)kViDone * B, (size_t)B * sizeof(int32_t));
+  memcpy(status, words + (size_t)kViStatus * B, (size_t)B * sizeof(int32_t));
+  return MIMO_OK;
+}
+
 // The loop of both families: `family` chooses the update and the gating kernel; the pass, its reduction and the finish are shared
 static int vi_run(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status,
                   const char* me, int family) {
@@ -666,16 +702,8 @@ static int vi_run(mimo_ctx* ctx, int K, int iters, double tol, int flags, double
   if (ctx->batch_stats_K != K)
     return fail(ctx, MIMO_E_STATE, "%s: the resident statistics are those of K = %d, not K = %d", me, ctx->batch_stats_K, K);
   const int B = ctx->batch_B, G = ctx->batch_G;
-  const size_t nwords = vi_words_len(B), ntrace = (size_t)iters * B, total = nwords + ntrace;
-  if (ctx->vi_loop.cap < total) {          // a longer trace than any before: the words move to the new block
-    Buf<double> grown;
-    if ((rc = grown.ensure(ctx, total))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(grown.p, ctx->vi_loop.p, nwords * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::swap(grown.p, ctx->vi_loop.p);
-    std::swap(grown.cap, ctx->vi_loop.cap);
-  }
-  if ((rc = ctx->vi_loop_h.ensure(ctx, total))) return rc;
+  size_t total = 0;
+  if ((rc = vi_loop_room(ctx, iters, &total))) return rc;
   if ((rc = ensure_partials(ctx, K, (size_t)G))) return rc;
   leaves(ctx, kPassTables, 0);
 
@@ -701,13 +729,7 @@ static int vi_run(mimo_ctx* ctx, int K, int iters, double tol, int flags, double
     if ((rc = batched_reduce(ctx, K, ctx->batch_wg_off_d, 0, true))) return rc;
     HIP_TRY(ctx, launch_vi_finish(va, it, ctx->stream));
   }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_loop_h, ctx->vi_loop, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const int32_t* words = reinterpret_cast<const int32_t*>(ctx->vi_loop_h.p);
-  memcpy(trace, ctx->vi_loop_h + nwords, ntrace * sizeof(double));
-  memcpy(n_done, words + (size_t)kViDone * B, (size_t)B * sizeof(int32_t));
-  memcpy(status, words + (size_t)kViStatus * B, (size_t)B * sizeof(int32_t));
-  return MIMO_OK;
+  return vi_loop_out(ctx, iters, total, trace, n_done, status);
   });
 }
 
@@ -830,6 +852,7 @@ int mimo_vi_ilr_prior_batched(mimo_ctx* ctx, int K, int dx, int dy, int gating_k
         return fail(ctx, MIMO_E_INVALID, "%s: %s of problem %d holds a NaN or an infinity", me, names[t], (int)(i / (lens[t] / B)));
   }
   ctx->vi_prior_valid = false;
+  ctx->svi_state_valid = false;
   const ViIlrLayout L{K, dx, dy};
   const size_t npost = 2 * B * (size_t)L.count(), nwork = 2 * BK + 2 * B;
   const size_t ntheta = image_len(ctx, K), nwords = vi_words_len(ctx->batch_B);
@@ -865,6 +888,240 @@ int mimo_vi_ilr_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int fla
 }
 
 int mimo_vi_ilr_get_batched(mimo_ctx* ctx, int K, double* out) { return vi_get(ctx, K, out, "mimo_vi_ilr_get_batched", 1); }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Device-resident batched SVI (the blend and init modes of mimo_vi_batched.hip / mimo_vi_ilr_batched.hip, svi_indices_kernel)
+// ------------------------------------------------------------------------------------------
+// The loop lives in the buffers of the VI loop of its family; what it adds: svi_sel (the minibatch indices of one call) and
+// svi_tables (the selection's small tables, the Philox seeds and 1 / scale).
+
+// One part of an uploaded posterior: `len` doubles per problem, at `at` of the family's posterior block
+struct SviPart { const char* name; const double* src; size_t len; size_t at; };
+
+// What mimo_svi_state_batched and mimo_svi_ilr_state_batched share: the parts, checked finite, into slot 0 of a loop that is reset
+// as the prior call resets it; then the init mode of the family's update and gating kernel, and the status words back.
+static int svi_state(mimo_ctx* ctx, int K, const SviPart* parts, int nparts, size_t per, int32_t* status, const char* me,
+                     int family) {
+  const size_t B = (size_t)ctx->batch_B;
+  for (int t = 0; t < nparts; ++t)
+    if (!parts[t].src) return fail(ctx, MIMO_E_INVALID, "%s: %s is NULL", me, parts[t].name);
+  if (!status) return fail(ctx, MIMO_E_INVALID, "%s: status is NULL", me);
+  for (int t = 0; t < nparts; ++t)
+    for (size_t i = 0; i < parts[t].len * B; ++i)
+      if (!std::isfinite(parts[t].src[i]))
+        return fail(ctx, MIMO_E_INVALID, "%s: %s of problem %d holds a NaN or an infinity", me, parts[t].name, (int)(i / parts[t].len));
+  ctx->svi_state_valid = false;
+  std::vector<double> block(B * per, 0.0);
+  for (int t = 0; t < nparts; ++t)
+    for (size_t p = 0; p < B; ++p)
+      memcpy(&block[p * per + parts[t].at], parts[t].src + p * parts[t].len, parts[t].len * sizeof(double));
+  std::vector<int32_t> words((size_t)kViWords * B, 0);
+  std::fill(words.begin() + (size_t)kViActive * B, words.begin() + (size_t)(kViActive + 1) * B, 1);
+  const size_t nwork = (family == 1 ? 2 : 1) * B * K + 2 * B;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_post, block.data(), block.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_post + B * per, 0, B * per * sizeof(double), ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_loop, words.data(), words.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_work, 0, nwork * sizeof(double), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_theta, 0, image_len(ctx, K) * sizeof(double), ctx->stream));
+  if (family == 1) {
+    ViIlrArgs ia = vi_ilr_args(ctx, K);
+    ia.loop.mode = kViInit;
+    HIP_TRY(ctx, launch_vi_ilr_update(ia, ctx->stream));
+    HIP_TRY(ctx, launch_vi_ilr_gating(ia, ctx->stream));
+  } else {
+    ViArgs va = vi_args(ctx, K);
+    va.mode = kViInit;
+    HIP_TRY(ctx, launch_vi_update(va, ctx->stream));
+    HIP_TRY(ctx, launch_vi_gating(va, ctx->stream));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(words.data(), ctx->vi_loop, words.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the sources are pageable host memory)
+  memcpy(status, words.data() + (size_t)kViStatus * B, B * sizeof(int32_t));
+  ctx->svi_state_valid = true;
+  ctx->svi_t = 0;
+  return MIMO_OK;
+}
+
+// The loop of both families (as vi_run is): per iteration the selection pass and its reduction (the statistics of the
+// minibatch), the blend update and the blend gating, a plain pass over all rows without statistics, its scalar reduction, and the
+// finish with tol = 0.  sel_off is the same for every iteration: one work table per call.
+static int svi_run(mimo_ctx* ctx, int K, int iters, double step_size, const double* scale, const int64_t* rows,
+                   const int64_t* sel_off, const uint64_t* seeds, int flags, double* trace, int32_t* n_done, int32_t* status,
+                   const char* me, int family) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, me))) return rc;
+  if (flags & ~MIMO_F_SVI_RESIDENT_START)
+    return fail(ctx, MIMO_E_INVALID, "%s: flags 0x%x: only MIMO_F_SVI_RESIDENT_START", me, flags);
+  if (iters < 1 || iters > 65536) return fail(ctx, MIMO_E_INVALID, "%s: iters = %d outside [1, 65536]", me, iters);
+  if (!(step_size > 0.0 && step_size <= 1.0)) return fail(ctx, MIMO_E_INVALID, "%s: step_size = %g outside (0, 1]", me, step_size);
+  if (!scale || !sel_off || !trace || !n_done || !status)
+    return fail(ctx, MIMO_E_INVALID, "%s: scale, sel_off, trace, n_done and status must be non-NULL", me);
+  const int B = ctx->batch_B, G = ctx->batch_G;
+  for (int p = 0; p < B; ++p)
+    if (!(std::isfinite(scale[p]) && scale[p] > 0.0))      // (above 1: a minibatch drawn with replacement, larger than its data set)
+      return fail(ctx, MIMO_E_INVALID, "%s: scale[%d] = %g must be finite and > 0", me, p, scale[p]);
+  if ((rc = vi_ready(ctx, K, me, family))) return rc;
+  if (!ctx->svi_state_valid)
+    return fail(ctx, MIMO_E_STATE, "%s: no starting posterior is resident (call %s after the prior block; an upload and a new prior "
+                "block drop it)", me, family == 1 ? "mimo_svi_ilr_state_batched" : "mimo_svi_state_batched");
+  if ((rc = check_offsets(ctx, sel_off, B, me, "sel_off"))) return rc;
+  const bool resident_start = (flags & MIMO_F_SVI_RESIDENT_START) != 0;
+  if (resident_start && (!ctx->batch_stats_valid || ctx->batch_stats_K != K || !ctx->S_d))
+    return fail(ctx, MIMO_E_STATE, "%s: MIMO_F_SVI_RESIDENT_START and no statistics of K = %d are resident (run a batched pass that "
+                "returns statistics first)", me, K);
+  const int n_sel = iters - (resident_start ? 1 : 0), first = resident_start ? 1 : 0;
+  const int64_t per_it = sel_off[B];
+  if (n_sel > 0 && per_it > 0 && !rows && !seeds)
+    return fail(ctx, MIMO_E_INVALID, "%s: rows and seeds are both NULL (give the indices or one Philox seed per problem)", me);
+  // the selection pass gathers through the indices unchecked: every one of every iteration is checked here, before anything is
+  // enqueued; the index kernel's own stay below N_b by construction, given a row to draw
+  for (int p = 0; p < B; ++p) {
+    const int64_t nb = ctx->batch_rows[(size_t)p + 1] - ctx->batch_rows[(size_t)p];
+    if (!rows) {
+      if (n_sel > 0 && sel_off[p + 1] > sel_off[p] && nb < 1)
+        return fail(ctx, MIMO_E_INVALID, "%s: problem %d has no rows to draw its %lld indices from", me, p,
+                    (long long)(sel_off[p + 1] - sel_off[p]));
+      continue;
+    }
+    for (int s = 0; s < n_sel; ++s)
+      for (int64_t i = sel_off[p]; i < sel_off[p + 1]; ++i) {
+        const int64_t r = rows[(int64_t)s * per_it + i];
+        if (r < 0 || r >= nb)
+          return fail(ctx, MIMO_E_INVALID, "%s: iteration %d, problem %d: index %lld (entry %lld of its selection) outside [0, %lld)",
+                      me, s + first, p, (long long)r, (long long)(i - sel_off[p]), (long long)nb);
+      }
+  }
+  std::vector<BatchedWork> work;
+  std::vector<int32_t> wg_off;
+  if ((rc = build_work(ctx, sel_off, B, me, &work, &wg_off))) return rc;
+  // the small tables: [sel_off (B + 1) | work table | wg_off (int32, B + 1, in whole words) | seeds B | 1 / scale B]
+  const size_t Gs = work.size(), at_work = (size_t)B + 1, at_wg = at_work + 2 * Gs, nwg = ((size_t)B + 2) / 2;
+  const size_t at_seeds = at_wg + nwg, at_inv = at_seeds + (size_t)B;
+  std::vector<uint64_t> tables(at_inv + (size_t)B, 0);
+  memcpy(tables.data(), sel_off, ((size_t)B + 1) * sizeof(int64_t));
+  if (Gs) memcpy(tables.data() + at_work, work.data(), Gs * sizeof(BatchedWork));
+  memcpy(tables.data() + at_wg, wg_off.data(), nwg * sizeof(uint64_t));
+  if (seeds) memcpy(tables.data() + at_seeds, seeds, (size_t)B * sizeof(uint64_t));
+  for (int p = 0; p < B; ++p) {
+    const double inv = 1.0 / scale[p];      // (as `1. / scale` of the host step rounds it)
+    memcpy(tables.data() + at_inv + p, &inv, sizeof(double));
+  }
+  size_t total = 0;
+  if ((rc = vi_loop_room(ctx, iters, &total))) return rc;
+  if ((rc = ensure_partials(ctx, K, std::max(Gs, (size_t)G)))) return rc;
+  if (!resident_start && (rc = ensure_block(ctx, batch_stats_len(ctx, K) + 3 * (size_t)B))) return rc;
+  if ((rc = ctx->svi_tables.ensure(ctx, tables.size()))) return rc;
+  if ((rc = ctx->svi_sel.ensure(ctx, (size_t)std::max(n_sel, 0) * (size_t)per_it))) return rc;
+  leaves(ctx, kPassTables, 0);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->svi_tables, tables.data(), tables.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  const uint64_t* const tables_d = ctx->svi_tables;
+  const int64_t* const sel_off_d = reinterpret_cast<const int64_t*>(tables_d);
+  const int32_t* const wg_off_d = reinterpret_cast<const int32_t*>(tables_d + at_wg);
+  if (n_sel > 0 && per_it > 0) {
+    if (rows) {
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->svi_sel, rows, (size_t)n_sel * (size_t)per_it * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    } else {
+      for (int s = 0; s < n_sel; s += 65535)      // (a grid's second dimension)
+        HIP_TRY(ctx, launch_svi_indices(ctx->svi_sel + (size_t)s * (size_t)per_it, sel_off_d, ctx->batch_row_off_d, tables_d + at_seeds,
+                                        B, std::min(n_sel - s, 65535), per_it, ctx->svi_t + (uint64_t)(first + s), ctx->stream));
+    }
+  }
+
+  ViIlrArgs ia{};
+  if (family == 1) ia = vi_ilr_args(ctx, K);
+  ViArgs& va = ia.loop;
+  if (family != 1) va = vi_args(ctx, K);
+  va.tol = 0.0;                               // SVI has no stopping rule
+  va.mode = kViBlend;
+  va.rho = step_size;
+  va.one_minus_rho = 1.0 - step_size;
+  va.inv_scale = reinterpret_cast<const double*>(tables_d + at_inv);
+  BatchedArgs sel_a = batched_args(ctx, K), full_a = batched_args(ctx, K);
+  sel_a.theta = full_a.theta = ctx->vi_theta;
+  sel_a.sel_off = sel_off_d;
+  sel_a.work = reinterpret_cast<const BatchedWork*>(tables_d + at_work);
+  full_a.do_stats = 0;
+  double* const scalars_d = ctx->S_d + batch_stats_len(ctx, K);
+  HIP_TRY(ctx, hipMemsetAsync(va.words + (size_t)kViDone * B, 0, (size_t)B * sizeof(int32_t), ctx->stream));
+  for (int it = 0; it < iters; ++it) {
+    if (it >= first) {
+      sel_a.sel = ctx->svi_sel + (size_t)(it - first) * (size_t)per_it;
+      if (Gs) HIP_TRY(ctx, launch_batched_rows(sel_a, (int)Gs, ctx->stream));      // (no slots at all: the reduction leaves zeros)
+      if ((rc = batched_reduce(ctx, K, wg_off_d, 0, true))) return rc;
+    }
+    if (family == 1) {
+      HIP_TRY(ctx, launch_vi_ilr_update(ia, ctx->stream));
+      HIP_TRY(ctx, launch_vi_ilr_gating(ia, ctx->stream));
+    } else {
+      HIP_TRY(ctx, launch_vi_update(va, ctx->stream));
+      HIP_TRY(ctx, launch_vi_gating(va, ctx->stream));
+    }
+    // the bound's pass: all rows, no statistics — the minibatch's stay resident, the scalars go behind them as always
+    HIP_TRY(ctx, launch_batched(full_a, G, ctx->stream));
+    HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, ctx->D, ctx->F, ctx->F16, 0, nullptr,
+                                       scalars_d, ctx->stream));
+    HIP_TRY(ctx, launch_vi_finish(va, it, ctx->stream));
+  }
+  ctx->svi_t += (uint64_t)iters;
+  return vi_loop_out(ctx, iters, total, trace, n_done, status);      // (tables and rows are host memory: alive up to this wait)
+  });
+}
+
+extern "C" {
+
+int mimo_svi_state_batched(mimo_ctx* ctx, int K, const double* alpha, const double* qa, const double* qb, const double* qc,
+                           const double* qd, int32_t* status) {
+  return guarded(ctx, [&]() -> int {
+  const char* const me = "mimo_svi_state_batched";
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, me))) return rc;
+  if ((rc = vi_ready(ctx, K, me, 0))) return rc;
+  const ViLayout L{K, ctx->D};
+  const size_t k = (size_t)K, D = (size_t)ctx->D;
+  const SviPart parts[5] = {{"alpha", alpha, k, (size_t)L.alpha()}, {"qa", qa, k * D, (size_t)L.qa()}, {"qb", qb, k, (size_t)L.qb()},
+                            {"qc", qc, k * D * D, (size_t)L.qc()}, {"qd", qd, k, (size_t)L.qd()}};
+  return svi_state(ctx, K, parts, 5, (size_t)L.count(), status, me, 0);
+  });
+}
+
+int mimo_svi_ilr_state_batched(mimo_ctx* ctx, int K, const double* g0, const double* g1, const double* qa, const double* qb,
+                               const double* qc, const double* qd, const double* ma, const double* mKq, const double* mc,
+                               const double* md, int32_t* status) {
+  return guarded(ctx, [&]() -> int {
+  const char* const me = "mimo_svi_ilr_state_batched";
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, me))) return rc;
+  if ((rc = vi_ready(ctx, K, me, 1))) return rc;
+  const ViIlrLayout L{K, ctx->vi_dx, ctx->vi_dy};
+  const size_t k = (size_t)K, dx = (size_t)ctx->vi_dx, dy = (size_t)ctx->vi_dy, dc = dx + 1;
+  const bool stick = ctx->vi_gating == kViGatingStick;
+  const std::vector<double> zeros(stick ? 0 : (size_t)ctx->batch_B * k, 0.0);      // (a Dirichlet gating has no second part)
+  const SviPart parts[10] = {{"g0", g0, k, (size_t)L.g0()}, {"g1", stick ? g1 : zeros.data(), k, (size_t)L.g1()},
+                             {"qa", qa, k * dx, (size_t)L.b_qa()}, {"qb", qb, k, (size_t)L.b_qb()},
+                             {"qc", qc, k * dx * dx, (size_t)L.b_qc()}, {"qd", qd, k, (size_t)L.b_qd()},
+                             {"ma", ma, k * dy * dc, (size_t)L.m_a()}, {"mKq", mKq, k * dc * dc, (size_t)L.m_Kq()},
+                             {"mc", mc, k * dy * dy, (size_t)L.m_c()}, {"md", md, k, (size_t)L.m_d()}};
+  return svi_state(ctx, K, parts, 10, (size_t)L.count(), status, me, 1);
+  });
+}
+
+int mimo_svi_run_batched(mimo_ctx* ctx, int K, int iters, double step_size, const double* scale, const int64_t* rows,
+                         const int64_t* sel_off, const uint64_t* seeds, int flags, double* trace, int32_t* n_done, int32_t* status) {
+  return svi_run(ctx, K, iters, step_size, scale, rows, sel_off, seeds, flags, trace, n_done, status, "mimo_svi_run_batched", 0);
+}
+
+int mimo_svi_ilr_run_batched(mimo_ctx* ctx, int K, int iters, double step_size, const double* scale, const int64_t* rows,
+                             const int64_t* sel_off, const uint64_t* seeds, int flags, double* trace, int32_t* n_done,
+                             int32_t* status) {
+  return svi_run(ctx, K, iters, step_size, scale, rows, sel_off, seeds, flags, trace, n_done, status, "mimo_svi_ilr_run_batched", 1);
+}
+
+}  // extern "C"
+
+extern "C" {
 
 // ------------------------------------------------------------------------------------------
 // Batched prediction (mimo_predict_batched.hip)

@@ -183,6 +183,12 @@ struct mimo_ctx {
   Buf<double> vi_theta;                                    // [B][K16][F16 / 4][64]: the operand images the loop's passes read
   Buf<double> vi_loop;                                     // [words: kViWords B int32, padded to doubles | trace of the last call]
   Buf<double, true> vi_loop_h;                             // its pinned sibling
+  // device-resident batched SVI (mimo_svi_state_batched / mimo_svi_run_batched) on the loop above: the state lives from its upload
+  // to the next prior block or upload
+  bool svi_state_valid = false;
+  uint64_t svi_t = 0;                                      // iterations since the state upload: the index kernel's Philox counter
+  Buf<int64_t> svi_sel;                                    // [selections of a call][sel_off[B]]: the minibatch indices
+  Buf<uint64_t> svi_tables;                                // [sel_off B + 1 | work table | wg_off | seeds B | 1 / scale B] of a call
 
   void* comm = nullptr;         // RCCL communicator (mimo_comm_init): every pass then returns statistics summed over the ranks
   int comm_world = 1;

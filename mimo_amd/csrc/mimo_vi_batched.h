@@ -40,6 +40,16 @@ enum ViWord : int { kViActive = 0, kViStatus = 1, kViTotal = 2, kViDone = 3, kVi
 constexpr int kViNotPosDef = 1;      // a component's posterior block C = c - kappa m m' is not positive definite
 constexpr int kViNotFinite = 2;      // a canonical form (c, b, W), a term of the bound or the bound itself is not finite
 
+// How the update and the gating kernel form the posterior's natural parameters (wave-uniform, ViArgs::mode):
+//   conjugate  eta = eta_prior + S                                            (coordinate descent: mimo_vi_run_batched)
+//   blend      eta = (1 - rho) eta_cur + rho (eta_prior + inv_scale_b S)      (the SVI step: mimo_svi_run_batched), eta_cur the
+//              natural parameters of the problem's current slot; the products are not contracted into the sums, in the order of
+//              _ConjugateBlock._apply_sgd: t = inv S, u = eta_prior + t, v = rho u, w = (1 - rho) eta_cur, w + v
+//   init       eta = eta_cur: no statistics are read (mimo_svi_state_batched: the derived parts, the image and the prior terms of
+//              an uploaded posterior)
+// Everything behind eta is the same code in all three, and the block goes to the slot that is not current.
+enum ViMode : int { kViConjugate = 0, kViBlend = 1, kViInit = 2 };
+
 struct ViArgs {
   const double* S;            // [B][K][1 + D + D^2]: the resident statistics block (launch_batched_reduce)
   const double* scalars;      // [B][3]: the scalars of the same reduction
@@ -61,7 +71,41 @@ struct ViArgs {
   double* trace;              // [iters][B] of this call
   int B, K, D, K16, NS;
   double tol;
+  // the SVI step (mode != kViConjugate); the zeros of ViArgs{} are the conjugate update
+  int mode;                   // ViMode
+  double rho, one_minus_rho;  // the step size and 1 - rho as the host rounds it
+  const double* inv_scale;    // [B]: 1 / scale_b as the host rounds it, scale_b = batch size / N_b (blend only)
 };
+
+#ifdef __HIPCC__
+// One entry of the posterior's natural parameters in mode M (ViMode): prior + s as the conjugate update always
+// formed it; the current entry; or the SVI blend in the operation order of _ConjugateBlock._apply_sgd and the gatings'
+// meanfield_sgd (distributions/bayesian.py), with contraction off so that no product is fused into the add behind it
+template <int M>
+__device__ __forceinline__ double vi_eta(double prior, double s, double cur, double rho, double omr, double inv) {
+  if constexpr (M == kViConjugate) {
+    return prior + s;
+  } else if constexpr (M == kViInit) {
+    return cur;
+  } else {
+#pragma clang fp contract(off)
+    const double t = inv * s;
+    const double u = prior + t;
+    const double v = rho * u;
+    const double w = omr * cur;
+    return w + v;
+  }
+}
+// what vi_eta reads beside the prior: entry i of the current block (not in the conjugate mode), of the statistics (not in the init mode)
+template <int M>
+__device__ __forceinline__ double vi_cur(const double* C, size_t i) {
+  if constexpr (M == kViConjugate) return 0.0; else return C[i];
+}
+template <int M>
+__device__ __forceinline__ double vi_stat(const double* S, size_t i) {
+  if constexpr (M == kViInit) return 0.0; else return S[i];
+}
+#endif
 
 // update: one wave per (problem, component); gating: one wave per problem.  Both return at once for a problem that is not active
 // or whose status word is set.
@@ -70,5 +114,12 @@ hipError_t launch_vi_gating(const ViArgs& a, hipStream_t stream);
 // finish (behind the pass and its reduction), iteration `it` of this call: trace[it][b] = prior_terms[b] + scalars[b][0] for an
 // active problem (NaN otherwise), and active[b] = 0 once two consecutive bounds are closer than tol.
 hipError_t launch_vi_finish(const ViArgs& a, int it, hipStream_t stream);
+
+// The minibatch indices of `n_it` SVI iterations, one lane per (iteration, problem, slot): for iteration i < n_it, problem b and
+// slot j < sel_off[b + 1] - sel_off[b],
+//   sel[i sel_off[B] + sel_off[b] + j] = min((int64)(philox_uniform(seeds[b], j, t0 + i) N_b), N_b - 1),  N_b = row_off[b + 1] - row_off[b]
+// (a draw with replacement; a problem without rows gets no slots: the caller checks).  All pointers are device pointers.
+hipError_t launch_svi_indices(int64_t* sel, const int64_t* sel_off, const int64_t* row_off, const uint64_t* seeds, int B, int n_it,
+                              int64_t per_it, uint64_t t0, hipStream_t stream);
 
 }  // namespace mimo

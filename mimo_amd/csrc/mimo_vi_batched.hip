@@ -10,6 +10,10 @@
 //   (launch_batched, launch_batched_reduce: the pass and its reduction, mimo_batched.hip)
 //   vi_finish_kernel   one lane per problem: the bound into the trace, the stopping rule
 //
+// The update and the gating kernel are templates over the mode (ViMode): the conjugate update above, the SVI blend of the current
+// slot's natural parameters with it, or the derived parts of an uploaded posterior; svi_indices_kernel draws the minibatch indices
+// of the SVI loop (mimo_svi_run_batched).
+//
 // All float64, plain launches, no atomics.  Every sum runs in a fixed order that depends on (K, Dz) alone and every workgroup
 // works on one problem, so a problem's numbers do not depend on what else is in the batch, bit for bit (the batch's determinism
 // rule, mimo_batched.hip).  A problem that has stopped is skipped by the update and the gating kernel: its posterior block and
@@ -64,6 +68,7 @@ __device__ __forceinline__ size_t vi_theta_at(int NS, int k, int f) {
   return ((size_t)(k >> 4) * NS + (f >> 2)) * 64 + (f & 3) * 16 + (k & 15);
 }
 
+template <int M>
 __global__ __launch_bounds__(64) void vi_update_kernel(const ViArgs a) {
   __shared__ double Qc[16 * kViLd];     // c of the posterior's natural parameters
   __shared__ double U[16 * kViLd];      // C = c - kappa m m' -> its upper Cholesky factor
@@ -83,21 +88,26 @@ __global__ __launch_bounds__(64) void vi_update_kernel(const ViArgs a) {
   const int B = a.B, K = a.K, D = a.D, DD = D * D;
   const int prob = blockIdx.x / K, k = blockIdx.x - prob * K;
   if (!a.words[kViActive * B + prob] || a.words[kViStatus * B + prob]) return;
-  const int slot = 1 - a.words[kViSlot * B + prob];
+  const int cur = a.words[kViSlot * B + prob], slot = 1 - cur;
   const ViLayout L{K, D};
   double* const P = a.post + ((size_t)slot * B + prob) * L.count();
+  const double* const C = a.post + ((size_t)cur * B + prob) * L.count();      // the current block (read in the blend and init modes)
   const size_t bk = (size_t)prob * K + k;
   const double* const Sk = a.S + bk * (size_t)(1 + D + DD);
   const double* const pck = a.pc + bk * DD;
+  const double rho = a.rho, omr = a.one_minus_rho;
+  double inv = 0.0;
+  if constexpr (M == kViBlend) inv = a.inv_scale[prob];
 
-  // eta_post = eta_prior + statistics
-  const double n = Sk[0];
+  // eta_post = eta_prior + statistics (conjugate), or the mode's form of it (vi_eta)
+  const double n = vi_stat<M>(Sk, 0);
   const double pb = a.pb[bk], pd = a.pd[bk];
-  const double qb = pb + n, qd = pd + n;
+  const double qb = vi_eta<M>(pb, n, vi_cur<M>(C, L.qb() + k), rho, omr, inv);
+  const double qd = vi_eta<M>(pd, n, vi_cur<M>(C, L.qd() + k), rho, omr, inv);
   const int ej = lane & 15, ei0 = lane >> 4;        // element (ei0 + 4 r, ej) of a Dz x Dz block, r = 0 .. 3
   if (lane < D) {
     const double p = a.pa[bk * D + lane];
-    const double q = p + Sk[1 + lane];
+    const double q = vi_eta<M>(p, vi_stat<M>(Sk, 1 + lane), vi_cur<M>(C, L.qa() + k * D + lane), rho, omr, inv);
     pav[lane] = p;
     qav[lane] = q;
     mv[lane] = q / qb;
@@ -105,7 +115,9 @@ __global__ __launch_bounds__(64) void vi_update_kernel(const ViArgs a) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int i = ei0 + 4 * r;
-    if (i < D && ej < D) Qc[i * kViLd + ej] = pck[i * D + ej] + Sk[1 + D + i * D + ej];
+    if (i < D && ej < D)
+      Qc[i * kViLd + ej] = vi_eta<M>(pck[i * D + ej], vi_stat<M>(Sk, 1 + D + i * D + ej), vi_cur<M>(C, L.qc() + k * DD + i * D + ej),
+                                     rho, omr, inv);
   }
   wg_sync();
 #pragma unroll
@@ -252,6 +264,7 @@ __global__ __launch_bounds__(64) void vi_update_kernel(const ViArgs a) {
   }
 }
 
+template <int M>
 __global__ __launch_bounds__(64) void vi_gating_kernel(const ViArgs a) {
   // alpha, alpha0, lgamma(alpha), lgamma(alpha0), (alpha - 1) E, (alpha0 - 1) E, terms, E[log pi], c_total
   __shared__ double t[9][kBatchedMaxK];
@@ -260,16 +273,21 @@ __global__ __launch_bounds__(64) void vi_gating_kernel(const ViArgs a) {
   const int B = a.B, K = a.K, D = a.D;
   const int prob = blockIdx.x;
   if (!a.words[kViActive * B + prob] || a.words[kViStatus * B + prob]) return;
-  const int slot = 1 - a.words[kViSlot * B + prob];
+  const int cur = a.words[kViSlot * B + prob], slot = 1 - cur;
   const ViLayout L{K, D};
   double* const P = a.post + ((size_t)slot * B + prob) * L.count();
+  const double* const C = a.post + ((size_t)cur * B + prob) * L.count();      // the current block (read in the blend and init modes)
   const size_t sstride = (size_t)(1 + D + D * D);
+  double inv = 0.0;
+  if constexpr (M == kViBlend) inv = a.inv_scale[prob];
 
-  // Dirichlet gating: alpha = ((alpha0 - 1) + n) + 1
+  // Dirichlet gating: alpha = ((alpha0 - 1) + n) + 1; the blend runs on the natural parameter alpha - 1 (gating.py: std_to_nat /
+  // nat_to_std around CategoricalWithDirichlet.meanfield_sgd); init keeps the uploaded alpha itself
   for (int k = lane; k < K; k += 64) {
     const size_t bk = (size_t)prob * K + k;
     const double a0 = a.alpha0[bk];
-    t[0][k] = ((a0 - 1.0) + a.S[bk * sstride]) + 1.0;
+    if constexpr (M == kViInit) t[0][k] = C[L.alpha() + k];
+    else t[0][k] = vi_eta<M>(a0 - 1.0, a.S[bk * sstride], vi_cur<M>(C, L.alpha() + k) - 1.0, a.rho, a.one_minus_rho, inv) + 1.0;
     t[1][k] = a0;
   }
   wg_sync();
@@ -345,29 +363,67 @@ __global__ __launch_bounds__(256) void vi_finish_kernel(const ViArgs a, int it) 
   a.trace[(size_t)it * B + b] = v;
 }
 
+// one lane per (iteration, problem, slot): the grid's x runs over the slots of one iteration, y over the iterations
+__global__ __launch_bounds__(256) void svi_indices_kernel(int64_t* sel, const int64_t* sel_off, const int64_t* row_off,
+                                                          const uint64_t* seeds, int B, int64_t per_it, uint64_t t0) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= per_it) return;
+  int lo = 0, hi = B - 1;                      // the problem whose slots hold e: the last b with sel_off[b] <= e
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (sel_off[mid] <= e) lo = mid; else hi = mid - 1;
+  }
+  const int64_t nb = row_off[lo + 1] - row_off[lo];
+  if (nb < 1) return;                          // (refused by the caller)
+  const int64_t j = e - sel_off[lo];
+  const double u = philox_uniform(seeds[lo], (uint64_t)j, t0 + blockIdx.y);
+  int64_t idx = (int64_t)(u * (double)nb);
+  if (idx > nb - 1) idx = nb - 1;
+  sel[(int64_t)blockIdx.y * per_it + e] = idx;
+}
+
+// (the init mode reads no statistics; the blend reads one factor per problem)
 bool vi_args_ok(const ViArgs& a) {
-  return a.B >= 1 && a.K >= 1 && a.K <= kBatchedMaxK && a.D >= 1 && a.D <= 16 && a.K16 == (a.K + 15) / 16 && a.NS >= 1 && a.S &&
-         a.scalars && a.alpha0 && a.pa && a.pb && a.pc && a.pd && a.plz && a.post && a.term && a.prior_terms && a.last && a.words &&
-         a.theta && a.trace;
+  if (a.mode != kViConjugate && a.mode != kViBlend && a.mode != kViInit) return false;
+  if (a.mode == kViBlend && !a.inv_scale) return false;
+  return a.B >= 1 && a.K >= 1 && a.K <= kBatchedMaxK && a.D >= 1 && a.D <= 16 && a.K16 == (a.K + 15) / 16 && a.NS >= 1 &&
+         (a.S || a.mode == kViInit) && (a.scalars || a.mode == kViInit) && a.alpha0 && a.pa && a.pb && a.pc && a.pd && a.plz &&
+         a.post && a.term && a.prior_terms && a.last && a.words && a.theta && a.trace;
 }
 
 }  // namespace
 
 hipError_t launch_vi_update(const ViArgs& a, hipStream_t stream) {
   if (!vi_args_ok(a) || (int64_t)a.B * a.K > (int64_t)INT32_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(vi_update_kernel, dim3((unsigned)(a.B * a.K)), dim3(64), 0, stream, a);
+  const dim3 grid((unsigned)(a.B * a.K));
+  if (a.mode == kViBlend) hipLaunchKernelGGL(vi_update_kernel<kViBlend>, grid, dim3(64), 0, stream, a);
+  else if (a.mode == kViInit) hipLaunchKernelGGL(vi_update_kernel<kViInit>, grid, dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL(vi_update_kernel<kViConjugate>, grid, dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 
 hipError_t launch_vi_gating(const ViArgs& a, hipStream_t stream) {
   if (!vi_args_ok(a)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(vi_gating_kernel, dim3((unsigned)a.B), dim3(64), 0, stream, a);
+  const dim3 grid((unsigned)a.B);
+  if (a.mode == kViBlend) hipLaunchKernelGGL(vi_gating_kernel<kViBlend>, grid, dim3(64), 0, stream, a);
+  else if (a.mode == kViInit) hipLaunchKernelGGL(vi_gating_kernel<kViInit>, grid, dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL(vi_gating_kernel<kViConjugate>, grid, dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 
 hipError_t launch_vi_finish(const ViArgs& a, int it, hipStream_t stream) {
   if (!vi_args_ok(a) || it < 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(vi_finish_kernel, dim3((unsigned)((a.B + 255) / 256)), dim3(256), 0, stream, a, it);
+  return hipGetLastError();
+}
+
+hipError_t launch_svi_indices(int64_t* sel, const int64_t* sel_off, const int64_t* row_off, const uint64_t* seeds, int B, int n_it,
+                              int64_t per_it, uint64_t t0, hipStream_t stream) {
+  if (!sel || !sel_off || !row_off || !seeds || B < 1 || n_it < 0 || n_it > 65535 || per_it < 0 ||
+      (per_it + 255) / 256 > (int64_t)INT32_MAX) return hipErrorInvalidValue;
+  if (n_it == 0 || per_it == 0) return hipSuccess;
+  hipLaunchKernelGGL(svi_indices_kernel, dim3((unsigned)((per_it + 255) / 256), (unsigned)n_it), dim3(256), 0, stream, sel, sel_off,
+                     row_off, seeds, B, per_it, t0);
   return hipGetLastError();
 }
 

@@ -10,6 +10,9 @@
 //   vi_ilr_gating_kernel   one wave per problem: the Dirichlet or stick-breaking update, E[log pi], c_total into the image, the
 //                          gating's term of the bound and the sums of the blocks' terms
 //
+// Both kernels are templates over the mode (ViMode, mimo_vi_batched.h): the conjugate update, the SVI blend of the current slot's
+// natural parameters with it, or the derived parts of an uploaded posterior.
+//
 // All float64, plain launches, no atomics but the status word's.  Every sum runs in a fixed order that depends on (K, dx, dy)
 // alone and every workgroup works on one problem, so a problem's numbers do not depend on what else is in the batch, bit for bit.
 // Stopped and failed problems: as in mimo_vi_batched.hip (skipped; the posterior blocks are double-buffered).
@@ -105,6 +108,7 @@ __device__ __forceinline__ double ilr_xxt(const double* X, int n, int i, int j) 
   return v;
 }
 
+template <int M>
 __global__ __launch_bounds__(64) void vi_ilr_update_kernel(const ViIlrArgs a) {
   __shared__ double Bq[kBlk];       // basis: c of the posterior's natural parameters
   __shared__ double Bp[kBlk];       // basis: psi
@@ -144,9 +148,13 @@ __global__ __launch_bounds__(64) void vi_ilr_update_kernel(const ViIlrArgs a) {
   const int prob = blockIdx.x / K, k = blockIdx.x - prob * K;
   int32_t* const words = a.loop.words;
   if (!words[kViActive * B + prob] || words[kViStatus * B + prob]) return;
-  const int slot = 1 - words[kViSlot * B + prob];
+  const int cur = words[kViSlot * B + prob], slot = 1 - cur;
   const ViIlrLayout L{K, dx, dy};
   double* const P = a.loop.post + ((size_t)slot * B + prob) * L.count();
+  const double* const C = a.loop.post + ((size_t)cur * B + prob) * L.count();      // the current block (blend and init modes)
+  const double rho = a.loop.rho, omr = a.loop.one_minus_rho;
+  double inv = 0.0;
+  if constexpr (M == kViBlend) inv = a.loop.inv_scale[prob];
   const size_t bk = (size_t)prob * K + k;
   const double* const Sk = a.loop.S + bk * (size_t)(1 + D + DD);
   const double* const sx = Sk + 1;            // sum r z
@@ -154,13 +162,15 @@ __global__ __launch_bounds__(64) void vi_ilr_update_kernel(const ViIlrArgs a) {
   const int ej = lane & 15, ei0 = lane >> 4;  // element (ei0 + 4 r, ej) of a block, r = 0 .. 3
 
   // ---- basis: the Normal-Wishart update on (sum r x, n, sum r x x', n) ---------------------------------------------------------
-  const double n = Sk[0];
+  // (every eta below: prior + statistics in the conjugate mode, the mode's form of it otherwise — vi_eta, mimo_vi_batched.h)
+  const double n = vi_stat<M>(Sk, 0);
   const double* const pck = a.pc + bk * dx * dx;
   const double pb = a.pb[bk], pd = a.pd[bk];
-  const double qb = pb + n, qd = pd + n;
+  const double qb = vi_eta<M>(pb, n, vi_cur<M>(C, L.b_qb() + k), rho, omr, inv);
+  const double qd = vi_eta<M>(pd, n, vi_cur<M>(C, L.b_qd() + k), rho, omr, inv);
   if (lane < dx) {
     const double p = a.pa[bk * dx + lane];
-    const double q = p + sx[lane];
+    const double q = vi_eta<M>(p, vi_stat<M>(sx, lane), vi_cur<M>(C, L.b_qa() + k * dx + lane), rho, omr, inv);
     pav[lane] = p;
     qav[lane] = q;
     mv[lane] = q / qb;
@@ -168,7 +178,9 @@ __global__ __launch_bounds__(64) void vi_ilr_update_kernel(const ViIlrArgs a) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int i = ei0 + 4 * r;
-    if (i < dx && ej < dx) Bq[i * kLd + ej] = pck[i * dx + ej] + sxx[i * D + ej];
+    if (i < dx && ej < dx)
+      Bq[i * kLd + ej] = vi_eta<M>(pck[i * dx + ej], vi_stat<M>(sxx, i * D + ej), vi_cur<M>(C, L.b_qc() + (k * dx + i) * dx + ej), rho,
+                                   omr, inv);
   }
   wg_sync();
 #pragma unroll
@@ -238,19 +250,22 @@ __global__ __launch_bounds__(64) void vi_ilr_update_kernel(const ViIlrArgs a) {
   const double* const mbk = a.mb + bk * dc * dc;
   const double* const mck = a.mc + bk * dy * dy;
   const double md = a.md[bk];
-  const double qdm = md + n;
+  const double qdm = vi_eta<M>(md, n, vi_cur<M>(C, L.m_d() + k), rho, omr, inv);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int i = ei0 + 4 * r;
     if (i < dy && ej < dc)        // the last column of y x~' is sum r y
-      Am[i * kLd + ej] = mak[i * dc + ej] + (ej < dx ? sxx[(dx + i) * D + ej] : sx[dx + i]);
+      Am[i * kLd + ej] = vi_eta<M>(mak[i * dc + ej], ej < dx ? vi_stat<M>(sxx, (dx + i) * D + ej) : vi_stat<M>(sx, dx + i),
+                                   vi_cur<M>(C, L.m_a() + (k * dy + i) * dc + ej), rho, omr, inv);
     if (i < dc && ej < dc) {      // the border of x~ x~' is sum r x and n
-      const double s = i < dx ? (ej < dx ? sxx[i * D + ej] : sx[i]) : (ej < dx ? sx[ej] : n);
-      const double v = mbk[i * dc + ej] + s;
+      const double s = i < dx ? (ej < dx ? vi_stat<M>(sxx, i * D + ej) : vi_stat<M>(sx, i)) : (ej < dx ? vi_stat<M>(sx, ej) : n);
+      const double v = vi_eta<M>(mbk[i * dc + ej], s, vi_cur<M>(C, L.m_Kq() + (k * dc + i) * dc + ej), rho, omr, inv);
       Kq[i * kLd + ej] = v;
       U[i * kLd + ej] = v;
     }
-    if (i < dy && ej < dy) Cq[i * kLd + ej] = mck[i * dy + ej] + sxx[(dx + i) * D + dx + ej];
+    if (i < dy && ej < dy)
+      Cq[i * kLd + ej] = vi_eta<M>(mck[i * dy + ej], vi_stat<M>(sxx, (dx + i) * D + dx + ej),
+                                   vi_cur<M>(C, L.m_c() + (k * dy + i) * dy + ej), rho, omr, inv);
   }
   wg_sync();
   double slK;
@@ -465,6 +480,7 @@ __global__ __launch_bounds__(64) void vi_ilr_update_kernel(const ViIlrArgs a) {
   }
 }
 
+template <int M>
 __global__ __launch_bounds__(64) void vi_ilr_gating_kernel(const ViIlrArgs a) {
   // g0, g1 of the posterior, of the prior; E[log stick | pi], E[log rest]; E[log pi]; c_total; six summands of the gating's term;
   // the basis terms, the experts' terms
@@ -475,13 +491,17 @@ __global__ __launch_bounds__(64) void vi_ilr_gating_kernel(const ViIlrArgs a) {
   const int prob = blockIdx.x;
   int32_t* const words = a.loop.words;
   if (!words[kViActive * B + prob] || words[kViStatus * B + prob]) return;
-  const int slot = 1 - words[kViSlot * B + prob];
+  const int cur = words[kViSlot * B + prob], slot = 1 - cur;
   const ViIlrLayout L{K, a.dx, a.dy};
   double* const P = a.loop.post + ((size_t)slot * B + prob) * L.count();
+  const double* const C = a.loop.post + ((size_t)cur * B + prob) * L.count();      // the current block (blend and init modes)
+  const double rho = a.loop.rho, omr = a.loop.one_minus_rho;
+  double inv = 0.0;
+  if constexpr (M == kViBlend) inv = a.loop.inv_scale[prob];
   const size_t sstride = (size_t)(1 + D + D * D);
   const bool stick = a.gating == kViGatingStick;
 
-  for (int k = lane; k < K; k += 64) t[8][k] = a.loop.S[((size_t)prob * K + k) * sstride];      // the counts
+  for (int k = lane; k < K; k += 64) t[8][k] = vi_stat<M>(a.loop.S, ((size_t)prob * K + k) * sstride);      // the counts
   wg_sync();
   double lgs = 0.0, lgs0 = 0.0;      // Dirichlet: lgamma of the sums
   if (stick) {
@@ -495,7 +515,9 @@ __global__ __launch_bounds__(64) void vi_ilr_gating_kernel(const ViIlrArgs a) {
     for (int k = lane; k < K; k += 64) {
       const size_t bk = (size_t)prob * K + k;
       const double g0 = a.g0[bk], d0 = a.g1[bk];
-      const double g = g0 + t[8][k], d = d0 + t[9][k];
+      // (blend: CategoricalWithStickBreaking.meanfield_sgd on the gammas and the deltas themselves)
+      const double g = vi_eta<M>(g0, t[8][k], vi_cur<M>(C, L.g0() + k), rho, omr, inv);
+      const double d = vi_eta<M>(d0, t[9][k], vi_cur<M>(C, L.g1() + k), rho, omr, inv);
       const double dsum = ilr_digamma(g + d);
       t[0][k] = g; t[1][k] = d; t[2][k] = g0; t[3][k] = d0;
       t[4][k] = ilr_digamma(g) - dsum;      // E[log stick]
@@ -514,7 +536,9 @@ __global__ __launch_bounds__(64) void vi_ilr_gating_kernel(const ViIlrArgs a) {
     // alpha = ((alpha0 - 1) + n) + 1
     for (int k = lane; k < K; k += 64) {
       const double a0 = a.g0[(size_t)prob * K + k];
-      t[0][k] = ((a0 - 1.0) + t[8][k]) + 1.0;
+      // (blend: on the natural parameter alpha - 1, CategoricalWithDirichlet.meanfield_sgd; init: the uploaded alpha itself)
+      if constexpr (M == kViInit) t[0][k] = C[L.g0() + k];
+      else t[0][k] = vi_eta<M>(a0 - 1.0, t[8][k], vi_cur<M>(C, L.g0() + k) - 1.0, rho, omr, inv) + 1.0;
       t[1][k] = 0.0;
       t[2][k] = a0;
       t[3][k] = 0.0;
@@ -597,9 +621,11 @@ __global__ __launch_bounds__(64) void vi_ilr_gating_kernel(const ViIlrArgs a) {
 
 bool ilr_args_ok(const ViIlrArgs& a) {
   const ViArgs& l = a.loop;
+  if (l.mode != kViConjugate && l.mode != kViBlend && l.mode != kViInit) return false;
+  if (l.mode == kViBlend && !l.inv_scale) return false;
   return l.B >= 1 && l.K >= 1 && l.K <= kBatchedMaxK && a.dx >= 1 && a.dy >= 1 && a.dx + a.dy <= 16 && l.D == a.dx + a.dy &&
-         l.K16 == (l.K + 15) / 16 && l.NS >= 1 && (a.gating == kViGatingDirichlet || a.gating == kViGatingStick) && l.S &&
-         l.scalars && l.post && l.prior_terms && l.last && l.words && l.theta && l.trace && a.g0 && a.g1 && a.pa && a.pb && a.pc &&
+         l.K16 == (l.K + 15) / 16 && l.NS >= 1 && (a.gating == kViGatingDirichlet || a.gating == kViGatingStick) &&
+         (l.S || l.mode == kViInit) && (l.scalars || l.mode == kViInit) && l.post && l.prior_terms && l.last && l.words && l.theta && l.trace && a.g0 && a.g1 && a.pa && a.pb && a.pc &&
          a.pd && a.plz && a.ma && a.mb && a.mc && a.md && a.mlz && a.term_b && a.term_m;
 }
 
@@ -607,13 +633,19 @@ bool ilr_args_ok(const ViIlrArgs& a) {
 
 hipError_t launch_vi_ilr_update(const ViIlrArgs& a, hipStream_t stream) {
   if (!ilr_args_ok(a) || (int64_t)a.loop.B * a.loop.K > (int64_t)INT32_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(vi_ilr_update_kernel, dim3((unsigned)(a.loop.B * a.loop.K)), dim3(64), 0, stream, a);
+  const dim3 grid((unsigned)(a.loop.B * a.loop.K));
+  if (a.loop.mode == kViBlend) hipLaunchKernelGGL(vi_ilr_update_kernel<kViBlend>, grid, dim3(64), 0, stream, a);
+  else if (a.loop.mode == kViInit) hipLaunchKernelGGL(vi_ilr_update_kernel<kViInit>, grid, dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL(vi_ilr_update_kernel<kViConjugate>, grid, dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 
 hipError_t launch_vi_ilr_gating(const ViIlrArgs& a, hipStream_t stream) {
   if (!ilr_args_ok(a)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(vi_ilr_gating_kernel, dim3((unsigned)a.loop.B), dim3(64), 0, stream, a);
+  const dim3 grid((unsigned)a.loop.B);
+  if (a.loop.mode == kViBlend) hipLaunchKernelGGL(vi_ilr_gating_kernel<kViBlend>, grid, dim3(64), 0, stream, a);
+  else if (a.loop.mode == kViInit) hipLaunchKernelGGL(vi_ilr_gating_kernel<kViInit>, grid, dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL(vi_ilr_gating_kernel<kViConjugate>, grid, dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -13,14 +13,15 @@ canonical form, host uniforms), then one batched label pass draws every model's 
 SVI: per outer iteration each model draws its minibatch indices, in model order; one batched pass over the chosen rows
 of every model's resident data (BatchedHipEngine.estep(rows=...): the rows are gathered on the device, nothing but the
 indices is uploaded) gives the minibatch statistics; each model takes its natural-gradient step (_svi_step, the step of
-its solo meanfield_stochastic_descent); one batched pass over all rows gives the bounds.
+its solo meanfield_stochastic_descent); one batched pass over all rows gives the bounds.  resident=True: the step runs on the
+device as well (BatchedHipEngine.svi_run), `chunk` iterations per call, and the posteriors come back once.
 
 Nested VI (meanfield_coordinate_descent_nested): the M inner mixtures of a mixture of mixtures (mixtures/hgmm.py) are the
 problems of ONE shared batch over one copy of the data; their inner descents run in lockstep on weighted batched passes, and
 the outer responsibilities — the weights of those passes — are computed and kept on the device."""
 import copy
 import random
-from contextlib import contextmanager
+from contextlib import contextmanager, nullcontext
 
 import numpy as np
 import numpy.random as npr
@@ -124,7 +125,6 @@ def _resident_reason(model, sample_likelihood):
 def _resident_descent(models, engine, maxiter, tol, chunk):
     """The loop of meanfield_coordinate_descent_batched(resident=True) behind the start: the statistics of the start lie on the
     device; priors up once, vi_run in chunks, state back once."""
-    from mimo_amd.utils.abstraction import Statistics as Stats
     B, K = len(models), models[0].size
     maxiter, chunk = int(maxiter), int(chunk)
     if chunk < 1:
@@ -149,7 +149,14 @@ def _resident_descent(models, engine, maxiter, tol, chunk):
             vlbs[i].extend(float(v) for v in trace[:int(n_done[i]), i])
             # (the device's own rule, on the same doubles: a problem that stopped at a chunk's last iteration is seen here)
             stopped[i] = n_done[i] < n or (len(vlbs[i]) > 1 and abs(vlbs[i][-1] - vlbs[i][-2]) < tol)
-    state = engine.vi_state(K)
+    _write_gmm_state(models, engine.vi_state(K), vlbs)
+    return vlbs
+
+
+def _write_gmm_state(models, state, vlbs, stream=None):
+    """The posterior blocks of a resident GMM loop (BatchedHipEngine.vi_state) into the models that appended a bound, as the
+    host-native sweep writes them, with memos; then one _refresh_likelihoods() per model (inside stream(i), if given)."""
+    from mimo_amd.utils.abstraction import Statistics as Stats
     part = lambda name, i: np.ascontiguousarray(state[name][i])
     for i, m in enumerate(models):
         if not vlbs[i]:
@@ -160,8 +167,8 @@ def _resident_descent(models, engine, maxiter, tol, chunk):
         post.params = (part('mus', i), qb, part('psis', i), nus)
         post._set_memo(nat=Stats([part('qa', i), qb, part('qc', i), part('qd', i)]), hld=part('hld', i),
                        estats=(bb, part('E2', i), - 0.5 * W, part('E4', i)), canon=(part('cc', i), bb, W), native=True)
-        m._refresh_likelihoods()
-    return vlbs
+        with stream(i) if stream is not None else nullcontext():
+            m._refresh_likelihoods()
 
 
 def meanfield_coordinate_descent_batched(models, data, randomize=True, maxiter=250, tol=1e-8, init_rng='host', seeds=None,
@@ -273,7 +280,6 @@ def meanfield_coordinate_descent_batched_ilr(models, data, randomize=True, maxit
     stick-breaking; input_dim + output_dim <= 16, size <= 128.  Anything else raises ValueError naming the model and the
     reason before anything is uploaded or drawn.  A problem one of whose blocks is not positive definite raises
     numpy.linalg.LinAlgError naming the problem; one whose canonical form or bound is not finite raises FloatingPointError."""
-    from mimo_amd.utils.abstraction import Statistics as Stats
     models, data = list(models), list(data)
     B = len(models)
     if B == 0 or len(data) != B:
@@ -326,7 +332,15 @@ def meanfield_coordinate_descent_batched_ilr(models, data, randomize=True, maxit
         for i in range(B):
             vlbs[i].extend(float(v) for v in trace[:int(n_done[i]), i])
             stopped[i] = n_done[i] < n or (len(vlbs[i]) > 1 and abs(vlbs[i][-1] - vlbs[i][-2]) < tol)
-    state = engine.vi_ilr_state(K)
+    _write_ilr_state(models, engine.vi_ilr_state(K), vlbs, stick)
+    return vlbs
+
+
+def _write_ilr_state(models, state, vlbs, stick, stream=None):
+    """The posterior blocks of a resident ILR loop (BatchedHipEngine.vi_ilr_state) into the models that appended a bound, as
+    the host route leaves them (gating, basis, experts with their memos); then one _refresh_likelihoods() per model (inside
+    stream(i), if given)."""
+    from mimo_amd.utils.abstraction import Statistics as Stats
     part = lambda name, i: np.ascontiguousarray(state[name][i])
     for i, m in enumerate(models):
         if not vlbs[i]:
@@ -346,8 +360,8 @@ def meanfield_coordinate_descent_batched_ilr(models, data, randomize=True, maxit
         post._set_memo(nat=Stats([part('m_a', i), Kq, part('m_c', i), part('m_d', i)]), hld=part('m_hld', i),
                        estats=(part('m_E1', i), part('m_E2', i), - 0.5 * nus[:, None, None] * psis, part('m_E4', i)),
                        canon_affine=(part('m_cc', i), part('m_bb', i), part('m_W', i)))
-        m._refresh_likelihoods()
-    return vlbs
+        with stream(i) if stream is not None else nullcontext():
+            m._refresh_likelihoods()
 
 
 def _nested_setup(model, obs, engine):
@@ -606,8 +620,98 @@ class _PythonStreams:
             random.setstate(self.caller)
 
 
+def _svi_resident_kind(models, sample_likelihood):
+    """What the device-resident SVI loop covers — the families of _resident_reason (mixtures of Gaussians) and of
+    _ilr_resident_reason (mixtures of linear-Gaussian experts, one gating kind per batch), without likelihood draws ->
+    None for mixtures of Gaussians, else the ILR batch's gating kind.  Raises ValueError naming the model and the reason."""
+    if type(models[0]) is BayesianMixtureOfGaussians:
+        for i, m in enumerate(models):
+            why = _resident_reason(m, sample_likelihood)
+            if why is not None:
+                raise ValueError(f"resident=True does not cover model {i}: {why}")
+        return None
+    if sample_likelihood:
+        raise ValueError("resident=True does not cover model 0: sample_likelihood=True (the loop makes no per-iteration "
+                         "likelihood draws)")
+    kinds = []
+    for i, m in enumerate(models):
+        why, kind = _ilr_resident_reason(m)
+        if why is not None:
+            raise ValueError(f"resident=True does not cover model {i}: {why}")
+        kinds.append(kind)
+    if any(k != kinds[0] for k in kinds):
+        raise ValueError(f"resident=True takes one gating kind per batch, got {kinds}")
+    return kinds[0]
+
+
+def philox_indices(seed, n_rows, batch_size, t):
+    """The minibatch the device draws for one problem at iteration t (index_rng='philox'): slot j holds
+    min(int(philox_uniform(seed, j, t) * n_rows), n_rows - 1) — with replacement, any batch_size."""
+    from mimo_amd.engine import philox_uniforms
+    u = philox_uniforms(seed, np.arange(int(batch_size)), int(t))
+    return np.minimum((u * float(n_rows)).astype(np.int64), int(n_rows) - 1)
+
+
+def _resident_stochastic_descent(models, engine, kind, nrows, first, maxiter, step_size, batch_size, chunk, draw, seeds,
+                                 stream):
+    """The loop of meanfield_stochastic_descent_batched(resident=True) behind the upload (and the random start, whose
+    statistics lie on the device: `first`): priors and the starting posterior up once, svi_run in chunks, state back once.
+    draw(): one iteration's B index arrays (index_rng='host'; unused with `seeds`, index_rng='philox'); stream(i): the context
+    model i's closing likelihood draws run in."""
+    B, K = len(models), models[0].size
+    gmm = type(models[0]) is BayesianMixtureOfGaussians
+    arr = lambda v: np.asarray(v, dtype=float)
+    stack = lambda parts: tuple(np.stack([arr(p[j]) for p in parts]) for j in range(len(parts[0])))
+    if gmm:
+        engine.vi_set_prior(np.stack([arr(m.gating.prior.alphas) for m in models]),
+                            *stack([_native_sweep._prior_block(m.components.prior) for m in models]))
+        status = engine.svi_set_state(np.stack([arr(m.gating.posterior.alphas) for m in models]),
+                                      *stack([tuple(m.components.posterior.nat_param) for m in models]))
+        run, get = engine.svi_run, engine.vi_state
+    else:
+        stick = kind == 'stick-breaking'
+        gate = lambda d: np.stack([arr(getattr(m.gating, d).gammas if stick else getattr(m.gating, d).alphas) for m in models])
+        rest = lambda d: np.stack([arr(getattr(m.gating, d).deltas) for m in models]) if stick else None
+        engine.vi_ilr_set_prior(kind, gate('prior'), rest('prior'),
+                                stack([_native_sweep._prior_block(m.basis.prior) for m in models]),
+                                stack([_native_sweep._prior_block(m.models.prior) for m in models]))
+        status = engine.svi_ilr_set_state(gate('posterior'), rest('posterior'),
+                                          stack([tuple(m.basis.posterior.nat_param) for m in models]),
+                                          stack([tuple(m.models.posterior.nat_param) for m in models]))
+        run, get = engine.svi_ilr_run, engine.vi_ilr_state
+
+    def check(status):
+        for i in np.flatnonzero(status):
+            if status[i] & 1:
+                raise np.linalg.LinAlgError(f"problem {int(i)}: Matrix is not positive definite (a block of a component's "
+                                            "posterior)")
+            raise FloatingPointError(f"problem {int(i)}: the canonical form or the bound of its posterior is not finite")
+
+    check(status)
+    vlbs = [[] for _ in range(B)]
+    scale = np.array([batch_size / float(n) for n in nrows])
+    sizes = np.full(B, batch_size, dtype=np.int64)
+    left = maxiter
+    while left > 0:
+        n = min(chunk, left)
+        start = first and left == maxiter
+        rows = [draw() for _ in range(n - (1 if start else 0))] if seeds is None else None
+        trace, n_done, status = run(K, n, step_size, scale, sizes, rows=rows, seeds=seeds, resident_start=start)
+        left -= n
+        check(status)
+        for i in range(B):
+            vlbs[i].extend(float(v) for v in trace[:int(n_done[i]), i])
+    state = get(K)
+    if gmm:
+        _write_gmm_state(models, state, vlbs, stream)
+    else:
+        _write_ilr_state(models, state, vlbs, kind == 'stick-breaking', stream)
+    return vlbs
+
+
 def meanfield_stochastic_descent_batched(models, data, randomize=True, maxiter=500, step_size=1e-3, batch_size=128,
-                                         sample_likelihood=True, numpy_seeds=None, python_seeds=None, engine=None):
+                                         sample_likelihood=True, numpy_seeds=None, python_seeds=None, engine=None,
+                                         resident=False, chunk=8, index_rng='host', seeds=None):
     """Stochastic variational inference of B models with two batched passes per outer iteration: per model what its solo
     meanfield_stochastic_descent(data, randomize, maxiter, step_size, batch_size, sample_likelihood=sample_likelihood)
     does in the plain form of the shared outer loop (mixtures/_svi.py).  models / data / engine as in
@@ -626,7 +730,22 @@ def meanfield_stochastic_descent_batched(models, data, randomize=True, maxiter=5
     draws run on streams of their own, started as numpy.random.seed(numpy_seeds[i]) and random.seed(python_seeds[i]), so
     with both lists the batch reproduces B solo runs each preceded by those two calls; the caller's states of both
     generators are restored at the end, also on an exception.  Without a list that generator's global stream is consumed
-    in model order (at B = 1: the solo plain form's order)."""
+    in model order (at B = 1: the solo plain form's order).
+
+    resident=True: the natural-gradient step runs on the device too (BatchedHipEngine.svi_run): after the upload (and, with
+    randomize=True, the random start exactly as above) the priors and the starting posteriors go up once, the loop runs
+    `chunk` iterations per call — minibatch pass, step, pass over all rows, bound, no host work per model — and the
+    posteriors come back once and are written into the models as the resident coordinate-descent drivers write them (then
+    one _refresh_likelihoods() per model).  Covered: the families of meanfield_coordinate_descent_batched(resident=True) and
+    of meanfield_coordinate_descent_batched_ilr, with sample_likelihood=False; anything else raises ValueError naming the
+    model and the reason before anything is uploaded or drawn.  index_rng='host': each chunk's indices are drawn with
+    sample_indices on the streams above, iteration by iteration and in model order within an iteration, so Python's
+    generator is consumed as the host route consumes it (batch_size > N_b raises ValueError).  index_rng='philox': the
+    indices are drawn on the device with replacement from the Philox stream keyed by seeds[i] (philox_indices; any
+    batch_size), and nothing is sent per chunk.  A problem one of whose blocks is not positive definite raises
+    numpy.linalg.LinAlgError naming the problem, one whose canonical form or bound is not finite FloatingPointError."""
+    models, data = list(models), list(data)
+    kind = _svi_resident_kind(models, sample_likelihood) if resident and models else None      # (sizes aside: the families first)
     models, data, cls = _check_models(models, data)
     B = len(models)
     maxiter, batch_size = int(maxiter), int(batch_size)
@@ -634,7 +753,19 @@ def meanfield_stochastic_descent_batched(models, data, randomize=True, maxiter=5
         raise ValueError(f"batch_size = {batch_size} < 1")
     for name, sd in (("numpy seeds", numpy_seeds), ("python seeds", python_seeds)):
         _per_model(sd, B, 0, name)
+    if resident:
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk = {chunk} < 1")
+        if index_rng not in ('host', 'philox'):
+            raise ValueError(index_rng)
+        seeds = [int(sd) for sd in _per_model(seeds, B, 0, "seeds")] if index_rng == 'philox' else None
     rows = [_rows(m, d) for m, d in zip(models, data)]       # (validates the structure before any draw)
+    if resident and index_rng == 'host':
+        for i, r in enumerate(rows):
+            if batch_size > len(r):
+                raise ValueError(f"model {i}: batch_size = {batch_size} exceeds its {len(r)} rows (index_rng='host' draws "
+                                 "without replacement; index_rng='philox' draws with)")
     nstreams, pstreams = _NumpyStreams(numpy_seeds, B), _PythonStreams(python_seeds, B)
     vlbs = [[] for _ in range(B)]
     if maxiter <= 0:
@@ -645,6 +776,28 @@ def meanfield_stochastic_descent_batched(models, data, randomize=True, maxiter=5
         engine.upload(rows)
         K = models[0].size
         nrows = [int(n) for n in np.diff(engine.row_off)]
+        if resident:
+            def draw():
+                batches = []
+                for i in range(B):
+                    with pstreams.of(i):
+                        batches.append(sample_indices(nrows[i], batch_size, as_array=True))
+                return batches
+
+            first = randomize is True
+            if first:       # the random start of the host route below, its statistics left on the device
+                batches = draw() if seeds is None else [philox_indices(seeds[i], nrows[i], batch_size, 0) for i in range(B)]
+                tables = []
+                for i in range(B):
+                    with nstreams.of(i):
+                        resp = npr.rand(K, len(batches[i]))
+                    resp /= np.sum(resp, axis=0)
+                    table = np.zeros((K, nrows[i]))
+                    np.add.at(table, (slice(None), batches[i]), resp)      # (a row drawn twice counts twice)
+                    tables.append(table)
+                engine.weighted_stats(tables)
+            return _resident_stochastic_descent(models, engine, kind, nrows, first, maxiter, step_size, batch_size, chunk,
+                                                draw, seeds, nstreams.of)
         for it in range(maxiter):
             batches = []
             for i in range(B):

@@ -2,7 +2,7 @@
 data resident), on the same inputs, after warm-up; wall time per pass (each call returns synchronised host results) and the
 largest relative difference of the outputs.  Writes <out>/bench_batched.json.
 
-    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3] [--start-only | --no-start | --svi | --predict | --nested | --resident | --resident-ilr]
+    python tools/bench_batched.py --out DIR [--reps R] [--shapes 1,2,3] [--start-only | --no-start | --svi | --predict | --nested | --resident | --resident-ilr | --resident-svi]
 
 Also times one iteration of meanfield_coordinate_descent_batched against B solo meanfield_iteration calls at shape 1
 (24 ILR models, K = 100, dx = dy = 1), split into host time and pass time.
@@ -55,6 +55,14 @@ repetitions' figures (use --reps 7), the largest relative difference of the trac
 update on tests/golden/vi_ilr_update_hp.npz.  Shapes (--shapes 1,2,3): 1. B = 24, N_b = 1600, dx = dy = 1, K = 100, stick-breaking
 (the reference's parallel job); 2. B = 64, N_b = 1e4, dx = dy = 1, K = 4, Dirichlet; 3. B = 8, N_b = 2.5e5, dx = 8, dy = 4, K = 64,
 stick-breaking.
+
+Resident SVI leg (--resident-svi, on its own; writes <out>/batched_resident_svi.json): the resident ILR leg's scheme for stochastic
+VI — meanfield_stochastic_descent_batched(resident=True) with index_rng='host' and with index_rng='philox' against the host route
+(resident=False, sample_likelihood=False) on the same ILR models, randomize=False, minibatches of 256 rows, step size 0.5, the
+same numpy and Python seeds; the three alternated, 1 and 1 + iters iterations per run, each run clocked from the return of the
+upload; median, minimum and maximum of the repetitions' figures (use --reps 7) and the largest relative difference between the
+host route's trace and the resident one on the same indices.  Shapes (--shapes 1,2,3): those of the resident ILR leg, shape 3 at
+N_b = 1e5.
 
 Shapes: 1. B = 24, N_b = 1600, Dz = 2, K = 100 (the reference's parallel ILR example); 2. B = 64, N_b = 1e4, Dz = 2, K = 4
 (restarts of the toy GMM); 3. B = 8, N_b = 2.5e5, Dz = 12, K = 64 (C4 per model)."""
@@ -813,6 +821,77 @@ def run_resident_ilr_shape(sid, reps, iters=10):
     return res
 
 
+class _UploadClock:
+    """BatchedHipEngine that stamps the return of the upload: an SVI driver run without a random start is clocked from there."""
+
+    def __init__(self, eng):
+        self.eng, self.t0 = eng, None
+
+    def upload(self, *a, **k):
+        out = self.eng.upload(*a, **k)
+        self.t0 = time.perf_counter()
+        return out
+
+    def __getattr__(self, name):
+        return getattr(self.eng, name)
+
+
+def run_resident_svi_shape(sid, reps, iters=10, batch=256):
+    """run_resident_ilr_shape for stochastic VI: meanfield_stochastic_descent_batched(resident=True), its indices drawn on the
+    host or on the device, against its host route (resident=False, sample_likelihood=False)."""
+    from mimo_amd.mixtures.batched import meanfield_stochastic_descent_batched
+    B, N, dx, dy, K, gating = RESIDENT_ILR_SHAPES[sid]
+    N = min(N, 100000)
+    solo_engine, beng = HipEngine(0), BatchedHipEngine(0)
+    build, data = ilr_resident_models(B, N, dx, dy, K, gating, solo_engine, 500 + sid)
+    kw = dict(randomize=False, step_size=0.5, batch_size=batch, sample_likelihood=False, numpy_seeds=list(range(B)),
+              python_seeds=list(range(B)))
+    routes = {"host": dict(resident=False), "resident_host_indices": dict(resident=True, chunk=8, index_rng='host'),
+              "resident_philox_indices": dict(resident=True, chunk=8, index_rng='philox', seeds=list(range(B)))}
+
+    def leg(route):
+        def run(n, out=None):
+            models = build()
+            clock = _UploadClock(beng)
+            vlbs = meanfield_stochastic_descent_batched(models, data, maxiter=n, engine=clock, **kw, **route)
+            dt = time.perf_counter() - clock.t0
+            if out is not None:
+                out.append(vlbs)
+            return dt
+        return run
+    legs = {name: leg(route) for name, route in routes.items()}
+    kept = {name: [] for name in legs}
+    for name, fn in legs.items():                        # warm-up, and the traces that are compared
+        fn(1)
+        fn(1 + iters, kept[name])
+    per = {name: [] for name in legs}
+    for _ in range(reps):                                # the legs alternate within a repetition
+        for name, fn in legs.items():
+            per[name].append((fn(1 + iters) - fn(1)) / iters)
+    h, r = np.array(kept["host"][0]), np.array(kept["resident_host_indices"][0])
+    res = {"resident_svi_shape": sid, "B": B, "N_b": N, "dx": dx, "dy": dy, "K": K, "gating": gating, "batch_size": batch,
+           "iters_per_figure": iters, "reps": reps, "chunk": 8, "max_rel_trace_diff": float(np.max(np.abs(r - h) / np.abs(h)))}
+    for name in legs:
+        ms = np.array(per[name]) * 1e3
+        res[name + "_ms_per_iteration"] = float(np.median(ms))
+        res[name + "_ms_per_iteration_min_max"] = [float(ms.min()), float(ms.max())]
+        res[name + "_ms_per_iteration_all"] = [float(v) for v in ms]
+    for name in ("resident_host_indices", "resident_philox_indices"):
+        res["speedup_" + name] = res["host_ms_per_iteration"] / res[name + "_ms_per_iteration"]
+    # what the host draws of one iteration's indices cost on their own (B sample_indices calls)
+    import random
+    from mimo_amd.utils.data import sample_indices
+    random.seed(0)
+    t0 = time.perf_counter()
+    for _ in range(20):
+        for _ in range(B):
+            sample_indices(N, batch, as_array=True)
+    res["host_index_draws_ms_per_iteration"] = (time.perf_counter() - t0) / 20 * 1e3
+    solo_engine.close()
+    beng.close()
+    return res
+
+
 def resident_ilr_error_ratios():
     """One device update on every shape of tests/golden/vi_ilr_update_hp.npz: per shape and output block the largest error of the
     device and of the host route against the 50-digit values, and their ratio."""
@@ -879,7 +958,20 @@ def main():
     ap.add_argument("--resident", action="store_true", help="only the resident leg (device-resident VI loop against the host route)")
     ap.add_argument("--resident-ilr", action="store_true",
                     help="only the resident ILR leg (device-resident loop for mixtures of linear-Gaussian experts against the host route)")
+    ap.add_argument("--resident-svi", action="store_true",
+                    help="only the resident SVI leg (device-resident SVI loop, host and device index draws, against the host route)")
     args = ap.parse_args()
+    if args.resident_svi:
+        os.makedirs(args.out, exist_ok=True)
+        res = {"timings": []}
+        path = os.path.join(args.out, "batched_resident_svi.json")
+        for s in args.shapes.split(","):
+            if int(s) in RESIDENT_ILR_SHAPES:
+                res["timings"].append(run_resident_svi_shape(int(s), args.reps))
+                print(json.dumps({k: v for k, v in res["timings"][-1].items() if not k.endswith("_all")}), flush=True)
+                with open(path, "w") as f:               # (after every shape: a long run leaves what it has)
+                    json.dump(res, f, indent=1)
+        return
     if args.resident_ilr:
         os.makedirs(args.out, exist_ok=True)
         res = {"timings": [], "update_error_vs_50_digits": resident_ilr_error_ratios()}

@@ -441,14 +441,7 @@ class BatchedHipEngine:
             raise ValueError("the priors must be finite")
         self._check(self._lib.mimo_vi_prior_batched(self._ctx, K, _ptr(alpha0), _ptr(pa), _ptr(pb), _ptr(pc), _ptr(pd), _ptr(plz)))
 
-    def vi_run(self, K, iters, tol):
-        """`iters` mean-field iterations of every problem that is still active, on the device: conjugate update from the
-        statistics the last pass left resident, canonical form, batched pass, bound, stopping rule |vlb_t - vlb_{t-1}| < tol
-        (mimo_vi_run_batched).  Returns (trace (iters, B), NaN where a problem appended nothing; n_done (B,), the bounds
-        appended in this call; status (B,), bits: 1 for a problem one of whose blocks was not positive definite, 2 for one
-        whose canonical form or bound was not finite — such a problem keeps the state of its last complete iteration).  The
-        loop's passes are plain passes over all rows, whatever pass left the statistics it starts from.  The state persists
-        across calls: vi_run(6) and vi_run(2) followed by vi_run(4) give the same bits."""
+    def _vi_run(self, call, K, iters, tol):
         K, iters, tol = int(K), int(iters), float(tol)
         if K < 1 or iters < 1:
             raise ValueError(f"K = {K} and iters = {iters} must be >= 1")
@@ -457,8 +450,29 @@ class BatchedHipEngine:
         trace = np.empty((iters, self.B))
         n_done = np.empty(self.B, dtype=np.int32)
         status = np.empty(self.B, dtype=np.int32)
-        self._check(self._lib.mimo_vi_run_batched(self._ctx, K, iters, tol, 0, _ptr(trace), _ptr(n_done), _ptr(status)))
+        self._check(getattr(self._lib, call)(self._ctx, K, iters, tol, 0, _ptr(trace), _ptr(n_done), _ptr(status)))
         return trace, n_done, status
+
+    def _vi_unpack(self, call, K, names, shapes):
+        """Every problem's current posterior block, split into its parts with a leading problem axis."""
+        sizes = [int(np.prod(s)) for s in shapes]
+        out = np.empty((self.B, sum(sizes)))
+        self._check(getattr(self._lib, call)(self._ctx, K, _ptr(out)))
+        state, o = {}, 0
+        for name, shape, n in zip(names, shapes, sizes):
+            state[name] = out[:, o:o + n].reshape((self.B,) + shape).copy()
+            o += n
+        return state
+
+    def vi_run(self, K, iters, tol):
+        """`iters` mean-field iterations of every problem that is still active, on the device: conjugate update from the
+        statistics the last pass left resident, canonical form, batched pass, bound, stopping rule |vlb_t - vlb_{t-1}| < tol
+        (mimo_vi_run_batched).  Returns (trace (iters, B), NaN where a problem appended nothing; n_done (B,), the bounds
+        appended in this call; status (B,), bits: 1 for a problem one of whose blocks was not positive definite, 2 for one
+        whose canonical form or bound was not finite — such a problem keeps the state of its last complete iteration).  The
+        loop's passes are plain passes over all rows, whatever pass left the statistics it starts from.  The state persists
+        across calls: vi_run(6) and vi_run(2) followed by vi_run(4) give the same bits."""
+        return self._vi_run('mimo_vi_run_batched', K, iters, tol)
 
     def vi_state(self, K):
         """The posterior blocks the loop holds, as a dict of arrays with a leading problem axis: alpha, qa, qb, qc, qd (the
@@ -468,15 +482,7 @@ class BatchedHipEngine:
         K = int(K)
         if K < 1:
             raise ValueError(f"K = {K} must be >= 1")
-        shapes = self._vi_part_shapes(K)
-        sizes = [int(np.prod(s)) for s in shapes]
-        out = np.empty((self.B, sum(sizes)))
-        self._check(self._lib.mimo_vi_get_batched(self._ctx, K, _ptr(out)))
-        state, o = {}, 0
-        for name, shape, n in zip(self.VI_PARTS, shapes, sizes):
-            state[name] = out[:, o:o + n].reshape((self.B,) + shape).copy()
-            o += n
-        return state
+        return self._vi_unpack('mimo_vi_get_batched', K, self.VI_PARTS, self._vi_part_shapes(K))
 
     def _vi_resident(self, K):
         """Test hook: (the operand images the loop's passes read (B, ceil(K/16), F16/4, 64); the statistics the last pass left
@@ -556,16 +562,7 @@ class BatchedHipEngine:
         (mimo_vi_ilr_run_batched): the same returns, the same stopping rule, the same persistence across calls.  Status bit
         1: one of a component's three factorised blocks (the basis block, Kq, C) was not positive definite; bit 2: a joint
         canonical form or a term of the bound was not finite."""
-        K, iters, tol = int(K), int(iters), float(tol)
-        if K < 1 or iters < 1:
-            raise ValueError(f"K = {K} and iters = {iters} must be >= 1")
-        if not tol >= 0.:
-            raise ValueError(f"tol = {tol} must be >= 0")
-        trace = np.empty((iters, self.B))
-        n_done = np.empty(self.B, dtype=np.int32)
-        status = np.empty(self.B, dtype=np.int32)
-        self._check(self._lib.mimo_vi_ilr_run_batched(self._ctx, K, iters, tol, 0, _ptr(trace), _ptr(n_done), _ptr(status)))
-        return trace, n_done, status
+        return self._vi_run('mimo_vi_ilr_run_batched', K, iters, tol)
 
     def vi_ilr_state(self, K):
         """The posterior blocks the ILR loop holds, as a dict of arrays with a leading problem axis (VI_ILR_PARTS):
@@ -579,15 +576,7 @@ class BatchedHipEngine:
         dims = getattr(self, '_vi_ilr_dims', None)
         if dims is None:
             raise ValueError("no ILR prior block was set (vi_ilr_set_prior)")
-        shapes = self._vi_ilr_part_shapes(K, *dims)
-        sizes = [int(np.prod(s)) for s in shapes]
-        out = np.empty((self.B, sum(sizes)))
-        self._check(self._lib.mimo_vi_ilr_get_batched(self._ctx, K, _ptr(out)))
-        state, o = {}, 0
-        for name, shape, n in zip(self.VI_ILR_PARTS, shapes, sizes):
-            state[name] = out[:, o:o + n].reshape((self.B,) + shape).copy()
-            o += n
-        return state
+        return self._vi_unpack('mimo_vi_ilr_get_batched', K, self.VI_ILR_PARTS, self._vi_ilr_part_shapes(K, *dims))
 
     # ---- device-resident SVI (mimo_svi_state_batched / mimo_svi_run_batched and their _ilr_ forms) ----
     def _svi_status(self, call, *args):

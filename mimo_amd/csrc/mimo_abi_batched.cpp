@@ -30,6 +30,7 @@
 #include "mimo_abi_internal.h"
 #include "mimo_kernels.h"
 #include "mimo_predict_batched.h"
+#include "mimo_selection.h"
 #include "mimo_vi_batched.h"
 #include "mimo_vi_ilr_batched.h"
 
@@ -60,22 +61,10 @@ static int check_offsets(mimo_ctx* ctx, const int64_t* off, int B, const char* m
   return MIMO_OK;
 }
 
-// The work table of B problems with the rows [off[b], off[b + 1]): problem b's tiles in runs of batched_tiles_per_wg(N_b), a
-// function of N_b alone; problem b owns the workgroups [wg_off[b], wg_off[b + 1]).  wg_off gets B + 2 entries (whole uint64
-// words for the caller that stages it behind an operand image).
+// The work table of a batch (build_work_table, mimo_selection.h) under the library's rule for the tiles of one workgroup
 static int build_work(mimo_ctx* ctx, const int64_t* off, int B, const char* me, std::vector<BatchedWork>* work,
                       std::vector<int32_t>* wg_off) {
-  work->clear();
-  *wg_off = std::vector<int32_t>((size_t)B + 2, 0);
-  for (int b = 0; b < B; ++b) {
-    const int64_t nb = off[b + 1] - off[b];
-    const int64_t tiles = (nb + kTile - 1) / kTile;
-    const int tpw = batched_tiles_per_wg(nb);
-    for (int64_t t = 0; t < tiles; t += tpw)
-      work->push_back(BatchedWork{b, (int32_t)t, (int32_t)std::min<int64_t>(tpw, tiles - t), 0});
-    if (work->size() > (size_t)INT32_MAX) return fail(ctx, MIMO_E_INVALID, "%s: too many rows", me);
-    (*wg_off)[(size_t)b + 1] = (int32_t)work->size();
-  }
+  if (!build_work_table(off, B, batched_tiles_per_wg, work, wg_off)) return fail(ctx, MIMO_E_INVALID, "%s: too many rows", me);
   return MIMO_OK;
 }
 
@@ -224,6 +213,14 @@ static int batched_reduce(mimo_ctx* ctx, int K, const int32_t* wg_off, int split
   return MIMO_OK;
 }
 
+// The same reduction for the scalars alone, into their place behind resident statistics of this K, which stay as they are and
+// stay valid (the bound's pass of the SVI loop)
+static int batched_reduce_scalars(mimo_ctx* ctx, int K, const int32_t* wg_off, int split) {
+  HIP_TRY(ctx, launch_batched_reduce(ctx->partials, wg_off, ctx->batch_B, ctx->feat_d, K, ctx->D, ctx->F, ctx->F16, split, nullptr,
+                                     ctx->S_d + batch_stats_len(ctx, K), ctx->stream));
+  return MIMO_OK;
+}
+
 // The end of every pass that returns statistics: room for the result block, the reduction, and the hand-out of S (with
 // `want_stats`) and of the 3 B scalars (null: not returned, and not copied).
 static int reduce_and_deliver(mimo_ctx* ctx, int K, const int32_t* wg_off, int split, bool want_stats, double* S, double* scalars) {
@@ -244,12 +241,10 @@ struct SoftmaxForm {
   int allowed;                        // flags the form takes
   const char* allowed_text;           // ... as its refusal names them
   const double* weights = nullptr;    // launch_batched_weighted: the per-row weights of the statistics (device)
-  // the rows form: `sel` (nsel indices) and then `tables` ([sel_off (B + 1) | work table (2 words per workgroup) | wg_off]) go
-  // behind the image in its transfer; at_work / at_wg: the words of `tables` where the work table and wg_off start; G workgroups
+  // the rows form: `sel` (nsel indices) and then the selection's tables (mimo_selection.h) go behind the image in its transfer
   const uint64_t* sel = nullptr;
   size_t nsel = 0;
-  const uint64_t* tables = nullptr;
-  size_t ntables = 0, at_work = 0, at_wg = 0, G = 0;
+  const SelectionTables* tables = nullptr;
 };
 
 static int softmax_args(mimo_ctx* ctx, const SoftmaxForm& f, const double* c, const double* b, const double* W, int flags,
@@ -265,8 +260,9 @@ static int batched_softmax_pass(mimo_ctx* ctx, const SoftmaxForm& f, const doubl
                                 int flags, double* S, double* scalars, const char* me) {
   int rc;
   if ((rc = softmax_args(ctx, f, c, b, W, flags, S, scalars, me))) return rc;
-  if ((rc = batched_theta(ctx, c, b, W, K, f.sel, f.nsel, me, f.tables, f.ntables))) return rc;
-  const size_t G = f.tables ? f.G : (size_t)ctx->batch_G;
+  if ((rc = batched_theta(ctx, c, b, W, K, f.sel, f.nsel, me, f.tables ? f.tables->words.data() : nullptr,
+                          f.tables ? f.tables->words.size() : 0))) return rc;
+  const size_t G = f.tables ? f.tables->G : (size_t)ctx->batch_G;
   if ((rc = ensure_partials(ctx, K, G))) return rc;
   const bool no_stats = (flags & MIMO_F_NO_STATS) != 0, keep_lse = (flags & MIMO_F_KEEP_LSE) != 0;
   if (keep_lse && (rc = ctx->lse.ensure(ctx, (size_t)table_rows(ctx)))) return rc;
@@ -281,8 +277,8 @@ static int batched_softmax_pass(mimo_ctx* ctx, const SoftmaxForm& f, const doubl
     const uint64_t* tables_d = sel_d + f.nsel;
     a.sel = reinterpret_cast<const int64_t*>(sel_d);
     a.sel_off = reinterpret_cast<const int64_t*>(tables_d);
-    a.work = reinterpret_cast<const BatchedWork*>(tables_d + f.at_work);
-    wg_off = reinterpret_cast<const int32_t*>(tables_d + f.at_wg);
+    a.work = reinterpret_cast<const BatchedWork*>(tables_d + f.tables->at_work);
+    wg_off = reinterpret_cast<const int32_t*>(tables_d + f.tables->at_wg);
   }
   HIP_TRY(ctx, f.launch(a, (int)G, ctx->stream));
   const int split = (flags & (MIMO_F_ENTROPY_SPLIT | MIMO_F_KEEP_LSE)) ? 1 : 0;
@@ -347,27 +343,14 @@ int mimo_estep_batched_rows(mimo_ctx* ctx, const double* c, const double* b, con
   const int B = ctx->batch_B;
   // the kernel gathers through these indices unchecked: every one is checked here, before anything is staged or launched
   if ((rc = check_offsets(ctx, sel_off, B, me, "sel_off"))) return rc;
-  for (int p = 0; p < B; ++p) {
-    const int64_t nb = ctx->batch_rows[(size_t)p + 1] - ctx->batch_rows[(size_t)p];
-    for (int64_t i = sel_off[p]; i < sel_off[p + 1]; ++i)
-      if (rows[i] < 0 || rows[i] >= nb)
-        return fail(ctx, MIMO_E_INVALID, "%s: problem %d: index %lld (entry %lld of its selection) outside [0, %lld)", me,
-                    p, (long long)rows[i], (long long)(i - sel_off[p]), (long long)nb);
-  }
-  std::vector<BatchedWork> work;
-  std::vector<int32_t> wg_off;
-  if ((rc = build_work(ctx, sel_off, B, me, &work, &wg_off))) return rc;
-  // the small tables: [sel_off (B + 1) | work table | wg_off (int32, B + 1, in whole words)]
-  static_assert(sizeof(BatchedWork) == 2 * sizeof(uint64_t), "a work table entry is two words of the staged block");
-  std::vector<uint64_t> tables((size_t)B + 1);
-  memcpy(tables.data(), sel_off, ((size_t)B + 1) * sizeof(int64_t));
-  const size_t G = work.size(), at_work = tables.size(), at_wg = at_work + 2 * G, nwg = ((size_t)B + 2) / 2;
-  tables.resize(at_wg + nwg);
-  if (G) memcpy(tables.data() + at_work, work.data(), G * sizeof(BatchedWork));
-  memcpy(tables.data() + at_wg, wg_off.data(), nwg * sizeof(uint64_t));
+  SelectionBad bad;
+  if (!selection_indices_ok(rows, 1, sel_off, ctx->batch_rows.data(), B, &bad))
+    return fail(ctx, MIMO_E_INVALID, "%s: problem %d: index %lld (entry %lld of its selection) outside [0, %lld)", me, bad.prob,
+                (long long)bad.index, (long long)bad.entry, (long long)bad.rows);
+  SelectionTables tables;
+  if (!tables.build(sel_off, B, batched_tiles_per_wg)) return fail(ctx, MIMO_E_INVALID, "%s: too many rows", me);
   form.sel = reinterpret_cast<const uint64_t*>(rows); form.nsel = (size_t)sel_off[B];      // (straight from the caller's array)
-  form.tables = tables.data(); form.ntables = tables.size();
-  form.at_work = at_work; form.at_wg = at_wg; form.G = G;
+  form.tables = &tables;
   return batched_softmax_pass(ctx, form, c, b, W, K, flags, S, scalars, me);
   });
 }
@@ -556,103 +539,164 @@ int mimo_random_resp_stats_batched(mimo_ctx* ctx, int K, const uint64_t* seeds, 
   });
 }
 
-// ------------------------------------------------------------------------------------------
-// Device-resident batched VI (mimo_vi_batched.hip)
-// ------------------------------------------------------------------------------------------
-// doubles the loop's int32 words take at the front of vi_loop
-static size_t vi_words_len(int B) { return ((size_t)kViWords * B + 1) / 2; }
+}  // extern "C"
 
-// What the loop's entry points share beyond batched_ready: a prior block of this K and of the caller's family (0: mixtures of
-// Gaussians, 1: mixtures of linear-Gaussian experts, -1: either)
-static const char* vi_family_name(int family) {
-  return family == 1 ? "mixtures of linear-Gaussian experts (mimo_vi_ilr_prior_batched)"
-                     : "mixtures of Gaussians (mimo_vi_prior_batched)";
+// ------------------------------------------------------------------------------------------
+// Device-resident batched VI and SVI (mimo_vi_batched.hip, mimo_vi_ilr_batched.hip)
+// ------------------------------------------------------------------------------------------
+// One family is resident at a time (ctx->vi_family indexes kViFamilies), in the same five buffers:
+//   vi_prior  the parts of the family's prior call, each [B][...], in the call's order (ViArgs / ViIlrArgs)
+//   vi_post   [2][B][post_len]
+//   vi_work   [the family's term arrays, B K each | prior terms B | last bound B]
+//   vi_theta  the operand images the loop's passes read;  vi_loop  the words, then the trace of one call
+// The SVI loop adds svi_sel (the minibatch indices of one call) and svi_tables (SelectionTables, mimo_selection.h).
+struct ViFamily {
+  int id;                                          // ctx->vi_family
+  const char* name;                                // as the refusals name the family
+  const char* prior_call;                          // the entry points that install its priors and its starting posterior
+  const char* state_call;
+  size_t (*post_len)(const mimo_ctx*, int K);      // doubles per problem of the posterior block
+  size_t terms;                                    // term arrays at the front of vi_work: vi_work holds terms B K + 2 B doubles
+  int (*step)(mimo_ctx*, const ViLoop&);           // the update and the gating kernel in the loop's mode
+};
+
+// the family's priors in vi_prior, one after the other: *p, then *p behind `per_bk` doubles per (problem, component)
+static const double* next_part(const double** p, const ViLoop& l, size_t per_bk) {
+  const double* at = *p;
+  *p += (size_t)l.B * l.K * per_bk;
+  return at;
 }
 
-static int vi_ready(mimo_ctx* ctx, int K, const char* me, int family = 0) {
+static int vi_gmm_step(mimo_ctx* ctx, const ViLoop& l) {
+  const size_t D = (size_t)l.D;
+  ViArgs a{};
+  a.loop = l;
+  const double* p = ctx->vi_prior;
+  a.alpha0 = next_part(&p, l, 1);
+  a.pa = next_part(&p, l, D); a.pb = next_part(&p, l, 1); a.pc = next_part(&p, l, D * D); a.pd = next_part(&p, l, 1);
+  a.plz = next_part(&p, l, 1);
+  a.term = ctx->vi_work;
+  HIP_TRY(ctx, launch_vi_update(a, ctx->stream));
+  HIP_TRY(ctx, launch_vi_gating(a, ctx->stream));
+  return MIMO_OK;
+}
+
+static int vi_ilr_step(mimo_ctx* ctx, const ViLoop& l) {
+  const size_t dx = (size_t)ctx->vi_dx, dy = (size_t)ctx->vi_dy, dc = dx + 1;
+  ViIlrArgs a{};
+  a.loop = l;
+  const double* p = ctx->vi_prior;
+  a.g0 = next_part(&p, l, 1); a.g1 = next_part(&p, l, 1);
+  a.pa = next_part(&p, l, dx); a.pb = next_part(&p, l, 1); a.pc = next_part(&p, l, dx * dx); a.pd = next_part(&p, l, 1);
+  a.plz = next_part(&p, l, 1);
+  a.ma = next_part(&p, l, dy * dc); a.mb = next_part(&p, l, dc * dc); a.mc = next_part(&p, l, dy * dy); a.md = next_part(&p, l, 1);
+  a.mlz = next_part(&p, l, 1);
+  a.term_b = ctx->vi_work;
+  a.term_m = ctx->vi_work + (size_t)l.B * l.K;
+  a.dx = ctx->vi_dx; a.dy = ctx->vi_dy; a.gating = ctx->vi_gating;
+  HIP_TRY(ctx, launch_vi_ilr_update(a, ctx->stream));
+  HIP_TRY(ctx, launch_vi_ilr_gating(a, ctx->stream));
+  return MIMO_OK;
+}
+
+enum { kViGmm = 0, kViIlr = 1 };
+static const ViFamily kViFamilies[2] = {
+    {kViGmm, "mixtures of Gaussians (mimo_vi_prior_batched)", "mimo_vi_prior_batched", "mimo_svi_state_batched",
+     [](const mimo_ctx* ctx, int K) { return (size_t)ViLayout{K, ctx->D}.count(); }, 1, vi_gmm_step},
+    {kViIlr, "mixtures of linear-Gaussian experts (mimo_vi_ilr_prior_batched)", "mimo_vi_ilr_prior_batched",
+     "mimo_svi_ilr_state_batched",
+     [](const mimo_ctx* ctx, int K) { return (size_t)ViIlrLayout{K, ctx->vi_dx, ctx->vi_dy}.count(); }, 2, vi_ilr_step}};
+
+// doubles the loop's int32 words take at the front of vi_loop
+static size_t vi_words_len(int B) { return ((size_t)kViWords * B + 1) / 2; }
+static size_t vi_work_len(const mimo_ctx* ctx, int K, const ViFamily& f) { return (f.terms * K + 2) * (size_t)ctx->batch_B; }
+
+// What the loop's entry points share beyond batched_ready: a prior block of this K and of the caller's family (null: either)
+static int vi_ready(mimo_ctx* ctx, int K, const char* me, const ViFamily* f) {
   if (!ctx->vi_prior_valid || !ctx->vi_prior)
     return fail(ctx, MIMO_E_STATE, "%s: no prior block is resident (call %s; an upload drops it)", me,
-                family == 1 ? "mimo_vi_ilr_prior_batched" : "mimo_vi_prior_batched");
-  if (family >= 0 && ctx->vi_family != family)
+                (f ? f : kViFamilies)->prior_call);
+  if (f && ctx->vi_family != f->id)
     return fail(ctx, MIMO_E_STATE, "%s: the resident prior block is that of %s, this call runs %s", me,
-                vi_family_name(ctx->vi_family), vi_family_name(family));
+                kViFamilies[ctx->vi_family].name, f->name);
   if (ctx->vi_K != K)
     return fail(ctx, MIMO_E_STATE, "%s: the resident prior block is that of K = %d, not K = %d", me, ctx->vi_K, K);
   return MIMO_OK;
 }
 
-static ViArgs vi_args(mimo_ctx* ctx, int K) {
-  const size_t B = (size_t)ctx->batch_B, BK = B * K, D = (size_t)ctx->D;
-  ViArgs a{};
-  a.S = ctx->S_d;
-  a.scalars = ctx->S_d + batch_stats_len(ctx, K);
-  const double* p = ctx->vi_prior;
-  a.alpha0 = p; p += BK;
-  a.pa = p; p += BK * D;
-  a.pb = p; p += BK;
-  a.pc = p; p += BK * D * D;
-  a.pd = p; p += BK;
-  a.plz = p;
-  a.post = ctx->vi_post;
-  a.term = ctx->vi_work;
-  a.prior_terms = ctx->vi_work + BK;
-  a.last = ctx->vi_work + BK + B;
-  a.words = reinterpret_cast<int32_t*>(ctx->vi_loop.p);
-  a.theta = ctx->vi_theta;
-  a.trace = ctx->vi_loop + vi_words_len(ctx->batch_B);
-  a.B = ctx->batch_B; a.K = K; a.D = ctx->D; a.K16 = (K + 15) / 16; a.NS = ctx->F16 / 4;
-  a.tol = 0.0;
-  return a;
+// What the pass, its reduction, the finish and the family's step read: the conjugate mode, tol = 0
+static ViLoop vi_loop_args(mimo_ctx* ctx, int K, const ViFamily& f) {
+  const size_t B = (size_t)ctx->batch_B;
+  ViLoop l{};
+  l.S = ctx->S_d;
+  l.scalars = ctx->S_d + batch_stats_len(ctx, K);
+  l.post = ctx->vi_post;
+  l.prior_terms = ctx->vi_work + vi_work_len(ctx, K, f) - 2 * B;
+  l.last = l.prior_terms + B;
+  l.words = reinterpret_cast<int32_t*>(ctx->vi_loop.p);
+  l.theta = ctx->vi_theta;
+  l.trace = ctx->vi_loop + vi_words_len(ctx->batch_B);
+  l.B = ctx->batch_B; l.K = K; l.D = ctx->D; l.K16 = (K + 15) / 16; l.NS = ctx->F16 / 4;
+  return l;
 }
 
-int mimo_vi_prior_batched(mimo_ctx* ctx, int K, const double* alpha0, const double* pa, const double* pb, const double* pc,
-                          const double* pd, const double* prior_logZ) {
-  return guarded(ctx, [&]() -> int {
-  const char* const me = "mimo_vi_prior_batched";
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, me))) return rc;
-  if (!alpha0 || !pa || !pb || !pc || !pd || !prior_logZ)
-    return fail(ctx, MIMO_E_INVALID, "%s: alpha0, pa, pb, pc, pd and prior_logZ must be non-NULL", me);
-  const size_t B = (size_t)ctx->batch_B, BK = B * K, D = (size_t)ctx->D;
-  const double* const parts[6] = {alpha0, pa, pb, pc, pd, prior_logZ};
-  const char* const names[6] = {"alpha0", "pa", "pb", "pc", "pd", "prior_logZ"};
-  const size_t lens[6] = {BK, BK * D, BK, BK * D * D, BK, BK};
-  for (int t = 0; t < 6; ++t)
-    for (size_t i = 0; i < lens[t]; ++i)
-      if (!std::isfinite(parts[t][i]))
-        return fail(ctx, MIMO_E_INVALID, "%s: %s of problem %d holds a NaN or an infinity", me, names[t], (int)(i / (lens[t] / B)));
+// One part of a prior block or of an uploaded posterior: `len` doubles per problem (at `at` of the family's posterior block)
+struct ViPart { const char* name; const double* src; size_t len; size_t at; };
+
+static int vi_parts_finite(mimo_ctx* ctx, const ViPart* parts, int nparts, const char* me) {
+  const size_t B = (size_t)ctx->batch_B;
+  for (int t = 0; t < nparts; ++t)
+    for (size_t i = 0; i < parts[t].len * B; ++i)
+      if (!std::isfinite(parts[t].src[i]))
+        return fail(ctx, MIMO_E_INVALID, "%s: %s of problem %d holds a NaN or an infinity", me, parts[t].name, (int)(i / parts[t].len));
+  return MIMO_OK;
+}
+
+// The loop state of a new prior block or a new starting posterior: every problem active, nothing appended, status clear, slot 0
+// current; slot 0 of every problem from `slot0` (host, alive up to the caller's wait; null: zeros), slot 1 zero; zero work, zero
+// images (the entries no kernel writes — padded features, the b / W entries of padding components — are the zeros pack_theta
+// leaves there)
+static int vi_reset_loop(mimo_ctx* ctx, int K, const ViFamily& f, const double* slot0) {
+  const size_t B = (size_t)ctx->batch_B, half = B * f.post_len(ctx, K);
+  static_assert(kViActive == 0, "the words' first row is set to 1 below");
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_loop, 0, (size_t)kViWords * B * sizeof(int32_t), ctx->stream));
+  HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctx->vi_loop.p), 1, B, ctx->stream));
+  if (slot0) HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_post, slot0, half * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_post + (slot0 ? half : 0), 0, (slot0 ? 1 : 2) * half * sizeof(double), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_work, 0, vi_work_len(ctx, K, f) * sizeof(double), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_theta, 0, image_len(ctx, K) * sizeof(double), ctx->stream));
+  return MIMO_OK;
+}
+
+// What the two prior calls share behind their own argument checks: the parts, checked finite, into vi_prior in their order, room
+// for the loop and its reset.  (dx, dy, gating: of the linear-Gaussian experts; they size that family's posterior block.)
+static int vi_install_prior(mimo_ctx* ctx, int K, const ViFamily& f, const ViPart* parts, int nparts, int dx, int dy, int gating,
+                            const char* me) {
+  const size_t B = (size_t)ctx->batch_B;
+  int rc;
+  if ((rc = vi_parts_finite(ctx, parts, nparts, me))) return rc;
   ctx->vi_prior_valid = false;
   ctx->svi_state_valid = false;
-  const ViLayout L{K, ctx->D};
-  const size_t nprior = BK * (4 + D + D * D), npost = 2 * B * (size_t)L.count(), nwork = BK + 2 * B;
-  const size_t ntheta = image_len(ctx, K), nwords = vi_words_len(ctx->batch_B);
+  ctx->vi_dx = dx; ctx->vi_dy = dy; ctx->vi_gating = gating;
+  size_t nprior = 0;
+  for (int t = 0; t < nparts; ++t) nprior += B * parts[t].len;
   if ((rc = ctx->vi_prior.ensure(ctx, nprior))) return rc;
-  if ((rc = ctx->vi_post.ensure(ctx, npost))) return rc;
-  if ((rc = ctx->vi_work.ensure(ctx, nwork))) return rc;
-  if ((rc = ctx->vi_theta.ensure(ctx, ntheta))) return rc;
-  if ((rc = ctx->vi_loop.ensure(ctx, nwords))) return rc;
-  // the loop state: every problem active, nothing appended, status clear, slot 0 current; zero blocks, zero images (the entries no
-  // kernel writes — padded features, the b / W entries of padding components — are the zeros pack_theta leaves there)
-  std::vector<int32_t> words((size_t)kViWords * B, 0);
-  std::fill(words.begin() + (size_t)kViActive * B, words.begin() + (size_t)(kViActive + 1) * B, 1);
+  if ((rc = ctx->vi_post.ensure(ctx, 2 * B * f.post_len(ctx, K)))) return rc;
+  if ((rc = ctx->vi_work.ensure(ctx, vi_work_len(ctx, K, f)))) return rc;
+  if ((rc = ctx->vi_theta.ensure(ctx, image_len(ctx, K)))) return rc;
+  if ((rc = ctx->vi_loop.ensure(ctx, vi_words_len(ctx->batch_B)))) return rc;
   double* q = ctx->vi_prior;
-  for (int t = 0; t < 6; ++t) {
-    HIP_TRY(ctx, hipMemcpyAsync(q, parts[t], lens[t] * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    q += lens[t];
+  for (int t = 0; t < nparts; ++t) {
+    HIP_TRY(ctx, hipMemcpyAsync(q, parts[t].src, B * parts[t].len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    q += B * parts[t].len;
   }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_loop, words.data(), words.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_post, 0, npost * sizeof(double), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_work, 0, nwork * sizeof(double), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_theta, 0, ntheta * sizeof(double), ctx->stream));
+  if ((rc = vi_reset_loop(ctx, K, f, nullptr))) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // the sources are pageable host memory
   ctx->vi_prior_valid = true;
   ctx->vi_K = K;
-  ctx->vi_family = 0;
+  ctx->vi_family = f.id;
   return MIMO_OK;
-  });
 }
-
-static ViIlrArgs vi_ilr_args(mimo_ctx* ctx, int K);
 
 // Room for the loop's words and the trace of a call of `iters` iterations, on the device and in the pinned sibling; *total: their
 // doubles.  A longer trace than any before: the words move to the new block.
@@ -685,9 +729,9 @@ static int vi_loop_out(mimo_ctx* ctx, int iters, size_t total, double* trace, in
   return MIMO_OK;
 }
 
-// The loop of both families: `family` chooses the update and the gating kernel; the pass, its reduction and the finish are shared
+// The loop of both families: the family's update and gating kernel; the pass, its reduction and the finish are shared
 static int vi_run(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status,
-                  const char* me, int family) {
+                  const char* me, const ViFamily& f) {
   return guarded(ctx, [&]() -> int {
   int rc = bind(ctx); if (rc) return rc;
   if ((rc = batched_ready(ctx, K, me))) return rc;
@@ -695,7 +739,7 @@ static int vi_run(mimo_ctx* ctx, int K, int iters, double tol, int flags, double
   if (iters < 1 || iters > 65536) return fail(ctx, MIMO_E_INVALID, "%s: iters = %d outside [1, 65536]", me, iters);
   if (!(tol >= 0.0)) return fail(ctx, MIMO_E_INVALID, "%s: tol = %g must be >= 0", me, tol);
   if (!trace || !n_done || !status) return fail(ctx, MIMO_E_INVALID, "%s: trace, n_done and status must be non-NULL", me);
-  if ((rc = vi_ready(ctx, K, me, family))) return rc;
+  if ((rc = vi_ready(ctx, K, me, &f))) return rc;
   if (!ctx->batch_stats_valid || !ctx->S_d)
     return fail(ctx, MIMO_E_STATE, "%s: no statistics are resident (run a batched pass that returns statistics first; an upload and "
                 "every call that returns something else drop them)", me);
@@ -707,45 +751,29 @@ static int vi_run(mimo_ctx* ctx, int K, int iters, double tol, int flags, double
   if ((rc = ensure_partials(ctx, K, (size_t)G))) return rc;
   leaves(ctx, kPassTables, 0);
 
-  ViIlrArgs ia{};
-  if (family == 1) {
-    ia = vi_ilr_args(ctx, K);
-    ia.loop.tol = tol;
-  }
-  ViArgs va = family == 1 ? ia.loop : vi_args(ctx, K);
-  va.tol = tol;
+  ViLoop l = vi_loop_args(ctx, K, f);
+  l.tol = tol;
   BatchedArgs a = batched_args(ctx, K);
   a.theta = ctx->vi_theta;
-  HIP_TRY(ctx, hipMemsetAsync(va.words + (size_t)kViDone * B, 0, (size_t)B * sizeof(int32_t), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(l.words + (size_t)kViDone * B, 0, (size_t)B * sizeof(int32_t), ctx->stream));
   for (int it = 0; it < iters; ++it) {
-    if (family == 1) {
-      HIP_TRY(ctx, launch_vi_ilr_update(ia, ctx->stream));
-      HIP_TRY(ctx, launch_vi_ilr_gating(ia, ctx->stream));
-    } else {
-      HIP_TRY(ctx, launch_vi_update(va, ctx->stream));
-      HIP_TRY(ctx, launch_vi_gating(va, ctx->stream));
-    }
+    if ((rc = f.step(ctx, l))) return rc;
     HIP_TRY(ctx, launch_batched(a, G, ctx->stream));
     if ((rc = batched_reduce(ctx, K, ctx->batch_wg_off_d, 0, true))) return rc;
-    HIP_TRY(ctx, launch_vi_finish(va, it, ctx->stream));
+    HIP_TRY(ctx, launch_vi_finish(l, it, ctx->stream));
   }
   return vi_loop_out(ctx, iters, total, trace, n_done, status);
   });
 }
 
-int mimo_vi_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status) {
-  return vi_run(ctx, K, iters, tol, flags, trace, n_done, status, "mimo_vi_run_batched", 0);
-}
-
-// Every problem's current posterior block (of `per` doubles in the family's layout) to the host
-static int vi_get(mimo_ctx* ctx, int K, double* out, const char* me, int family) {
+// Every problem's current posterior block (in the family's layout) to the host
+static int vi_get(mimo_ctx* ctx, int K, double* out, const char* me, const ViFamily& f) {
   return guarded(ctx, [&]() -> int {
   int rc = bind(ctx); if (rc) return rc;
   if ((rc = batched_ready(ctx, K, me))) return rc;
   if (!out) return fail(ctx, MIMO_E_INVALID, "%s: out is NULL", me);
-  if ((rc = vi_ready(ctx, K, me, family))) return rc;
-  const size_t B = (size_t)ctx->batch_B;
-  const size_t per = family == 1 ? (size_t)ViIlrLayout{K, ctx->vi_dx, ctx->vi_dy}.count() : (size_t)ViLayout{K, ctx->D}.count();
+  if ((rc = vi_ready(ctx, K, me, &f))) return rc;
+  const size_t B = (size_t)ctx->batch_B, per = f.post_len(ctx, K);
   std::vector<double> both(2 * B * per);
   std::vector<int32_t> words((size_t)kViWords * B);
   HIP_TRY(ctx, hipMemcpyAsync(both.data(), ctx->vi_post, both.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -759,7 +787,150 @@ static int vi_get(mimo_ctx* ctx, int K, double* out, const char* me, int family)
   });
 }
 
-int mimo_vi_get_batched(mimo_ctx* ctx, int K, double* out) { return vi_get(ctx, K, out, "mimo_vi_get_batched", 0); }
+// What mimo_svi_state_batched and mimo_svi_ilr_state_batched share behind batched_ready and vi_ready: the parts, checked finite,
+// into slot 0 of a loop that is reset as the prior call resets it; then the init mode of the family's update and gating kernel,
+// and the status words back.
+static int svi_state(mimo_ctx* ctx, int K, const ViPart* parts, int nparts, int32_t* status, const char* me, const ViFamily& f) {
+  const size_t B = (size_t)ctx->batch_B, per = f.post_len(ctx, K);
+  int rc;
+  for (int t = 0; t < nparts; ++t)
+    if (!parts[t].src) return fail(ctx, MIMO_E_INVALID, "%s: %s is NULL", me, parts[t].name);
+  if (!status) return fail(ctx, MIMO_E_INVALID, "%s: status is NULL", me);
+  if ((rc = vi_parts_finite(ctx, parts, nparts, me))) return rc;
+  ctx->svi_state_valid = false;
+  std::vector<double> block(B * per, 0.0);
+  for (int t = 0; t < nparts; ++t)
+    for (size_t p = 0; p < B; ++p)
+      memcpy(&block[p * per + parts[t].at], parts[t].src + p * parts[t].len, parts[t].len * sizeof(double));
+  if ((rc = vi_reset_loop(ctx, K, f, block.data()))) return rc;
+  ViLoop l = vi_loop_args(ctx, K, f);
+  l.mode = kViInit;
+  if ((rc = f.step(ctx, l))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(status, l.words + (size_t)kViStatus * B, B * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the sources are pageable host memory)
+  ctx->svi_state_valid = true;
+  ctx->svi_t = 0;
+  return MIMO_OK;
+}
+
+// The SVI loop of both families (as vi_run is): per iteration the selection pass and its reduction (the statistics of the
+// minibatch), the blend update and the blend gating, a plain pass over all rows without statistics, its scalar reduction, and the
+// finish with tol = 0.  sel_off is the same for every iteration: one work table per call.
+static int svi_run(mimo_ctx* ctx, int K, int iters, double step_size, const double* scale, const int64_t* rows,
+                   const int64_t* sel_off, const uint64_t* seeds, int flags, double* trace, int32_t* n_done, int32_t* status,
+                   const char* me, const ViFamily& f) {
+  return guarded(ctx, [&]() -> int {
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, me))) return rc;
+  if (flags & ~MIMO_F_SVI_RESIDENT_START)
+    return fail(ctx, MIMO_E_INVALID, "%s: flags 0x%x: only MIMO_F_SVI_RESIDENT_START", me, flags);
+  if (iters < 1 || iters > 65536) return fail(ctx, MIMO_E_INVALID, "%s: iters = %d outside [1, 65536]", me, iters);
+  if (!(step_size > 0.0 && step_size <= 1.0)) return fail(ctx, MIMO_E_INVALID, "%s: step_size = %g outside (0, 1]", me, step_size);
+  if (!scale || !sel_off || !trace || !n_done || !status)
+    return fail(ctx, MIMO_E_INVALID, "%s: scale, sel_off, trace, n_done and status must be non-NULL", me);
+  const int B = ctx->batch_B, G = ctx->batch_G;
+  for (int p = 0; p < B; ++p)
+    if (!(std::isfinite(scale[p]) && scale[p] > 0.0))      // (above 1: a minibatch drawn with replacement, larger than its data set)
+      return fail(ctx, MIMO_E_INVALID, "%s: scale[%d] = %g must be finite and > 0", me, p, scale[p]);
+  if ((rc = vi_ready(ctx, K, me, &f))) return rc;
+  if (!ctx->svi_state_valid)
+    return fail(ctx, MIMO_E_STATE, "%s: no starting posterior is resident (call %s after the prior block; an upload and a new prior "
+                "block drop it)", me, f.state_call);
+  if ((rc = check_offsets(ctx, sel_off, B, me, "sel_off"))) return rc;
+  const bool resident_start = (flags & MIMO_F_SVI_RESIDENT_START) != 0;
+  if (resident_start && (!ctx->batch_stats_valid || ctx->batch_stats_K != K || !ctx->S_d))
+    return fail(ctx, MIMO_E_STATE, "%s: MIMO_F_SVI_RESIDENT_START and no statistics of K = %d are resident (run a batched pass that "
+                "returns statistics first)", me, K);
+  const int n_sel = iters - (resident_start ? 1 : 0), first = resident_start ? 1 : 0;
+  const int64_t per_it = sel_off[B];
+  if (n_sel > 0 && per_it > 0 && !rows && !seeds)
+    return fail(ctx, MIMO_E_INVALID, "%s: rows and seeds are both NULL (give the indices or one Philox seed per problem)", me);
+  // the selection pass gathers through the indices unchecked: every one of every iteration is checked here, before anything is
+  // enqueued; the index kernel's own stay below N_b by construction, given a row to draw
+  SelectionBad bad;
+  if (rows && !selection_indices_ok(rows, n_sel, sel_off, ctx->batch_rows.data(), B, &bad))
+    return fail(ctx, MIMO_E_INVALID, "%s: iteration %d, problem %d: index %lld (entry %lld of its selection) outside [0, %lld)", me,
+                bad.sel + first, bad.prob, (long long)bad.index, (long long)bad.entry, (long long)bad.rows);
+  for (int p = 0; !rows && n_sel > 0 && p < B; ++p)
+    if (sel_off[p + 1] > sel_off[p] && ctx->batch_rows[(size_t)p + 1] - ctx->batch_rows[(size_t)p] < 1)
+      return fail(ctx, MIMO_E_INVALID, "%s: problem %d has no rows to draw its %lld indices from", me, p,
+                  (long long)(sel_off[p + 1] - sel_off[p]));
+  SelectionTables tables;
+  if (!tables.build(sel_off, B, batched_tiles_per_wg, seeds, scale)) return fail(ctx, MIMO_E_INVALID, "%s: too many rows", me);
+  const size_t Gs = tables.G;
+  size_t total = 0;
+  if ((rc = vi_loop_room(ctx, iters, &total))) return rc;
+  if ((rc = ensure_partials(ctx, K, std::max(Gs, (size_t)G)))) return rc;
+  if (!resident_start && (rc = ensure_block(ctx, batch_stats_len(ctx, K) + 3 * (size_t)B))) return rc;
+  if ((rc = ctx->svi_tables.ensure(ctx, tables.words.size()))) return rc;
+  if ((rc = ctx->svi_sel.ensure(ctx, (size_t)std::max(n_sel, 0) * (size_t)per_it))) return rc;
+  leaves(ctx, kPassTables, 0);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->svi_tables, tables.words.data(), tables.words.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
+                              ctx->stream));
+  const uint64_t* const tables_d = ctx->svi_tables;
+  const int64_t* const sel_off_d = reinterpret_cast<const int64_t*>(tables_d);
+  const int32_t* const wg_off_d = reinterpret_cast<const int32_t*>(tables_d + tables.at_wg);
+  if (n_sel > 0 && per_it > 0) {
+    if (rows) {
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->svi_sel, rows, (size_t)n_sel * (size_t)per_it * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    } else {
+      for (int s = 0; s < n_sel; s += 65535)      // (a grid's second dimension)
+        HIP_TRY(ctx, launch_svi_indices(ctx->svi_sel + (size_t)s * (size_t)per_it, sel_off_d, ctx->batch_row_off_d,
+                                        tables_d + tables.at_seeds, B, std::min(n_sel - s, 65535), per_it,
+                                        ctx->svi_t + (uint64_t)(first + s), ctx->stream));
+    }
+  }
+
+  ViLoop l = vi_loop_args(ctx, K, f);         // (tol = 0: SVI has no stopping rule)
+  l.mode = kViBlend;
+  l.rho = step_size;
+  l.one_minus_rho = 1.0 - step_size;
+  l.inv_scale = reinterpret_cast<const double*>(tables_d + tables.at_inv);
+  BatchedArgs sel_a = batched_args(ctx, K), full_a = batched_args(ctx, K);
+  sel_a.theta = full_a.theta = ctx->vi_theta;
+  sel_a.sel_off = sel_off_d;
+  sel_a.work = reinterpret_cast<const BatchedWork*>(tables_d + tables.at_work);
+  full_a.do_stats = 0;
+  HIP_TRY(ctx, hipMemsetAsync(l.words + (size_t)kViDone * B, 0, (size_t)B * sizeof(int32_t), ctx->stream));
+  for (int it = 0; it < iters; ++it) {
+    if (it >= first) {
+      sel_a.sel = ctx->svi_sel + (size_t)(it - first) * (size_t)per_it;
+      if (Gs) HIP_TRY(ctx, launch_batched_rows(sel_a, (int)Gs, ctx->stream));      // (no slots at all: the reduction leaves zeros)
+      if ((rc = batched_reduce(ctx, K, wg_off_d, 0, true))) return rc;
+    }
+    if ((rc = f.step(ctx, l))) return rc;
+    // the bound's pass: all rows, no statistics — the minibatch's stay resident, the scalars go behind them as always
+    HIP_TRY(ctx, launch_batched(full_a, G, ctx->stream));
+    if ((rc = batched_reduce_scalars(ctx, K, ctx->batch_wg_off_d, 0))) return rc;
+    HIP_TRY(ctx, launch_vi_finish(l, it, ctx->stream));
+  }
+  ctx->svi_t += (uint64_t)iters;
+  return vi_loop_out(ctx, iters, total, trace, n_done, status);      // (tables and rows are host memory: alive up to this wait)
+  });
+}
+
+extern "C" {
+
+int mimo_vi_prior_batched(mimo_ctx* ctx, int K, const double* alpha0, const double* pa, const double* pb, const double* pc,
+                          const double* pd, const double* prior_logZ) {
+  return guarded(ctx, [&]() -> int {
+  const char* const me = "mimo_vi_prior_batched";
+  int rc = bind(ctx); if (rc) return rc;
+  if ((rc = batched_ready(ctx, K, me))) return rc;
+  if (!alpha0 || !pa || !pb || !pc || !pd || !prior_logZ)
+    return fail(ctx, MIMO_E_INVALID, "%s: alpha0, pa, pb, pc, pd and prior_logZ must be non-NULL", me);
+  const size_t k = (size_t)K, D = (size_t)ctx->D;
+  const ViPart parts[6] = {{"alpha0", alpha0, k, 0}, {"pa", pa, k * D, 0}, {"pb", pb, k, 0}, {"pc", pc, k * D * D, 0},
+                           {"pd", pd, k, 0}, {"prior_logZ", prior_logZ, k, 0}};
+  return vi_install_prior(ctx, K, kViFamilies[kViGmm], parts, 6, 0, 0, 0, me);
+  });
+}
+
+int mimo_vi_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status) {
+  return vi_run(ctx, K, iters, tol, flags, trace, n_done, status, "mimo_vi_run_batched", kViFamilies[kViGmm]);
+}
+
+int mimo_vi_get_batched(mimo_ctx* ctx, int K, double* out) { return vi_get(ctx, K, out, "mimo_vi_get_batched", kViFamilies[kViGmm]); }
 
 int mimo_vi_get_theta_batched(mimo_ctx* ctx, int K, double* theta, double* stats) {
   return guarded(ctx, [&]() -> int {
@@ -767,7 +938,7 @@ int mimo_vi_get_theta_batched(mimo_ctx* ctx, int K, double* theta, double* stats
   int rc = bind(ctx); if (rc) return rc;
   if ((rc = batched_ready(ctx, K, me))) return rc;
   if (!theta && !stats) return fail(ctx, MIMO_E_INVALID, "%s: theta and stats are both NULL", me);
-  if ((rc = vi_ready(ctx, K, me, -1))) return rc;
+  if ((rc = vi_ready(ctx, K, me, nullptr))) return rc;
   if (stats && (!ctx->batch_stats_valid || ctx->batch_stats_K != K || !ctx->S_d))
     return fail(ctx, MIMO_E_STATE, "%s: no statistics of K = %d are resident", me, K);
   const size_t B = (size_t)ctx->batch_B;
@@ -777,50 +948,6 @@ int mimo_vi_get_theta_batched(mimo_ctx* ctx, int K, double* theta, double* stats
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MIMO_OK;
   });
-}
-
-// ------------------------------------------------------------------------------------------
-// Device-resident batched VI for mixtures of linear-Gaussian experts (mimo_vi_ilr_batched.hip)
-// ------------------------------------------------------------------------------------------
-// The loop lives in the buffers of the GMM loop (one family is resident at a time: vi_family):
-//   vi_prior  [g0 B K | g1 B K | basis pa B K dx | pb B K | pc B K dx^2 | pd B K | log Z B K |
-//              experts ma B K dy dc | mb B K dc^2 | mc B K dy^2 | md B K | log Z B K]
-//   vi_post   [2][B][ViIlrLayout::count()]
-//   vi_work   [basis terms B K | expert terms B K | prior terms B | last bound B]
-static ViIlrArgs vi_ilr_args(mimo_ctx* ctx, int K) {
-  const size_t B = (size_t)ctx->batch_B, BK = B * K;
-  const size_t dx = (size_t)ctx->vi_dx, dy = (size_t)ctx->vi_dy, dc = dx + 1;
-  ViIlrArgs a{};
-  const double* p = ctx->vi_prior;
-  a.g0 = p; p += BK;
-  a.g1 = p; p += BK;
-  a.pa = p; p += BK * dx;
-  a.pb = p; p += BK;
-  a.pc = p; p += BK * dx * dx;
-  a.pd = p; p += BK;
-  a.plz = p; p += BK;
-  a.ma = p; p += BK * dy * dc;
-  a.mb = p; p += BK * dc * dc;
-  a.mc = p; p += BK * dy * dy;
-  a.md = p; p += BK;
-  a.mlz = p;
-  a.term_b = ctx->vi_work;
-  a.term_m = ctx->vi_work + BK;
-  a.dx = ctx->vi_dx; a.dy = ctx->vi_dy; a.gating = ctx->vi_gating;
-  ViArgs& l = a.loop;
-  l.S = ctx->S_d;
-  l.scalars = ctx->S_d + batch_stats_len(ctx, K);
-  l.alpha0 = a.g0; l.pa = a.pa; l.pb = a.pb; l.pc = a.pc; l.pd = a.pd; l.plz = a.plz;      // (vi_finish_kernel reads none of them)
-  l.post = ctx->vi_post;
-  l.term = a.term_b;
-  l.prior_terms = ctx->vi_work + 2 * BK;
-  l.last = ctx->vi_work + 2 * BK + B;
-  l.words = reinterpret_cast<int32_t*>(ctx->vi_loop.p);
-  l.theta = ctx->vi_theta;
-  l.trace = ctx->vi_loop + vi_words_len(ctx->batch_B);
-  l.B = ctx->batch_B; l.K = K; l.D = ctx->D; l.K16 = (K + 15) / 16; l.NS = ctx->F16 / 4;
-  l.tol = 0.0;
-  return a;
 }
 
 int mimo_vi_ilr_prior_batched(mimo_ctx* ctx, int K, int dx, int dy, int gating_kind, const double* g0, const double* g1,
@@ -839,251 +966,39 @@ int mimo_vi_ilr_prior_batched(mimo_ctx* ctx, int K, int dx, int dy, int gating_k
   if (!g0 || (stick && !g1) || !pa || !pb || !pc || !pd || !basis_logZ || !ma || !mb || !mc || !md || !experts_logZ)
     return fail(ctx, MIMO_E_INVALID, "%s: g0, (stick-breaking: g1,) the basis' pa, pb, pc, pd, basis_logZ and the experts' ma, mb, mc, "
                 "md, experts_logZ must be non-NULL", me);
-  const size_t B = (size_t)ctx->batch_B, BK = B * K, sx = (size_t)dx, sy = (size_t)dy, sc = sx + 1;
-  const std::vector<double> zeros(stick ? 0 : BK, 0.0);
-  const double* const parts[12] = {g0, stick ? g1 : zeros.data(), pa, pb, pc, pd, basis_logZ, ma, mb, mc, md, experts_logZ};
-  const char* const names[12] = {"g0", "g1", "pa", "pb", "pc", "pd", "basis_logZ", "ma", "mb", "mc", "md", "experts_logZ"};
-  const size_t lens[12] = {BK, BK, BK * sx, BK, BK * sx * sx, BK, BK, BK * sy * sc, BK * sc * sc, BK * sy * sy, BK, BK};
-  size_t nprior = 0;
-  for (int t = 0; t < 12; ++t) {
-    nprior += lens[t];
-    for (size_t i = 0; i < lens[t]; ++i)
-      if (!std::isfinite(parts[t][i]))
-        return fail(ctx, MIMO_E_INVALID, "%s: %s of problem %d holds a NaN or an infinity", me, names[t], (int)(i / (lens[t] / B)));
-  }
-  ctx->vi_prior_valid = false;
-  ctx->svi_state_valid = false;
-  const ViIlrLayout L{K, dx, dy};
-  const size_t npost = 2 * B * (size_t)L.count(), nwork = 2 * BK + 2 * B;
-  const size_t ntheta = image_len(ctx, K), nwords = vi_words_len(ctx->batch_B);
-  if ((rc = ctx->vi_prior.ensure(ctx, nprior))) return rc;
-  if ((rc = ctx->vi_post.ensure(ctx, npost))) return rc;
-  if ((rc = ctx->vi_work.ensure(ctx, nwork))) return rc;
-  if ((rc = ctx->vi_theta.ensure(ctx, ntheta))) return rc;
-  if ((rc = ctx->vi_loop.ensure(ctx, nwords))) return rc;
-  // the loop state of mimo_vi_prior_batched: every problem active, nothing appended, status clear, slot 0 current; zero blocks,
-  // zero images
-  std::vector<int32_t> words((size_t)kViWords * B, 0);
-  std::fill(words.begin() + (size_t)kViActive * B, words.begin() + (size_t)(kViActive + 1) * B, 1);
-  double* q = ctx->vi_prior;
-  for (int t = 0; t < 12; ++t) {
-    HIP_TRY(ctx, hipMemcpyAsync(q, parts[t], lens[t] * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    q += lens[t];
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_loop, words.data(), words.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_post, 0, npost * sizeof(double), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_work, 0, nwork * sizeof(double), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_theta, 0, ntheta * sizeof(double), ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // the sources are pageable host memory
-  ctx->vi_prior_valid = true;
-  ctx->vi_K = K;
-  ctx->vi_family = 1;
-  ctx->vi_dx = dx; ctx->vi_dy = dy; ctx->vi_gating = stick ? kViGatingStick : kViGatingDirichlet;
-  return MIMO_OK;
+  const size_t k = (size_t)K, sx = (size_t)dx, sy = (size_t)dy, sc = sx + 1;
+  const std::vector<double> zeros(stick ? 0 : (size_t)ctx->batch_B * k, 0.0);      // (a Dirichlet gating has no second part)
+  const ViPart parts[12] = {{"g0", g0, k, 0}, {"g1", stick ? g1 : zeros.data(), k, 0},
+                            {"pa", pa, k * sx, 0}, {"pb", pb, k, 0}, {"pc", pc, k * sx * sx, 0}, {"pd", pd, k, 0},
+                            {"basis_logZ", basis_logZ, k, 0},
+                            {"ma", ma, k * sy * sc, 0}, {"mb", mb, k * sc * sc, 0}, {"mc", mc, k * sy * sy, 0}, {"md", md, k, 0},
+                            {"experts_logZ", experts_logZ, k, 0}};
+  return vi_install_prior(ctx, K, kViFamilies[kViIlr], parts, 12, dx, dy, stick ? kViGatingStick : kViGatingDirichlet, me);
   });
 }
 
 int mimo_vi_ilr_run_batched(mimo_ctx* ctx, int K, int iters, double tol, int flags, double* trace, int32_t* n_done, int32_t* status) {
-  return vi_run(ctx, K, iters, tol, flags, trace, n_done, status, "mimo_vi_ilr_run_batched", 1);
+  return vi_run(ctx, K, iters, tol, flags, trace, n_done, status, "mimo_vi_ilr_run_batched", kViFamilies[kViIlr]);
 }
 
-int mimo_vi_ilr_get_batched(mimo_ctx* ctx, int K, double* out) { return vi_get(ctx, K, out, "mimo_vi_ilr_get_batched", 1); }
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// Device-resident batched SVI (the blend and init modes of mimo_vi_batched.hip / mimo_vi_ilr_batched.hip, svi_indices_kernel)
-// ------------------------------------------------------------------------------------------
-// The loop lives in the buffers of the VI loop of its family; what it adds: svi_sel (the minibatch indices of one call) and
-// svi_tables (the selection's small tables, the Philox seeds and 1 / scale).
-
-// One part of an uploaded posterior: `len` doubles per problem, at `at` of the family's posterior block
-struct SviPart { const char* name; const double* src; size_t len; size_t at; };
-
-// What mimo_svi_state_batched and mimo_svi_ilr_state_batched share: the parts, checked finite, into slot 0 of a loop that is reset
-// as the prior call resets it; then the init mode of the family's update and gating kernel, and the status words back.
-static int svi_state(mimo_ctx* ctx, int K, const SviPart* parts, int nparts, size_t per, int32_t* status, const char* me,
-                     int family) {
-  const size_t B = (size_t)ctx->batch_B;
-  for (int t = 0; t < nparts; ++t)
-    if (!parts[t].src) return fail(ctx, MIMO_E_INVALID, "%s: %s is NULL", me, parts[t].name);
-  if (!status) return fail(ctx, MIMO_E_INVALID, "%s: status is NULL", me);
-  for (int t = 0; t < nparts; ++t)
-    for (size_t i = 0; i < parts[t].len * B; ++i)
-      if (!std::isfinite(parts[t].src[i]))
-        return fail(ctx, MIMO_E_INVALID, "%s: %s of problem %d holds a NaN or an infinity", me, parts[t].name, (int)(i / parts[t].len));
-  ctx->svi_state_valid = false;
-  std::vector<double> block(B * per, 0.0);
-  for (int t = 0; t < nparts; ++t)
-    for (size_t p = 0; p < B; ++p)
-      memcpy(&block[p * per + parts[t].at], parts[t].src + p * parts[t].len, parts[t].len * sizeof(double));
-  std::vector<int32_t> words((size_t)kViWords * B, 0);
-  std::fill(words.begin() + (size_t)kViActive * B, words.begin() + (size_t)(kViActive + 1) * B, 1);
-  const size_t nwork = (family == 1 ? 2 : 1) * B * K + 2 * B;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_post, block.data(), block.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_post + B * per, 0, B * per * sizeof(double), ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->vi_loop, words.data(), words.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_work, 0, nwork * sizeof(double), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->vi_theta, 0, image_len(ctx, K) * sizeof(double), ctx->stream));
-  if (family == 1) {
-    ViIlrArgs ia = vi_ilr_args(ctx, K);
-    ia.loop.mode = kViInit;
-    HIP_TRY(ctx, launch_vi_ilr_update(ia, ctx->stream));
-    HIP_TRY(ctx, launch_vi_ilr_gating(ia, ctx->stream));
-  } else {
-    ViArgs va = vi_args(ctx, K);
-    va.mode = kViInit;
-    HIP_TRY(ctx, launch_vi_update(va, ctx->stream));
-    HIP_TRY(ctx, launch_vi_gating(va, ctx->stream));
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(words.data(), ctx->vi_loop, words.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the sources are pageable host memory)
-  memcpy(status, words.data() + (size_t)kViStatus * B, B * sizeof(int32_t));
-  ctx->svi_state_valid = true;
-  ctx->svi_t = 0;
-  return MIMO_OK;
+int mimo_vi_ilr_get_batched(mimo_ctx* ctx, int K, double* out) {
+  return vi_get(ctx, K, out, "mimo_vi_ilr_get_batched", kViFamilies[kViIlr]);
 }
-
-// The loop of both families (as vi_run is): per iteration the selection pass and its reduction (the statistics of the
-// minibatch), the blend update and the blend gating, a plain pass over all rows without statistics, its scalar reduction, and the
-// finish with tol = 0.  sel_off is the same for every iteration: one work table per call.
-static int svi_run(mimo_ctx* ctx, int K, int iters, double step_size, const double* scale, const int64_t* rows,
-                   const int64_t* sel_off, const uint64_t* seeds, int flags, double* trace, int32_t* n_done, int32_t* status,
-                   const char* me, int family) {
-  return guarded(ctx, [&]() -> int {
-  int rc = bind(ctx); if (rc) return rc;
-  if ((rc = batched_ready(ctx, K, me))) return rc;
-  if (flags & ~MIMO_F_SVI_RESIDENT_START)
-    return fail(ctx, MIMO_E_INVALID, "%s: flags 0x%x: only MIMO_F_SVI_RESIDENT_START", me, flags);
-  if (iters < 1 || iters > 65536) return fail(ctx, MIMO_E_INVALID, "%s: iters = %d outside [1, 65536]", me, iters);
-  if (!(step_size > 0.0 && step_size <= 1.0)) return fail(ctx, MIMO_E_INVALID, "%s: step_size = %g outside (0, 1]", me, step_size);
-  if (!scale || !sel_off || !trace || !n_done || !status)
-    return fail(ctx, MIMO_E_INVALID, "%s: scale, sel_off, trace, n_done and status must be non-NULL", me);
-  const int B = ctx->batch_B, G = ctx->batch_G;
-  for (int p = 0; p < B; ++p)
-    if (!(std::isfinite(scale[p]) && scale[p] > 0.0))      // (above 1: a minibatch drawn with replacement, larger than its data set)
-      return fail(ctx, MIMO_E_INVALID, "%s: scale[%d] = %g must be finite and > 0", me, p, scale[p]);
-  if ((rc = vi_ready(ctx, K, me, family))) return rc;
-  if (!ctx->svi_state_valid)
-    return fail(ctx, MIMO_E_STATE, "%s: no starting posterior is resident (call %s after the prior block; an upload and a new prior "
-                "block drop it)", me, family == 1 ? "mimo_svi_ilr_state_batched" : "mimo_svi_state_batched");
-  if ((rc = check_offsets(ctx, sel_off, B, me, "sel_off"))) return rc;
-  const bool resident_start = (flags & MIMO_F_SVI_RESIDENT_START) != 0;
-  if (resident_start && (!ctx->batch_stats_valid || ctx->batch_stats_K != K || !ctx->S_d))
-    return fail(ctx, MIMO_E_STATE, "%s: MIMO_F_SVI_RESIDENT_START and no statistics of K = %d are resident (run a batched pass that "
-                "returns statistics first)", me, K);
-  const int n_sel = iters - (resident_start ? 1 : 0), first = resident_start ? 1 : 0;
-  const int64_t per_it = sel_off[B];
-  if (n_sel > 0 && per_it > 0 && !rows && !seeds)
-    return fail(ctx, MIMO_E_INVALID, "%s: rows and seeds are both NULL (give the indices or one Philox seed per problem)", me);
-  // the selection pass gathers through the indices unchecked: every one of every iteration is checked here, before anything is
-  // enqueued; the index kernel's own stay below N_b by construction, given a row to draw
-  for (int p = 0; p < B; ++p) {
-    const int64_t nb = ctx->batch_rows[(size_t)p + 1] - ctx->batch_rows[(size_t)p];
-    if (!rows) {
-      if (n_sel > 0 && sel_off[p + 1] > sel_off[p] && nb < 1)
-        return fail(ctx, MIMO_E_INVALID, "%s: problem %d has no rows to draw its %lld indices from", me, p,
-                    (long long)(sel_off[p + 1] - sel_off[p]));
-      continue;
-    }
-    for (int s = 0; s < n_sel; ++s)
-      for (int64_t i = sel_off[p]; i < sel_off[p + 1]; ++i) {
-        const int64_t r = rows[(int64_t)s * per_it + i];
-        if (r < 0 || r >= nb)
-          return fail(ctx, MIMO_E_INVALID, "%s: iteration %d, problem %d: index %lld (entry %lld of its selection) outside [0, %lld)",
-                      me, s + first, p, (long long)r, (long long)(i - sel_off[p]), (long long)nb);
-      }
-  }
-  std::vector<BatchedWork> work;
-  std::vector<int32_t> wg_off;
-  if ((rc = build_work(ctx, sel_off, B, me, &work, &wg_off))) return rc;
-  // the small tables: [sel_off (B + 1) | work table | wg_off (int32, B + 1, in whole words) | seeds B | 1 / scale B]
-  const size_t Gs = work.size(), at_work = (size_t)B + 1, at_wg = at_work + 2 * Gs, nwg = ((size_t)B + 2) / 2;
-  const size_t at_seeds = at_wg + nwg, at_inv = at_seeds + (size_t)B;
-  std::vector<uint64_t> tables(at_inv + (size_t)B, 0);
-  memcpy(tables.data(), sel_off, ((size_t)B + 1) * sizeof(int64_t));
-  if (Gs) memcpy(tables.data() + at_work, work.data(), Gs * sizeof(BatchedWork));
-  memcpy(tables.data() + at_wg, wg_off.data(), nwg * sizeof(uint64_t));
-  if (seeds) memcpy(tables.data() + at_seeds, seeds, (size_t)B * sizeof(uint64_t));
-  for (int p = 0; p < B; ++p) {
-    const double inv = 1.0 / scale[p];      // (as `1. / scale` of the host step rounds it)
-    memcpy(tables.data() + at_inv + p, &inv, sizeof(double));
-  }
-  size_t total = 0;
-  if ((rc = vi_loop_room(ctx, iters, &total))) return rc;
-  if ((rc = ensure_partials(ctx, K, std::max(Gs, (size_t)G)))) return rc;
-  if (!resident_start && (rc = ensure_block(ctx, batch_stats_len(ctx, K) + 3 * (size_t)B))) return rc;
-  if ((rc = ctx->svi_tables.ensure(ctx, tables.size()))) return rc;
-  if ((rc = ctx->svi_sel.ensure(ctx, (size_t)std::max(n_sel, 0) * (size_t)per_it))) return rc;
-  leaves(ctx, kPassTables, 0);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->svi_tables, tables.data(), tables.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-  const uint64_t* const tables_d = ctx->svi_tables;
-  const int64_t* const sel_off_d = reinterpret_cast<const int64_t*>(tables_d);
-  const int32_t* const wg_off_d = reinterpret_cast<const int32_t*>(tables_d + at_wg);
-  if (n_sel > 0 && per_it > 0) {
-    if (rows) {
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->svi_sel, rows, (size_t)n_sel * (size_t)per_it * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    } else {
-      for (int s = 0; s < n_sel; s += 65535)      // (a grid's second dimension)
-        HIP_TRY(ctx, launch_svi_indices(ctx->svi_sel + (size_t)s * (size_t)per_it, sel_off_d, ctx->batch_row_off_d, tables_d + at_seeds,
-                                        B, std::min(n_sel - s, 65535), per_it, ctx->svi_t + (uint64_t)(first + s), ctx->stream));
-    }
-  }
-
-  ViIlrArgs ia{};
-  if (family == 1) ia = vi_ilr_args(ctx, K);
-  ViArgs& va = ia.loop;
-  if (family != 1) va = vi_args(ctx, K);
-  va.tol = 0.0;                               // SVI has no stopping rule
-  va.mode = kViBlend;
-  va.rho = step_size;
-  va.one_minus_rho = 1.0 - step_size;
-  va.inv_scale = reinterpret_cast<const double*>(tables_d + at_inv);
-  BatchedArgs sel_a = batched_args(ctx, K), full_a = batched_args(ctx, K);
-  sel_a.theta = full_a.theta = ctx->vi_theta;
-  sel_a.sel_off = sel_off_d;
-  sel_a.work = reinterpret_cast<const BatchedWork*>(tables_d + at_work);
-  full_a.do_stats = 0;
-  double* const scalars_d = ctx->S_d + batch_stats_len(ctx, K);
-  HIP_TRY(ctx, hipMemsetAsync(va.words + (size_t)kViDone * B, 0, (size_t)B * sizeof(int32_t), ctx->stream));
-  for (int it = 0; it < iters; ++it) {
-    if (it >= first) {
-      sel_a.sel = ctx->svi_sel + (size_t)(it - first) * (size_t)per_it;
-      if (Gs) HIP_TRY(ctx, launch_batched_rows(sel_a, (int)Gs, ctx->stream));      // (no slots at all: the reduction leaves zeros)
-      if ((rc = batched_reduce(ctx, K, wg_off_d, 0, true))) return rc;
-    }
-    if (family == 1) {
-      HIP_TRY(ctx, launch_vi_ilr_update(ia, ctx->stream));
-      HIP_TRY(ctx, launch_vi_ilr_gating(ia, ctx->stream));
-    } else {
-      HIP_TRY(ctx, launch_vi_update(va, ctx->stream));
-      HIP_TRY(ctx, launch_vi_gating(va, ctx->stream));
-    }
-    // the bound's pass: all rows, no statistics — the minibatch's stay resident, the scalars go behind them as always
-    HIP_TRY(ctx, launch_batched(full_a, G, ctx->stream));
-    HIP_TRY(ctx, launch_batched_reduce(ctx->partials, ctx->batch_wg_off_d, B, ctx->feat_d, K, ctx->D, ctx->F, ctx->F16, 0, nullptr,
-                                       scalars_d, ctx->stream));
-    HIP_TRY(ctx, launch_vi_finish(va, it, ctx->stream));
-  }
-  ctx->svi_t += (uint64_t)iters;
-  return vi_loop_out(ctx, iters, total, trace, n_done, status);      // (tables and rows are host memory: alive up to this wait)
-  });
-}
-
-extern "C" {
 
 int mimo_svi_state_batched(mimo_ctx* ctx, int K, const double* alpha, const double* qa, const double* qb, const double* qc,
                            const double* qd, int32_t* status) {
   return guarded(ctx, [&]() -> int {
   const char* const me = "mimo_svi_state_batched";
+  const ViFamily& f = kViFamilies[kViGmm];
   int rc = bind(ctx); if (rc) return rc;
   if ((rc = batched_ready(ctx, K, me))) return rc;
-  if ((rc = vi_ready(ctx, K, me, 0))) return rc;
+  if ((rc = vi_ready(ctx, K, me, &f))) return rc;
   const ViLayout L{K, ctx->D};
+  const ViNwLayout N = L.nw();
   const size_t k = (size_t)K, D = (size_t)ctx->D;
-  const SviPart parts[5] = {{"alpha", alpha, k, (size_t)L.alpha()}, {"qa", qa, k * D, (size_t)L.qa()}, {"qb", qb, k, (size_t)L.qb()},
-                            {"qc", qc, k * D * D, (size_t)L.qc()}, {"qd", qd, k, (size_t)L.qd()}};
-  return svi_state(ctx, K, parts, 5, (size_t)L.count(), status, me, 0);
+  const ViPart parts[5] = {{"alpha", alpha, k, (size_t)L.alpha()}, {"qa", qa, k * D, (size_t)N.qa()}, {"qb", qb, k, (size_t)N.qb()},
+                           {"qc", qc, k * D * D, (size_t)N.qc()}, {"qd", qd, k, (size_t)N.qd()}};
+  return svi_state(ctx, K, parts, 5, status, me, f);
   });
 }
 
@@ -1092,31 +1007,35 @@ int mimo_svi_ilr_state_batched(mimo_ctx* ctx, int K, const double* g0, const dou
                                const double* md, int32_t* status) {
   return guarded(ctx, [&]() -> int {
   const char* const me = "mimo_svi_ilr_state_batched";
+  const ViFamily& f = kViFamilies[kViIlr];
   int rc = bind(ctx); if (rc) return rc;
   if ((rc = batched_ready(ctx, K, me))) return rc;
-  if ((rc = vi_ready(ctx, K, me, 1))) return rc;
+  if ((rc = vi_ready(ctx, K, me, &f))) return rc;
   const ViIlrLayout L{K, ctx->vi_dx, ctx->vi_dy};
+  const ViNwLayout N = L.basis();
   const size_t k = (size_t)K, dx = (size_t)ctx->vi_dx, dy = (size_t)ctx->vi_dy, dc = dx + 1;
   const bool stick = ctx->vi_gating == kViGatingStick;
   const std::vector<double> zeros(stick ? 0 : (size_t)ctx->batch_B * k, 0.0);      // (a Dirichlet gating has no second part)
-  const SviPart parts[10] = {{"g0", g0, k, (size_t)L.g0()}, {"g1", stick ? g1 : zeros.data(), k, (size_t)L.g1()},
-                             {"qa", qa, k * dx, (size_t)L.b_qa()}, {"qb", qb, k, (size_t)L.b_qb()},
-                             {"qc", qc, k * dx * dx, (size_t)L.b_qc()}, {"qd", qd, k, (size_t)L.b_qd()},
-                             {"ma", ma, k * dy * dc, (size_t)L.m_a()}, {"mKq", mKq, k * dc * dc, (size_t)L.m_Kq()},
-                             {"mc", mc, k * dy * dy, (size_t)L.m_c()}, {"md", md, k, (size_t)L.m_d()}};
-  return svi_state(ctx, K, parts, 10, (size_t)L.count(), status, me, 1);
+  const ViPart parts[10] = {{"g0", g0, k, (size_t)L.g0()}, {"g1", stick ? g1 : zeros.data(), k, (size_t)L.g1()},
+                            {"qa", qa, k * dx, (size_t)N.qa()}, {"qb", qb, k, (size_t)N.qb()},
+                            {"qc", qc, k * dx * dx, (size_t)N.qc()}, {"qd", qd, k, (size_t)N.qd()},
+                            {"ma", ma, k * dy * dc, (size_t)L.m_a()}, {"mKq", mKq, k * dc * dc, (size_t)L.m_Kq()},
+                            {"mc", mc, k * dy * dy, (size_t)L.m_c()}, {"md", md, k, (size_t)L.m_d()}};
+  return svi_state(ctx, K, parts, 10, status, me, f);
   });
 }
 
 int mimo_svi_run_batched(mimo_ctx* ctx, int K, int iters, double step_size, const double* scale, const int64_t* rows,
                          const int64_t* sel_off, const uint64_t* seeds, int flags, double* trace, int32_t* n_done, int32_t* status) {
-  return svi_run(ctx, K, iters, step_size, scale, rows, sel_off, seeds, flags, trace, n_done, status, "mimo_svi_run_batched", 0);
+  return svi_run(ctx, K, iters, step_size, scale, rows, sel_off, seeds, flags, trace, n_done, status, "mimo_svi_run_batched",
+                 kViFamilies[kViGmm]);
 }
 
 int mimo_svi_ilr_run_batched(mimo_ctx* ctx, int K, int iters, double step_size, const double* scale, const int64_t* rows,
                              const int64_t* sel_off, const uint64_t* seeds, int flags, double* trace, int32_t* n_done,
                              int32_t* status) {
-  return svi_run(ctx, K, iters, step_size, scale, rows, sel_off, seeds, flags, trace, n_done, status, "mimo_svi_ilr_run_batched", 1);
+  return svi_run(ctx, K, iters, step_size, scale, rows, sel_off, seeds, flags, trace, n_done, status, "mimo_svi_ilr_run_batched",
+                 kViFamilies[kViIlr]);
 }
 
 }  // extern "C"

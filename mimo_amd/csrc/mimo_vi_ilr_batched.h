@@ -14,7 +14,7 @@ constexpr int kViGatingStick = 1;
 
 // One problem's posterior block.  dc = dx + 1 (affine experts), D = dx + dy.
 //   gating   g0 K (alpha | gamma) | g1 K (zeros | delta) | E[log pi] K
-//   basis    qa K dx | qb K | qc K dx^2 | qd K | mus K dx | psis K dx^2 | nus K | hld K | cc K | bb K dx | W K dx^2 | E2 K | E4 K
+//   basis    the Normal-Wishart parts over dx (ViNwLayout, mimo_vi_batched.h)
 //   experts  a K dy dc | Kq K dc^2 | c K dy^2 | d K | Ms K dy dc | psis K dy^2 | nus K | hld K | Kinv K dc^2 | E1 K dy dc |
 //            E2 K dc^2 | E4 K | cc K | bb K D | W K D^2
 //   joint    c_total K | bb K D | W K D^2
@@ -26,22 +26,9 @@ struct ViIlrLayout {
   __host__ __device__ int g0() const { return 0; }
   __host__ __device__ int g1() const { return K; }
   __host__ __device__ int elp() const { return 2 * K; }
-  // basis
-  __host__ __device__ int b_qa() const { return 3 * K; }
-  __host__ __device__ int b_qb() const { return b_qa() + K * dx; }
-  __host__ __device__ int b_qc() const { return b_qb() + K; }
-  __host__ __device__ int b_qd() const { return b_qc() + K * dx * dx; }
-  __host__ __device__ int b_mus() const { return b_qd() + K; }
-  __host__ __device__ int b_psis() const { return b_mus() + K * dx; }
-  __host__ __device__ int b_nus() const { return b_psis() + K * dx * dx; }
-  __host__ __device__ int b_hld() const { return b_nus() + K; }
-  __host__ __device__ int b_cc() const { return b_hld() + K; }
-  __host__ __device__ int b_bb() const { return b_cc() + K; }
-  __host__ __device__ int b_W() const { return b_bb() + K * dx; }
-  __host__ __device__ int b_E2() const { return b_W() + K * dx * dx; }
-  __host__ __device__ int b_E4() const { return b_E2() + K; }
+  __host__ __device__ ViNwLayout basis() const { return {K, dx, 3 * K}; }
   // experts
-  __host__ __device__ int m_a() const { return b_E4() + K; }
+  __host__ __device__ int m_a() const { return basis().end(); }
   __host__ __device__ int m_Kq() const { return m_a() + K * dy * dc(); }
   __host__ __device__ int m_c() const { return m_Kq() + K * dc() * dc(); }
   __host__ __device__ int m_d() const { return m_c() + K * dy * dy; }
@@ -68,16 +55,13 @@ struct ViIlrLayout {
 //   g0 B K | g1 B K | basis pa B K dx | pb B K | pc B K dx^2 | pd B K | log Z B K |
 //   experts ma B K dy dc | mb B K dc^2 | mc B K dy^2 | md B K | log Z B K
 struct ViIlrArgs {
-  ViArgs loop;                // S, scalars, post ([2][B][ViIlrLayout::count()]), prior_terms, last, words, theta, trace, B, K, D = dx + dy,
-                              // K16, NS, tol: what the pass, its reduction and vi_finish_kernel read (alpha0 / pa .. plz / term are
-                              // set to the blocks below so that the struct is complete)
+  ViLoop loop;                // post: [2][B][ViIlrLayout::count()]; D = dx + dy
   const double* g0;           // [B][K] alpha0 | gamma0
   const double* g1;           // [B][K] unused | delta0
   const double* pa; const double* pb; const double* pc; const double* pd; const double* plz;      // basis
   const double* ma; const double* mb; const double* mc; const double* md; const double* mlz;      // experts
   double* term_b;             // [B][K]: the basis blocks' terms of the bound (update kernel -> gating kernel)
   double* term_m;             // [B][K]: the experts' terms
-  double* cc;                 // [B][K]: c1 + c2 of the joint form (update kernel -> gating kernel)
   int dx, dy, gating;
 };
 

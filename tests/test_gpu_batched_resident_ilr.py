@@ -472,3 +472,63 @@ def test_the_driver_names_the_failing_problem(engine, beng):
     models[2].models.prior._memo['sweep_c64'] = (blk[0], blk[1], blk[2], np.full_like(blk[3], -1e6), blk[4])
     with pytest.raises(FloatingPointError, match="problem 2"):
         meanfield_coordinate_descent_batched_ilr(models, data, **kw)
+
+
+NW_PARTS = ('qa', 'qb', 'qc', 'qd', 'mus', 'psis', 'nus', 'hld', 'cc', 'bb', 'W', 'E2', 'E4')
+
+
+@pytest.mark.parametrize("gating", ['dirichlet', 'stick-breaking'])
+@pytest.mark.parametrize("dx,dy,K", [(1, 1, 128), (1, 15, 17), (15, 1, 5), (8, 4, 33)])
+def test_the_basis_block_is_the_gmm_loops_normal_wishart_block(beng, dx, dy, K, gating):
+    """The ILR loop's basis parts are the GMM loop's Normal-Wishart parts on the x columns, bit for bit, in all three modes: one
+    conjugate iteration, an uploaded posterior (init) and one SVI step on the resident statistics (blend).  Dyadic rows and
+    tables: the statistics of x are exactly the x block of the statistics of z, whatever the order of the sums."""
+    counts = (9, 0, 12)          # (one problem without rows)
+    B = len(counts)
+    _, _, prior = _problems(dx, dy, K, (4, 4, 4), gating, seed=100 * dx + dy)
+    rng = np.random.default_rng(K)
+    rows = [rng.integers(-16, 17, size=(n, dx + dy)) / 8.0 for n in counts]
+    tables = [rng.integers(0, 17, size=(K, n)) / 16.0 for n in counts]
+    pa, pb, pc, pd, plz = prior["basis"]
+    gmm_prior = dict(alpha0=prior["g0"], pa=pa, pb=pb, pc=pc, pd=pd, prior_logZ=plz)
+    half, none = np.full(B, 0.5), np.zeros(B, dtype=np.int64)
+
+    def exact(z):
+        S = beng.weighted_stats(tables)
+        for b, s in enumerate(S):
+            assert np.array_equal(s.n, tables[b].sum(axis=1)) and np.array_equal(s.sx, tables[b] @ z[b]) \
+                and np.array_equal(s.sxx, np.einsum('kn,na,nb->kab', tables[b], z[b], z[b]))
+
+    def ok(out):
+        assert not out[-1].any()
+
+    # mixtures of linear-Gaussian experts over z = [x, y]
+    beng.upload(rows)
+    exact(rows)
+    _set_prior(beng, prior)
+    ok(beng.vi_ilr_run(K, 1, 0.))
+    ilr = [beng.vi_ilr_state(K)]
+    exact(rows)
+    s = ilr[0]
+    assert not beng.svi_ilr_set_state(s['g0'], s['g1'] if gating == 'stick-breaking' else None, tuple(s[n] for n in NW_PARTS[:4]),
+                                      (s['m_a'], s['m_Kq'], s['m_c'], s['m_d'])).any()
+    ilr.append(beng.vi_ilr_state(K))
+    ok(beng.svi_ilr_run(K, 1, 0.5, half, none, rows=[], resident_start=True))
+    ilr.append(beng.vi_ilr_state(K))
+
+    # mixtures of Gaussians over x alone, the basis prior as the components' prior
+    xs = [np.ascontiguousarray(z[:, :dx]) for z in rows]
+    beng.upload(xs)
+    exact(xs)
+    beng.vi_set_prior(**gmm_prior)
+    ok(beng.vi_run(K, 1, 0.))
+    gmm = [beng.vi_state(K)]
+    exact(xs)
+    assert not beng.svi_set_state(gmm[0]['alpha'], *(s[n] for n in NW_PARTS[:4])).any()
+    gmm.append(beng.vi_state(K))
+    ok(beng.svi_run(K, 1, 0.5, half, none, rows=[], resident_start=True))
+    gmm.append(beng.vi_state(K))
+
+    for mode, a, g in zip(('conjugate', 'init', 'blend'), ilr, gmm):
+        for name in NW_PARTS:
+            assert np.array_equal(a[name], g[name]), (mode, name)

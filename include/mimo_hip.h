@@ -727,6 +727,18 @@ int mimo_host_block_order(int K, int D, const double* means, const double* mass,
 int mimo_host_estep_certificate(int K, int D, const double* c0, const double* b0, const double* W0, const double* c, const double* b,
                                 const double* W, double margin, double* out, double* table);
 
+/* The same in two parts, for a reference that serves many passes.  mimo_host_estep_certificate_ref does what depends on the
+ * reference alone (the factors of the W0, the centres, the peaks c^0) and writes it to `ref`, a block of
+ * mimo_host_estep_certificate_ref_size(K, D) doubles (0 for a K or D out of range); mimo_host_estep_certificate_cur takes the block and
+ * the current parameters and writes `out` and `table`.  One after the other they deliver, byte for byte and with the same return
+ * code, what mimo_host_estep_certificate delivers, which is exactly that.  A reference that is refused (MIMO_E_INVALID) still
+ * leaves a block, and the second part refuses it as the one-part function would; the block of another (K, D) is MIMO_E_INVALID.
+ * The second part scans only the current parameters for NaN and infinity: the reference's were scanned when its block was made. */
+size_t mimo_host_estep_certificate_ref_size(int K, int D);
+int mimo_host_estep_certificate_ref(int K, int D, const double* c0, const double* b0, const double* W0, double* ref);
+int mimo_host_estep_certificate_cur(int K, int D, const double* ref, const double* c, const double* b, const double* W, double margin,
+                                    double* out, double* table);
+
 /* K blocks of variates from numpy.random's LEGACY stream (RandomState over MT19937), bit for bit what the reference's
  * per-component calls consume and return: per block k, n_before x normal(), then standard_gamma(shapes[k][i]) for i < n_gamma
  * (chisquare(df) = 2 standard_gamma(df / 2), gamma(a, scale) = scale standard_gamma(a): the caller scales), then n_after x

@@ -79,6 +79,9 @@ SIGNATURES = {
     "mimo_host_gmm_vi_bound": (C.c_int, [C.c_int, C.c_int, C.c_int] + [_vp] * 21),
     "mimo_host_block_order": (C.c_int, [C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
     "mimo_host_estep_certificate": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
+    "mimo_host_estep_certificate_ref_size": (C.c_size_t, [C.c_int, C.c_int]),
+    "mimo_host_estep_certificate_ref": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "mimo_host_estep_certificate_cur": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
     "mimo_host_mnw_vi": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 15),
     "mimo_host_nw_gibbs": (C.c_int, [C.c_int, C.c_int] + [_vp] * 10),
     "mimo_host_digamma": (C.c_double, [C.c_double]),

@@ -175,11 +175,11 @@ static int cert_plan(mimo_ctx* ctx, const KernelArgs& a, const double* c, const 
   memcpy(ctx->cert_prev_part, part, sizeof part);
   ctx->cert_prev_K = K;
   if (ctx->cert_valid && (ctx->cert_K != K || ctx->cert_skip != a.resp_skip || memcmp(part, ctx->cert_part, sizeof part))) ctx->cert_valid = false;
-  const size_t KD = (size_t)K * D, KDD = KD * D;
   if (ctx->cert_valid && ctx->cert_age < kCertRenew) {
     double out[5 * 64 + 4], t[4 + 2 * 64];
-    const double* r = ctx->cert_ref.data();
-    if (mimo_host_estep_certificate(K, D, r, r + K, r + K + KD, c, b, W, -0.6931471805599453 * a.resp_skip - kCertEps, out, t) == MIMO_OK) {
+    // (the reference's side was worked out, and its arrays scanned, when this block was stored below; c, b, W are scanned here: the
+    // Theta packer, which validates them for the pass, runs behind this plan)
+    if (mimo_host_estep_certificate_cur(K, D, ctx->cert_ref.data(), c, b, W, -0.6931471805599453 * a.resp_skip - kCertEps, out, t) == MIMO_OK) {
       memcpy(tab, t, 4 * sizeof(double));
       uint8_t* blk = reinterpret_cast<uint8_t*>(tab + 4 + 128);
       for (int s = 0; s < 64; ++s) {          // by the slot of the REFERENCE pass, which is what the rows' certificates name
@@ -201,10 +201,10 @@ static int cert_plan(mimo_ctx* ctx, const KernelArgs& a, const double* c, const 
     if ((rc = ctx->cert_cnt.ensure(ctx, 4))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(ctx->cert_cnt, 0, 4 * sizeof(unsigned long long), ctx->stream));
   }
-  ctx->cert_ref.resize(K + KD + KDD);
-  memcpy(ctx->cert_ref.data(), c, K * sizeof(double));
-  memcpy(ctx->cert_ref.data() + K, b, KD * sizeof(double));
-  memcpy(ctx->cert_ref.data() + K + KD, W, KDD * sizeof(double));
+  // what the certified passes need of this reference, once: a refused one (MIMO_E_INVALID) leaves a block that says so, and the
+  // first certified pass drops the certificates
+  ctx->cert_ref.resize(mimo_host_estep_certificate_ref_size(K, D));
+  if ((rc = mimo_host_estep_certificate_ref(K, D, c, b, W, ctx->cert_ref.data())) != MIMO_OK && rc != MIMO_E_INVALID) return rc;
   memcpy(ctx->cert_order, ctx->order, K * sizeof(int32_t));
   memcpy(ctx->cert_part, part, sizeof part);
   ctx->cert_K = K; ctx->cert_skip = a.resp_skip; ctx->cert_age = 0;

@@ -113,7 +113,7 @@ struct mimo_ctx {
   bool cert_valid = false;                                // cert_k / cert_m / cert_a hold a reference pass of the resident rows, and:
   int cert_K = 0, cert_skip = 0;                          //   its K and resp_skip_log2
   int cert_age = 0;                                       //   certified passes since
-  std::vector<double> cert_ref;                           //   its parameters [c K | b K D | W K D D]
+  std::vector<double> cert_ref;                           //   what the certificate constants need of its parameters (mimo_host_estep_certificate_ref)
   int32_t cert_order[64] = {0};                           //   its slot order
   uint64_t cert_part[4] = {0, 0, 0, 0};                   //   its partition into row blocks: the blocks' component sets, ascending
   uint64_t cert_prev_part[4] = {0, 0, 0, 0};              // the partition of the last eligible pass, and its K (0: none)

@@ -21,6 +21,7 @@
 #include <stdexcept>
 #include <system_error>
 #include <thread>
+#include <memory>
 #include <vector>
 
 #include "../../include/mimo_hip.h"
@@ -1116,93 +1117,164 @@ int mimo_host_block_order(int K, int D, const double* means, const double* mass,
 // nats under the rest, and one set of constants over all K would prove nothing.  margin = ln tau - eps.
 // table: [alpha_0, beta_0, alpha_1, beta_1 | gamma K | delta K]; a component without a bound (rho_bar = inf) gets delta = 0,
 // gamma = -1e300: its rows are unproven.
+extern "C++" {
 namespace {
 constexpr double kCertGrid[] = {0.98, 0.95, 0.9, 0.8, 0.65, 0.5, 0.3, 0.1};
 
 // upper Cholesky factor U'U of FOUR symmetric matrices at once, one per SIMD lane (as spd_inverse4: the matrices are too narrow
 // for row-wise vectorisation, but K of them are independent), in place on the upper triangle of M (n x n, row-major).  Bit l of
 // the result: a pivot of lane l was not above 1e-10 of its diagonal entry (the lane goes on with a pivot of 1; its factor is void).
-unsigned cert_chol4(v4d* __restrict__ M, int n) {
+// (V: v4d, or v4s — four doubles inside a block of doubles, which is aligned as doubles are)
+struct v4s { double v[4]; };
+inline v4d ld4(const v4d* p) { return *p; }
+inline v4d ld4(const v4s* p) { v4d r; memcpy(&r, p, sizeof r); return r; }
+inline void st4(v4d* p, v4d x) { *p = x; }
+inline void st4(v4s* p, v4d x) { memcpy(p, &x, sizeof x); }
+
+template <class V>
+unsigned cert_chol4(V* __restrict__ M, int n) {
   unsigned bad = 0;
   v4d d0[32];
-  for (int j = 0; j < n; ++j) d0[j] = M[j * n + j];
+  for (int j = 0; j < n; ++j) d0[j] = ld4(M + j * n + j);
   for (int j = 0; j < n; ++j) {
-    v4d* mj = M + (size_t)j * n;
-    v4d d = mj[j], piv;
+    V* mj = M + (size_t)j * n;
+    v4d d = ld4(mj + j), piv;
     for (int l = 0; l < 4; ++l) {
       if (!(d[l] > 1e-10 * std::fabs(d0[j][l]))) { bad |= 1u << l; d[l] = 1.0; }
       piv[l] = std::sqrt(d[l]);
     }
     const v4d inv = 1.0 / piv;
-    for (int c = j; c < n; ++c) mj[c] *= inv;
+    for (int c = j; c < n; ++c) st4(mj + c, ld4(mj + c) * inv);
     for (int i = j + 1; i < n; ++i) {
-      const v4d f = mj[i];
-      v4d* mi = M + (size_t)i * n;
-      for (int c = i; c < n; ++c) mi[c] -= f * mj[c];
+      const v4d f = ld4(mj + i);
+      V* mi = M + (size_t)i * n;
+      for (int c = i; c < n; ++c) st4(mi + c, ld4(mi + c) - f * ld4(mj + c));
     }
   }
   return bad;
 }
+
+// mu = (U'U)^-1 rhs for the four lanes; returns rhs'(U'U)^-1 rhs = |U^-T rhs|^2 (y: D v4d of scratch)
+template <class VU, class VM>
+v4d cert_solve4(const VU* U, const double* const rhs[4], VM* mu, v4d* y, int D) {
+  v4d yy = {0.0, 0.0, 0.0, 0.0};
+  for (int i = 0; i < D; ++i) {
+    v4d s = {rhs[0][i], rhs[1][i], rhs[2][i], rhs[3][i]};
+    for (int r = 0; r < i; ++r) s -= ld4(U + r * D + i) * y[r];
+    y[i] = s / ld4(U + i * D + i);
+    yy += y[i] * y[i];
+  }
+  for (int i = D - 1; i >= 0; --i) {
+    v4d s = y[i];
+    for (int r = i + 1; r < D; ++r) s -= ld4(U + i * D + r) * ld4(mu + r);
+    st4(mu + i, s / ld4(U + i * D + i));
+  }
+  return yy;
+}
+}  // namespace
+}  // extern "C++" (the two templates)
+
+// The certificate constants in two parts.  Everything that depends on the reference pass alone is fixed from that pass on: the
+// packed A0 of each group of four components, its factor U0, the centres mu0 and the peaks c^0.  mimo_host_estep_certificate_ref
+// computes that block once, mimo_host_estep_certificate_cur takes it and does the per-pass rest; the public function is the one
+// followed by the other on a block of its own, so the three deliver the same bytes.
+//   ref: [K, D, groups that factorised (-1: refused before the first), 0 | c^0 K | per group of four: A0 D D x 4, U0 D D x 4, mu0 D x 4]
+// (A0 holds the whole of each W0, not its upper triangle alone: the test "W = W0 to the bit" reads the lower one too; U0 is the
+// factor in the upper triangle of a copy.)  A reference that is refused — a
+// NaN or an infinity, or a W0 that is not positive definite in group g — still gives a block: it says so, and the per-pass part
+// refuses where the one-part function refused, after the same groups.
+namespace {
+constexpr size_t kCertRefHead = 4;
+inline size_t cert_ref_group(int D) { return (2 * (size_t)D * D + D) * 4; }
 }  // namespace
 
-int mimo_host_estep_certificate(int K, int D, const double* c0, const double* b0, const double* W0, const double* c, const double* b,
-                                const double* W, double margin, double* out, double* table) {
+size_t mimo_host_estep_certificate_ref_size(int K, int D) {
+  if (K < 1 || D < 1 || K > 256 || D > 32) return 0;
+  return kCertRefHead + (size_t)K + (size_t)((K + 3) / 4) * cert_ref_group(D);
+}
+
+int mimo_host_estep_certificate_ref(int K, int D, const double* c0, const double* b0, const double* W0, double* ref) {
   return guarded_host([&]() -> int {
-  if (K < 1 || D < 1 || !c0 || !b0 || !W0 || !c || !b || !W || !out) return MIMO_E_INVALID;
+  if (K < 1 || D < 1 || !c0 || !b0 || !W0 || !ref) return MIMO_E_INVALID;
   if (K > 256 || D > 32) return MIMO_E_UNSUPPORTED;
   const size_t DD = (size_t)D * D;
-  for (size_t i = 0; i < (size_t)K; ++i) if (!std::isfinite(c0[i]) || !std::isfinite(c[i])) return MIMO_E_INVALID;
-  for (size_t i = 0; i < (size_t)K * D; ++i) if (!std::isfinite(b0[i]) || !std::isfinite(b[i])) return MIMO_E_INVALID;
-  for (size_t i = 0; i < (size_t)K * DD; ++i) if (!std::isfinite(W0[i]) || !std::isfinite(W[i])) return MIMO_E_INVALID;
-  double *ch0 = out, *ch = out + K, *rho = out + 2 * (size_t)K, *rhob = out + 3 * (size_t)K, *dk = out + 4 * (size_t)K, *cons = out + 5 * (size_t)K;
-  std::vector<v4d> work(5 * DD);
-  v4d *A0 = work.data(), *A1 = A0 + DD, *U0 = A1 + DD, *U1 = U0 + DD, *T = U1 + DD;
-  v4d y[32], mu0[32], mu1[32];
-  // mu = (U'U)^-1 rhs; returns rhs'(U'U)^-1 rhs = |U^-T rhs|^2
-  auto solve = [&](const v4d* U, const double* const rhs[4], v4d* mu) {
-    v4d yy = {0.0, 0.0, 0.0, 0.0};
-    for (int i = 0; i < D; ++i) {
-      v4d s = {rhs[0][i], rhs[1][i], rhs[2][i], rhs[3][i]};
-      for (int r = 0; r < i; ++r) s -= U[r * D + i] * y[r];
-      y[i] = s / U[i * D + i];
-      yy += y[i] * y[i];
-    }
-    for (int i = D - 1; i >= 0; --i) {
-      v4d s = y[i];
-      for (int r = i + 1; r < D; ++r) s -= U[i * D + r] * mu[r];
-      mu[i] = s / U[i * D + i];
-    }
-    return yy;
-  };
-  for (int k0 = 0; k0 < K; k0 += 4) {
+  ref[0] = K; ref[1] = D; ref[2] = -1.0; ref[3] = 0.0;             // (-1: refused before any group)
+  for (size_t i = 0; i < (size_t)K; ++i) if (!std::isfinite(c0[i])) return MIMO_E_INVALID;
+  for (size_t i = 0; i < (size_t)K * D; ++i) if (!std::isfinite(b0[i])) return MIMO_E_INVALID;
+  for (size_t i = 0; i < (size_t)K * DD; ++i) if (!std::isfinite(W0[i])) return MIMO_E_INVALID;
+  double* ch0 = ref + kCertRefHead;
+  double* grp = ch0 + K;
+  v4d y[32];
+  int g = 0;
+  for (int k0 = 0; k0 < K; k0 += 4, ++g, grp += cert_ref_group(D)) {
     int kk[4];                                    // (a last group short of four repeats its last component)
     for (int l = 0; l < 4; ++l) kk[l] = std::min(k0 + l, K - 1);
-    const double *a0[4], *a1[4], *r0[4], *r1[4];
-    for (int l = 0; l < 4; ++l) { a0[l] = W0 + kk[l] * DD; a1[l] = W + kk[l] * DD; r0[l] = b0 + (size_t)kk[l] * D; r1[l] = b + (size_t)kk[l] * D; }
+    const double *a0[4], *r0[4];
+    for (int l = 0; l < 4; ++l) { a0[l] = W0 + kk[l] * DD; r0[l] = b0 + (size_t)kk[l] * D; }
+    v4s *A0 = reinterpret_cast<v4s*>(grp), *U0 = A0 + DD, *mu0 = U0 + DD;
+    for (size_t e = 0; e < DD; ++e) U0[e] = A0[e] = v4s{{a0[0][e], a0[1][e], a0[2][e], a0[3][e]}};
+    ref[2] = g;                                   // groups before this one stand
+    if (cert_chol4(U0, D)) return MIMO_E_INVALID;                 // a precision that is not positive definite
+    const v4d q0 = cert_solve4(U0, r0, mu0, y, D);
+    for (int l = 0; l < 4 && k0 + l < K; ++l) ch0[k0 + l] = c0[k0 + l] + 0.5 * q0[l];
+  }
+  ref[2] = g;
+  return MIMO_OK;
+  });
+}
+
+int mimo_host_estep_certificate_cur(int K, int D, const double* ref, const double* c, const double* b, const double* W, double margin,
+                                    double* out, double* table) {
+  return guarded_host([&]() -> int {
+  if (K < 1 || D < 1 || !ref || !c || !b || !W || !out) return MIMO_E_INVALID;
+  if (K > 256 || D > 32) return MIMO_E_UNSUPPORTED;
+  if (ref[0] != (double)K || ref[1] != (double)D) return MIMO_E_INVALID;        // a block of another shape
+  const size_t DD = (size_t)D * D;
+  // (the reference's three arrays were scanned by mimo_host_estep_certificate_ref when the block was made, and a block refused there
+  // says so: only the current ones are scanned per pass)
+  if (ref[2] < 0.0) return MIMO_E_INVALID;
+  for (size_t i = 0; i < (size_t)K; ++i) if (!std::isfinite(c[i])) return MIMO_E_INVALID;
+  for (size_t i = 0; i < (size_t)K * D; ++i) if (!std::isfinite(b[i])) return MIMO_E_INVALID;
+  for (size_t i = 0; i < (size_t)K * DD; ++i) if (!std::isfinite(W[i])) return MIMO_E_INVALID;
+  const int good = (int)ref[2];                   // groups of the reference that factorised
+  const double *rch0 = ref + kCertRefHead, *grp = rch0 + K;
+  double *ch0 = out, *ch = out + K, *rho = out + 2 * (size_t)K, *rhob = out + 3 * (size_t)K, *dk = out + 4 * (size_t)K, *cons = out + 5 * (size_t)K;
+  std::vector<v4d> work(3 * DD);
+  v4d *A1 = work.data(), *U1 = A1 + DD, *T = U1 + DD;
+  v4d y[32], mu1[32];
+  int g = 0;
+  for (int k0 = 0; k0 < K; k0 += 4, ++g, grp += cert_ref_group(D)) {
+    int kk[4];                                    // (a last group short of four repeats its last component)
+    for (int l = 0; l < 4; ++l) kk[l] = std::min(k0 + l, K - 1);
+    const double *a1[4], *r1[4];
+    for (int l = 0; l < 4; ++l) { a1[l] = W + kk[l] * DD; r1[l] = b + (size_t)kk[l] * D; }
+    const v4s *A0 = reinterpret_cast<const v4s*>(grp), *U0 = A0 + DD, *mu0 = U0 + DD;
     for (int i = 0; i < D; ++i)
       for (int j = i; j < D; ++j) {
         const size_t e = (size_t)i * D + j;
-        U0[e] = A0[e] = v4d{a0[0][e], a0[1][e], a0[2][e], a0[3][e]};
         U1[e] = A1[e] = v4d{a1[0][e], a1[1][e], a1[2][e], a1[3][e]};
       }
-    if (cert_chol4(U0, D) | cert_chol4(U1, D)) return MIMO_E_INVALID;               // a precision that is not positive definite
-    const v4d q0 = solve(U0, r0, mu0), q1 = solve(U1, r1, mu1);
+    if ((g >= good) | (cert_chol4(U1, D) != 0)) return MIMO_E_INVALID;             // a precision that is not positive definite
+    const v4d q1 = cert_solve4(U1, r1, mu1, y, D);
     v4d d2 = {0.0, 0.0, 0.0, 0.0};
     for (int i = 0; i < D; ++i) {                 // |U0 (mu - mu0)|^2
       v4d s = {0.0, 0.0, 0.0, 0.0};
-      for (int r = i; r < D; ++r) s += U0[i * D + r] * (mu1[r] - mu0[r]);
+      for (int r = i; r < D; ++r) s += ld4(U0 + i * D + r) * (mu1[r] - ld4(mu0 + r));
       d2 += s * s;
     }
     unsigned same = 0;                            // W = W0 to the bit: both eigenvalue bounds are 1
-    for (int l = 0; l < 4; ++l) if (!memcmp(a0[l], a1[l], DD * sizeof(double))) same |= 1u << l;
+    for (int l = 0; l < 4; ++l) {                 // (as a memcmp of the two matrices: the bytes, both triangles)
+      size_t e = 0;
+      while (e < DD && !memcmp(&A0[e].v[l], a1[l] + e, sizeof(double))) ++e;
+      if (e == DD) same |= 1u << l;
+    }
     double lo[4] = {0.0, 0.0, 0.0, 0.0}, hi[4] = {HUGE_VAL, HUGE_VAL, HUGE_VAL, HUGE_VAL};
     for (int side = 0; side < 2; ++side) {        // 0: rho from W - s W0, 1: 1 / rho_bar from W0 - s W
-      const v4d *P = side ? A0 : A1, *Q = side ? A1 : A0;
       unsigned pending = 0xFu & ~same;
       for (const double s : kCertGrid) {
         if (!pending) break;
         for (int i = 0; i < D; ++i)
-          for (int j = i; j < D; ++j) T[i * D + j] = P[i * D + j] - s * Q[i * D + j];
+          for (int j = i; j < D; ++j) T[i * D + j] = side ? ld4(A0 + i * D + j) - s * A1[i * D + j] : A1[i * D + j] - s * ld4(A0 + i * D + j);
         const unsigned ok = pending & ~cert_chol4(T, D);
         for (int l = 0; l < 4; ++l) if (ok >> l & 1u) { if (side) hi[l] = 1.0 / s; else lo[l] = s; }
         pending &= ~ok;
@@ -1210,7 +1282,7 @@ int mimo_host_estep_certificate(int K, int D, const double* c0, const double* b0
     }
     for (int l = 0; l < 4 && k0 + l < K; ++l) {
       const int k = k0 + l;
-      ch0[k] = c0[k] + 0.5 * q0[l];
+      ch0[k] = rch0[k];
       ch[k] = c[k] + 0.5 * q1[l];
       dk[k] = std::sqrt(d2[l]);
       rho[k] = (same >> l & 1u) ? 1.0 : lo[l];
@@ -1250,6 +1322,19 @@ int mimo_host_estep_certificate(int K, int D, const double* c0, const double* b0
     gam[k] = ch[k] - del[k] * ch0[k] - 0.5 * rhob[k] * (1.0 + 1.0 / e) * dk[k] * dk[k] + margin;
   }
   return MIMO_OK;
+  });
+}
+
+
+int mimo_host_estep_certificate(int K, int D, const double* c0, const double* b0, const double* W0, const double* c, const double* b,
+                                const double* W, double margin, double* out, double* table) {
+  return guarded_host([&]() -> int {
+  if (K < 1 || D < 1 || !c0 || !b0 || !W0 || !c || !b || !W || !out) return MIMO_E_INVALID;
+  if (K > 256 || D > 32) return MIMO_E_UNSUPPORTED;
+  const std::unique_ptr<double[]> ref(new double[mimo_host_estep_certificate_ref_size(K, D)]);
+  const int rc = mimo_host_estep_certificate_ref(K, D, c0, b0, W0, ref.get());
+  if (rc != MIMO_OK && rc != MIMO_E_INVALID) return rc;
+  return mimo_host_estep_certificate_cur(K, D, ref.get(), c, b, W, margin, out, table);   // (a refused reference: refused there, as far on)
   });
 }
 

@@ -104,9 +104,9 @@ constexpr bool fused_lane_regs(int NCB, int RBW, int MODE, int DS, int SPLIT, bo
 
 // CERT (SKIP at Dz >= 14, launched for K16 = 4; DESIGN section 4, "E-step certificates"): two more instantiations of the SKIP
 // kernel, not branches inside it.  kCertReference is the SKIP kernel whose normalise phase also stores each row's certificate.
-// kCertCertified reads them: per tile every wave tests the 32 rows (row lane & 31 on every lane: one fused multiply-add per
-// class of components, one for the row's own bound, a compare), ballots the rows proven dead outside their row block, and
-// contracts step 3 over the rows it has to — the unproven ones and the proven ones of its own block.  At most 16 of them: ONE
+// kCertCertified reads them: per tile, one tile ahead (cert_descriptor), every wave tests the 32 rows (row lane & 31 on every lane:
+// one fused multiply-add per class of components, one for the row's own bound, a compare), ballots the rows proven dead outside
+// their row block, and contracts step 3 over the rows it has to — the unproven ones and the proven ones of its own block.  At most 16 of them: ONE
 // column group over the compacted rows (NS MFMAs instead of 2 NS; lane (q, j) reads Phi[row_j][4 s + q] and stores
 // Lt[row_j][16 wave + q + 4 r], an empty slot reads a valid row and stores nothing).  More: the SKIP kernel's two groups, on a
 // wave-uniform branch.  Everything delivered is bit for bit what the SKIP kernel delivers (normalise_tile, mimo_tile.h).
@@ -310,11 +310,11 @@ void fused_kernel(const KernelArgs a) {
   store_z(blockIdx.x);
   load_z((int64_t)blockIdx.x + gridDim.x);
   // kCertCertified: the certificate of row (lane & 31) of the tile.  Like the z~ rows it is fetched two tiles ahead, at the end of
-  // a tile, and handed on one tile later: a load issued in front of step 3 would sit in front of the Theta ring's loads, whose
+  // a tile, and turned into the tile's descriptor one tile later (below): a load issued in front of step 3 would sit in front of the Theta ring's loads, whose
   // counted waits then wait for its HBM round trip too.  The per-slot coefficients and row blocks are a 136-double table in
   // LDS, the two classes' coefficients scalars.
-  int ck = 0, nk = 0;
-  double cm = 0.0, ca = 0.0, nm = 0.0, na = 0.0;
+  int nk = 0;
+  double nm = 0.0, na = 0.0;
   auto load_cert = [&](int64_t t, int& k, double& m, double& av) {
     const int64_t n = t * T + (lane & 31);
     const bool in = n < N;                    // (tiles past the data, which the prefetch reaches, read nothing)
@@ -324,19 +324,65 @@ void fused_kernel(const KernelArgs a) {
   };
   double ctab[4] = {0.0, 0.0, 0.0, 0.0};
   double* const ctl = reinterpret_cast<double*>(fe + 2 * F16);      // [64] gamma | [64] delta | 64 bytes: row block of the slot
+  double* const ninf = ctl + (kCertTabLen - 4);                     // [8] -inf: what a lane loads whose slots were not contracted
   uint32_t cnt_proven = 0, cnt_one = 0, cnt_all = 0;
+  // The check of a tile and what step 3 and the normalise phase need of it are worked out one tile ahead, at the hand-over behind
+  // step 1' (and once in front of the loop), from the certificate fetched a tile before that and the static table: the top barrier
+  // of the next tile, where a wave waits for the slowest one's statistics, covers the chain, and behind the barrier of step 3
+  // only the operand reads and the MFMAs are left.  What crosses the tile boundary:
+  //   d_need   (scalar) the rows this wave contracts, all 32 bits: the two-group code
+  //   d_poff, d_lwoff   one group: this lane's row of Phi (+ q) and of the L tile (+ 16 wave + q).  Slot j = lane & 15 takes the
+  //            j-th row of d_need: lane i < 32 whose bit is set pushes i to lane rank(i) (v_mbcnt, one ds_permute; the others push
+  //            to lane 63, which nobody reads), and lane (q, j) pulls slot j's.  A slot past the last reads whatever valid row
+  //            arrives (& 31) and stores nothing.
+  //   d_roff   the lane's 8 doubles of the normalise phase: its slots of row 8 wave + (lane & 7) where some wave contracted them,
+  //            else the -inf row
+  uint32_t d_need = 0xFFFFFFFFu;
+  int d_poff = 0, d_lwoff = 0, d_roff = 0;
+  auto cert_descriptor = [&](int64_t t, int k, double m, double av) {
+    if (t >= a.ntiles) return;                                      // (scalar) past the workgroup's last tile: nothing to describe or count
+    const bool in = t * T + (lane & 31) < N;                        // a row past N is unproven
+    const double cgam = ctl[k], cdel = ctl[64 + k];                 // the row's own coefficients and row block, by its slot
+    const int cblk = reinterpret_cast<const uint8_t*>(ctl + 128)[k];
+    const double ub = fmax(fma(ctab[1], av, ctab[0]), fma(ctab[3], av, ctab[2]));
+    const bool proven = in && ub <= fma(cdel, m, cgam);
+    const uint32_t pm = (uint32_t)__builtin_amdgcn_ballot_w64(proven);
+    const uint32_t b0 = (uint32_t)__builtin_amdgcn_ballot_w64((cblk & 1) != 0), b1 = (uint32_t)__builtin_amdgcn_ballot_w64((cblk & 2) != 0);
+    // the rows proven dead in row block w: proven, and their own block differs from w in one of its two bits.  Wave w contracts
+    // the others, ~dead(w): the unproven rows and the proven ones of its block; 16 of them at most, or it runs the two-group code.
+    auto dead = [&](int w) -> uint32_t { return pm & ((b0 ^ (0u - (w & 1))) | (b1 ^ (0u - ((w >> 1) & 1)))); };
+    const uint32_t dw = dead(wave);                                 // (scalar) this wave's, for step 3
+    d_need = __builtin_popcount(dw) >= 16 ? ~dw : 0xFFFFFFFFu;
+    const uint32_t dl = dead(lane >> 4);                            // per lane: its row block's (lane >> 4), for the normalise phase
+    const int pt = 8 * wave + (lane & 7);
+    const bool have = __builtin_popcount(dl) < 16 || !((dl >> pt) & 1u);
+    d_roff = have ? pt * LS + 8 * (lane >> 3) : (int)(ninf - Lt);
+    const int rank = __builtin_amdgcn_mbcnt_lo(d_need, 0);
+    const bool push = lane < 32 && ((d_need >> (lane & 31)) & 1u);
+    const int got = __builtin_amdgcn_ds_permute((push ? rank : 63) << 2, lane);
+    const int rj = __builtin_amdgcn_ds_bpermute(j << 2, got) & 31;
+    d_poff = rj * RS + q;
+    d_lwoff = rj * LS + 16 * wave + q;
+    if (wave == 0) cnt_proven += __builtin_popcount(pm);
+    cnt_one += d_need != 0xFFFFFFFFu ? 1u : 0u;
+    cnt_all += 1u;
+  };
   if constexpr (CERT == kCertCertified) {
-    load_cert(blockIdx.x, ck, cm, ca);
-    load_cert((int64_t)blockIdx.x + gridDim.x, nk, nm, na);
+    load_cert(blockIdx.x, nk, nm, na);
 #pragma unroll
     for (int i = 0; i < 4; ++i) ctab[i] = a.cert_tab[i];
     for (int e = tid; e < kCertTabLen - 4; e += kWG) ctl[e] = a.cert_tab[4 + e];   // (in LDS by the barrier in front of the tile loop)
+    if (tid < 8) ninf[tid] = -INFINITY;
   }
 
   // feature build: thread (row = tid & 31, g = tid >> 5) produces the 2*NCB consecutive features
   // [g*2*NCB, (g+1)*2*NCB); their (a,b) byte pairs are NCB consecutive 32-bit words of the table.
   const int frow = tid & (T - 1), fgrp = tid >> 5;
   wg_sync();  // feature table and exp table are in LDS
+  if constexpr (CERT == kCertCertified) {
+    cert_descriptor(blockIdx.x, nk, nm, na);
+    load_cert((int64_t)blockIdx.x + gridDim.x, nk, nm, na);
+  }
   uint32_t w[NCB];
   if constexpr (DS == 0) {
 #pragma unroll
@@ -432,30 +478,8 @@ void fused_kernel(const KernelArgs a) {
       // ---- 3. L tile = Theta . Phi' ------------------------------------------------------
       // B operand: lane (kk = q, col = j) holds Phi[row 16 g + j][4 s + q].
       // C/D layout of v_mfma_f64_16x16x4_f64: reg r of lane (q, j) = row q + 4 r, col j.
-      // kCertCertified: need = the rows this wave contracts (all 32 bits: the two-group code), computed = per lane, the rows whose
-      // slots of the lane's row block (lane >> 4) some wave contracts.  Every wave derives all four waves' sets from the same
-      // three ballots, on the scalar side.  A row past N is unproven.
-      uint32_t need = 0xFFFFFFFFu, computed = 0xFFFFFFFFu;
-      if constexpr (CERT == kCertCertified) {
-        const bool in = n0 + (lane & 31) < N;
-        const double cgam = ctl[ck], cdel = ctl[64 + ck];            // the row's own coefficients and row block, by its slot
-        const int cblk = reinterpret_cast<const uint8_t*>(ctl + 128)[ck];
-        const double ub = fmax(fma(ctab[1], ca, ctab[0]), fma(ctab[3], ca, ctab[2]));
-        const bool proven = in && ub <= fma(cdel, cm, cgam);
-        const uint32_t pm = (uint32_t)__builtin_amdgcn_ballot_w64(proven);
-        const uint32_t b0 = (uint32_t)__builtin_amdgcn_ballot_w64((cblk & 1) != 0), b1 = (uint32_t)__builtin_amdgcn_ballot_w64((cblk & 2) != 0);
-        uint32_t eff[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          const uint32_t nd = ~pm | (((w & 1) ? b0 : ~b0) & ((w & 2) ? b1 : ~b1));
-          eff[w] = __builtin_popcount(nd) <= 16 ? nd : 0xFFFFFFFFu;
-        }
-        need = wave == 0 ? eff[0] : wave == 1 ? eff[1] : wave == 2 ? eff[2] : eff[3];
-        computed = lane < 16 ? eff[0] : lane < 32 ? eff[1] : lane < 48 ? eff[2] : eff[3];
-        if (wave == 0) cnt_proven += __builtin_popcount(pm);
-        cnt_one += need != 0xFFFFFFFFu ? 1u : 0u;
-        cnt_all += 1u;
-      }
+      // kCertCertified: the tile's check was evaluated at the hand-over (cert_descriptor); what is left here is a scalar test
+      // and the one-group code's two row offsets.
       if constexpr (is_split) {
         if (sidx < 2) {                     // column group sidx of row block srb
           gptr_t th = (gptr_t)(a.theta + (size_t)srb * NSI * 64);
@@ -489,21 +513,12 @@ void fused_kernel(const KernelArgs a) {
         const double* p0 = Ph + j * RS + q;
         const double* p1 = Ph + (16 + j) * RS + q;
         bool one_group = false;
-        if constexpr (CERT == kCertCertified) one_group = need != 0xFFFFFFFFu;      // (scalar)
+        if constexpr (CERT == kCertCertified) one_group = d_need != 0xFFFFFFFFu;      // (scalar)
         if (one_group) {
           if constexpr (CERT == kCertCertified) {
-            // slot jj of the column group takes the jj-th row of `need`, ascending (a scalar walk over its bits); the slots past
-            // the last one repeat the first row (none at all: row 0) and store nothing
-            const int cnt = __builtin_popcount(need);
-            int rj = need ? __builtin_ctz(need) : 0;
-            {
-              uint32_t mleft = need;
-              for (int jj = 0; mleft; ++jj) {                 // (scalar loop: a compare and a select per row)
-                rj = j == jj ? __builtin_ctz(mleft) : rj;
-                mleft &= mleft - 1;
-              }
-            }
-            int p_off = rj * RS + q;
+            // slot j of the column group takes the j-th row of d_need, ascending; the slots past the last one store nothing
+            const int cnt = __builtin_popcount(d_need);
+            int p_off = d_poff;
             asm volatile("" : "+v"(p_off));
             const double* pc = Ph + p_off;
             d4 acc = SEED ? d4{cseed[0], cseed[1], cseed[2], cseed[3]} : d4{0.0, 0.0, 0.0, 0.0};
@@ -519,7 +534,7 @@ void fused_kernel(const KernelArgs a) {
               acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bq[s % 3], acc, 0, 0, 0);
             }
             if (j < cnt) {
-              int lw_off = rj * LS + 16 * wave + q;
+              int lw_off = d_lwoff;
               asm volatile("" : "+v"(lw_off));
               double* lw = Lt + lw_off;
 #pragma unroll
@@ -590,7 +605,7 @@ void fused_kernel(const KernelArgs a) {
       if constexpr (RBW == 1)
         normalise_tile<RBW, MODE, E2K, SKIP, LX, CERT>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
                                                    out_lse, sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T, lnt,
-                                                   live, computed);
+                                                   live, d_roff);
       else
         normalise_tile_chunked<RBW, MODE, LX>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
                                           out_lse, sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T);
@@ -814,12 +829,14 @@ void fused_kernel(const KernelArgs a) {
     }
 
     // ---- 1'. stage the next tile's z~ rows (Zs was last read before the barrier after step 2)
-    store_z(t + gridDim.x);
-    load_z(t + 2 * (int64_t)gridDim.x);
+    // kCertCertified: the next tile's check first, from the certificate fetched a tile ago.  Its wait then stands in front of
+    // this tile's z~ loads, not behind them (behind them it would wait for their HBM round trip as well).
     if constexpr (CERT == kCertCertified) {
-      ck = nk; cm = nm; ca = na;
+      cert_descriptor(t + gridDim.x, nk, nm, na);
       load_cert(t + 2 * (int64_t)gridDim.x, nk, nm, na);
     }
+    store_z(t + gridDim.x);
+    load_z(t + 2 * (int64_t)gridDim.x);
     STAMP(7);
 #ifdef MIMO_STAMPS
     if (st_trace) st_tr[3] = st_prev;
@@ -1348,7 +1365,7 @@ __global__ void unpack_stats(const double* __restrict__ red, const uint8_t* __re
 // (src = kSrcEstep at Dz = 14 .. 16 with K <= 64 on the full map: the instantiations with the 2048-entry exp table, fused_kernel E2K)
 size_t fused_lds_bytes(const KernelArgs& a, int src) {
   const bool e2k = src == kSrcEstep && !a.diag && a.D >= 14 && a.D <= kMaxFusedD && a.K16 <= 4;
-  const size_t cert = src == kSrcEstep && a.cert == kCertCertified ? sizeof(double) * (kCertTabLen - 4) : 0;     // its table, behind the feature bytes
+  const size_t cert = src == kSrcEstep && a.cert == kCertCertified ? sizeof(double) * (kCertTabLen - 4 + 8) : 0;     // its table and its -inf row, behind the feature bytes
   return sizeof(double) * ((size_t)kTile * (a.ZS + a.RS + a.LS) + 16 + (e2k ? kExpTab : 64)) + (size_t)a.F16 * 2 + cert;
 }
 

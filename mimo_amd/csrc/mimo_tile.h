@@ -117,8 +117,8 @@ __device__ __forceinline__ void build_features_static(const double (&zl)[D + 2],
 //                   block maxima exist after the lane ^ 8 stage; the stages ^ 16 and ^ 32 then carry the pair (largest,
 //                   second largest block maximum): the second largest IS the largest outside the winner's block.  One lane
 //                   per row stores: of the lanes whose own maximum equals the row's, the lowest.
-//   kCertCertified  bit pt of `computed` says whether this lane's 8 slots of row pt were contracted this tile; a lane whose slots
-//                   were not loads -inf instead of the stale tile.  Such a lane belongs to a row proven dead in its block: the
+//   kCertCertified  cert_row is the offset from Lt of the 8 doubles this lane loads: its slots of row pt where they were contracted
+//                   this tile, else 8 doubles of -inf kept in LDS, not the stale tile.  Such a lane belongs to a row proven dead in its block: the
 //                   maximum lies elsewhere, its exponentials are 0 where CERT = 0 has values below 2^-60 (48 of them at most:
 //                   under half an ulp of a sum >= 1, which they meet only at the ^ 16 and ^ 32 stages), its live bit is clear
 //                   either way, and nothing reads the weights it writes back.
@@ -139,7 +139,7 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
                                                double* const out_lse, double& sc_lse, double& sc_rl, double& sc_prod,
                                                int* __restrict__ labs, PhiloxBatch& pb,
                                                const int64_t tstride, const double lnt = 0.0,
-                                               uint32_t* __restrict__ live = nullptr, const uint32_t computed = 0) {
+                                               uint32_t* __restrict__ live = nullptr, const int cert_row = 0) {
         static_assert(RBW == 1, "register variant: at most 8 components per lane");
         static_assert(!SKIP || MODE == kFastVI, "responsibility skip: softmax of the fast VI mode only");
         static_assert(CERT == 0 || (SKIP && LX), "certificates: the skipping softmax pass, lane exchanges in registers");
@@ -158,9 +158,9 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
         // x[] holds l, then exp(l - max), then the weight written back — one register array
         double x[8], lsave[8];
         if constexpr (CERT == kCertCertified && FULL) {
-          const bool have = (computed >> pt) & 1u;
+          const double* src = Lt + cert_row;        // the lane's slots of the tile, or the -inf row: one select, made by the caller
 #pragma unroll
-          for (int c = 0; c < 8; ++c) x[c] = have ? row[c] : -INFINITY;
+          for (int c = 0; c < 8; ++c) x[c] = src[c];
         } else {
 #pragma unroll
           for (int c = 0; c < 8; ++c) x[c] = ok(c) ? row[c] : -INFINITY;

@@ -910,6 +910,11 @@ int mimo_tune(mimo_ctx* ctx, const char* key, int64_t value);
  * pairs that contracted one column group, (tile, wave) pairs].  Waits for the stream.  Reads nothing else and changes nothing. */
 int mimo_estep_cert_info(mimo_ctx* ctx, int64_t* out6);
 
+/* One more running total of the certified passes: the (tile, wave) pairs whose eight rows were all proven, which the kernel
+ * normalises over each row's live row block alone (two slots per lane instead of eight).  Waits for the stream; reads nothing
+ * else and changes nothing. */
+int mimo_estep_cert_proven_waves(mimo_ctx* ctx, int64_t* out);
+
 /* Test hook for the no-exception contract: throws, INSIDE the guarded boundary, kind 1: std::bad_alloc,
  * 2: std::runtime_error, 3: a non-std exception; returns the code the guard maps it to (MIMO_E_NOMEM,
  * MIMO_E_INTERNAL, MIMO_E_INTERNAL) with the message in mimo_last_error(ctx) (ctx may be NULL).  kind 0: MIMO_OK.

@@ -111,6 +111,7 @@ SIGNATURES = {
     "mimo_comm_destroy": (C.c_int, [_vp]),
     "mimo_tune": (C.c_int, [_vp, C.c_char_p, C.c_int64]),
     "mimo_estep_cert_info": (C.c_int, [_vp, _vp]),
+    "mimo_estep_cert_proven_waves": (C.c_int, [_vp, _vp]),
     "mimo_data_checksum": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "mimo_debug_fault": (C.c_int, [_vp, C.c_int]),
     "mimo_host_debug_fault": (C.c_int, [C.c_int]),

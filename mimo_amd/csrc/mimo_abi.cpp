@@ -1332,6 +1332,21 @@ int mimo_estep_cert_info(mimo_ctx* ctx, int64_t* out6) {
   });
 }
 
+int mimo_estep_cert_proven_waves(mimo_ctx* ctx, int64_t* out) {
+  return guarded(ctx, [&]() -> int {
+    int rc = bind(ctx); if (rc) return rc;
+    if (!out) return fail(ctx, MIMO_E_INVALID, "mimo_estep_cert_proven_waves: out is NULL");
+    if (ctx->pending_async) return fail(ctx, MIMO_E_STATE, "an asynchronous call is pending: call mimo_wait first");
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    if (ctx->cert_cnt.p) {
+      HIP_TRY(ctx, hipMemcpyAsync(cnt, ctx->cert_cnt, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    *out = (int64_t)cnt[3];
+    return MIMO_OK;
+  });
+}
+
 double mimo_philox_uniform(uint64_t seed, uint64_t row, uint64_t sweep) {
   return philox_uniform_host(seed, row, sweep);
 }

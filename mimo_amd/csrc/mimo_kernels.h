@@ -67,7 +67,7 @@ struct KernelArgs {
   double* cert_m;         // (N,) that log-density
   double* cert_a;         // (N,) the largest log-density of the reference pass outside the row block of that slot
   const double* cert_tab; // kCertTabLen doubles behind the Theta image: [alpha0, beta0, alpha1, beta1 | gamma[64] | delta[64] | row block of slot s: 64 bytes]
-  unsigned long long* cert_cnt;   // [0] rows proven, [1] wave-tiles on one column group, [2] wave-tiles, summed over the certified passes
+  unsigned long long* cert_cnt;   // [0] rows proven, [1] wave-tiles on one column group, [2] wave-tiles, [3] wave-tiles normalised on the live row block, summed over the certified passes
 };
 enum Cert : int { kCertNone = 0, kCertReference = 1, kCertCertified = 2 };
 constexpr int kCertTabLen = 4 + 64 + 64 + 8;

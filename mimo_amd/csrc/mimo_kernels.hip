@@ -325,7 +325,7 @@ void fused_kernel(const KernelArgs a) {
   double ctab[4] = {0.0, 0.0, 0.0, 0.0};
   double* const ctl = reinterpret_cast<double*>(fe + 2 * F16);      // [64] gamma | [64] delta | 64 bytes: row block of the slot
   double* const ninf = ctl + (kCertTabLen - 4);                     // [8] -inf: what a lane loads whose slots were not contracted
-  uint32_t cnt_proven = 0, cnt_one = 0, cnt_all = 0;
+  uint32_t cnt_proven = 0, cnt_one = 0, cnt_all = 0, cnt_block = 0;
   // The check of a tile and what step 3 and the normalise phase need of it are worked out one tile ahead, at the hand-over behind
   // step 1' (and once in front of the loop), from the certificate fetched a tile before that and the static table: the top barrier
   // of the next tile, where a wave waits for the slowest one's statistics, covers the chain, and behind the barrier of step 3
@@ -337,7 +337,11 @@ void fused_kernel(const KernelArgs a) {
   //            arrives (& 31) and stores nothing.
   //   d_roff   the lane's 8 doubles of the normalise phase: its slots of row 8 wave + (lane & 7) where some wave contracted them,
   //            else the -inf row
-  uint32_t d_need = 0xFFFFFFFFu;
+  //   d_live   (scalar) not 0: all eight rows this wave normalises are proven (byte `wave` of the ballot is all ones; proven implies
+  //            inside N).  Each is live in its own row block alone, so the wave's four live bytes follow from the rows' block bits
+  //            (byte b: the rows of block b; together they cover the eight rows, so the word is not 0), and d_roff is the lane's TWO
+  //            slots of the row's own block, which its owner wave always contracts (normalise_tile, the proven wave)
+  uint32_t d_need = 0xFFFFFFFFu, d_live = 0;
   int d_poff = 0, d_lwoff = 0, d_roff = 0;
   auto cert_descriptor = [&](int64_t t, int k, double m, double av) {
     if (t >= a.ntiles) return;                                      // (scalar) past the workgroup's last tile: nothing to describe or count
@@ -356,7 +360,11 @@ void fused_kernel(const KernelArgs a) {
     const uint32_t dl = dead(lane >> 4);                            // per lane: its row block's (lane >> 4), for the normalise phase
     const int pt = 8 * wave + (lane & 7);
     const bool have = __builtin_popcount(dl) < 16 || !((dl >> pt) & 1u);
-    d_roff = have ? pt * LS + 8 * (lane >> 3) : (int)(ninf - Lt);
+    // this wave's eight rows all proven: the lane's two slots of the row's own block, and the live bytes from the rows' block bits
+    const uint32_t w0 = (b0 >> (8 * wave)) & 0xFFu, w1 = (b1 >> (8 * wave)) & 0xFFu;      // (scalar)
+    d_live = ((pm >> (8 * wave)) & 0xFFu) == 0xFFu ? (0xFFu & ~w0 & ~w1) | ((w0 & ~w1) << 8) | ((w1 & ~w0) << 16) | ((w0 & w1) << 24) : 0u;
+    const int own = pt * LS + 16 * (int)(((b0 >> pt) & 1u) | (((b1 >> pt) & 1u) << 1)) + 2 * (lane >> 3);
+    d_roff = d_live != 0 ? own : have ? pt * LS + 8 * (lane >> 3) : (int)(ninf - Lt);
     const int rank = __builtin_amdgcn_mbcnt_lo(d_need, 0);
     const bool push = lane < 32 && ((d_need >> (lane & 31)) & 1u);
     const int got = __builtin_amdgcn_ds_permute((push ? rank : 63) << 2, lane);
@@ -366,6 +374,7 @@ void fused_kernel(const KernelArgs a) {
     if (wave == 0) cnt_proven += __builtin_popcount(pm);
     cnt_one += d_need != 0xFFFFFFFFu ? 1u : 0u;
     cnt_all += 1u;
+    cnt_block += d_live != 0 ? 1u : 0u;
   };
   if constexpr (CERT == kCertCertified) {
     load_cert(blockIdx.x, nk, nm, na);
@@ -605,7 +614,7 @@ void fused_kernel(const KernelArgs a) {
       if constexpr (RBW == 1)
         normalise_tile<RBW, MODE, E2K, SKIP, LX, CERT>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
                                                    out_lse, sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T, lnt,
-                                                   live, d_roff);
+                                                   live, d_roff, d_live);
       else
         normalise_tile_chunked<RBW, MODE, LX>(a, Lt, LS, etab, K, K16, N, n0, wave, lane, gibbs, out_logp, out_resp,
                                           out_lse, sc_lse, sc_rl, sc_prod, labs, pbatch, (int64_t)gridDim.x * T);
@@ -878,6 +887,7 @@ void fused_kernel(const KernelArgs a) {
       if (wave == 0) atomicAdd(a.cert_cnt, (unsigned long long)cnt_proven);
       atomicAdd(a.cert_cnt + 1, (unsigned long long)cnt_one);
       atomicAdd(a.cert_cnt + 2, (unsigned long long)cnt_all);
+      atomicAdd(a.cert_cnt + 3, (unsigned long long)cnt_block);
     }
   }
   if constexpr (MODE == kFastVI || MODE == kFastGibbs) sc_lse += log(sc_prod);

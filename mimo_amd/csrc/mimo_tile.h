@@ -121,7 +121,9 @@ __device__ __forceinline__ void build_features_static(const double (&zl)[D + 2],
 //                   this tile, else 8 doubles of -inf kept in LDS, not the stale tile.  Such a lane belongs to a row proven dead in its block: the
 //                   maximum lies elsewhere, its exponentials are 0 where CERT = 0 has values below 2^-60 (48 of them at most:
 //                   under half an ulp of a sum >= 1, which they meet only at the ^ 16 and ^ 32 stages), its live bit is clear
-//                   either way, and nothing reads the weights it writes back.
+//                   either way, and nothing reads the weights it writes back.  cert_live != 0 (scalar): the wave's eight rows are
+//                   all proven; cert_row is then the lane's TWO slots of the row's own block and cert_live the wave's four live
+//                   bytes (the proven wave, at the top of the function).
 // ------------------------------------------------------------------------------------------
 // {max, min} of v and the value of lane ^ MASK (MASK 16 or 32: the swap hands them over in lane-dependent order)
 template <int MASK>
@@ -139,11 +141,47 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
                                                double* const out_lse, double& sc_lse, double& sc_rl, double& sc_prod,
                                                int* __restrict__ labs, PhiloxBatch& pb,
                                                const int64_t tstride, const double lnt = 0.0,
-                                               uint32_t* __restrict__ live = nullptr, const int cert_row = 0) {
+                                               uint32_t* __restrict__ live = nullptr, const int cert_row = 0,
+                                               const uint32_t cert_live = 0) {
         static_assert(RBW == 1, "register variant: at most 8 components per lane");
         static_assert(!SKIP || MODE == kFastVI, "responsibility skip: softmax of the fast VI mode only");
         static_assert(CERT == 0 || (SKIP && LX), "certificates: the skipping softmax pass, lane exchanges in registers");
         const int pt = 8 * wave + (lane & 7), part = lane >> 3;
+        if constexpr (CERT == kCertCertified) {
+          // Proven wave (cert_live != 0, scalar: all eight rows of this wave proven, K16 = 4): every row is live in its own row block
+          // and in no other, so the eight lanes of a row share that block's 16 slots, two each (cert_row: slots 2 part and 2 part
+          // + 1 of the block), instead of six of them pushing the -inf row through eight exponentials each.  Same bits: with
+          // p_c = e_2c + e_2c+1 in lane c the stages ^8, ^16, ^32 add ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)), which is
+          // tree_sum8 of slots 0 .. 7 plus tree_sum8 of slots 8 .. 15, the block sum of the eight-slot map after its ^8 stage; what
+          // that map adds to it at ^16 and ^32 is below half an ulp of a sum >= 1 (above).  The maximum is exact in any order, and
+          // it lies in the block.  The wave's live bytes are cert_live itself (the caller made them from the rows' block bits):
+          // no compare, no ballot.  Only the two weights are written back: the statistics of block b read the rows live in b.
+          if (cert_live != 0) {
+            double* src = Lt + cert_row;
+            double x0 = src[0], x1 = src[1];
+            double m = fmax(x0, x1);
+            m = butterfly_max<LX, 8>(m);
+            m = butterfly_max<LX, 16>(m);
+            m = butterfly_max<LX, 32>(m);
+            if (lane < K16) reinterpret_cast<uint8_t*>(live)[4 * lane + wave] = (uint8_t)(cert_live >> (8 * lane));
+            x0 = E2K ? exp_nonpos_t2048c(x0 - m, etab) : exp_nonpos(x0 - m, etab);
+            x1 = E2K ? exp_nonpos_t2048c(x1 - m, etab) : exp_nonpos(x1 - m, etab);
+            double ssum = x0 + x1;
+            ssum = butterfly_sum<LX, 8>(ssum);
+            ssum = butterfly_sum<LX, 16>(ssum);
+            ssum = butterfly_sum<LX, 32>(ssum);
+            double inv = __builtin_amdgcn_rcp(ssum);
+            inv = fma(fma(-ssum, inv, 1.0), inv, inv);
+            inv = fma(fma(-ssum, inv, 1.0), inv, inv);
+            if (part == 0) {            // (a proven row lies inside N)
+              sc_lse += m;
+              sc_prod *= ssum;
+            }
+            src[0] = x0 * inv;
+            src[1] = x1 * inv;
+            return;
+          }
+        }
         const int CPP = 2 * K16, k0 = part * CPP;
         const int64_t n = n0 + pt;
         const bool valid = n < N;
@@ -335,7 +373,8 @@ __device__ __forceinline__ void normalise_tile(const KernelArgs& a, double* __re
           }
         }
         };
-        if (CPP == 8) body(std::true_type{});
+        // (certificates run at K16 = 4 only: that instantiation does not carry the other body, nor the scalars it keeps across tiles)
+        if (CERT == kCertCertified || CPP == 8) body(std::true_type{});
         else body(std::false_type{});
 }
 

@@ -269,6 +269,13 @@ class HipEngine(BoundDataGuard):
         return {"kind": ("plain", "reference", "certified")[int(out[0])], "valid": bool(out[1]), "age": int(out[2]),
                 "proven_rows": int(out[3]), "one_group": int(out[4]), "wave_tiles": int(out[5])}
 
+    def estep_cert_proven_waves(self):
+        """Running total of the context's certified passes (mimo_estep_cert_proven_waves): wave-tiles whose eight rows were all
+        proven and were normalised over each row's live row block only."""
+        out = np.zeros(1, dtype=np.int64)
+        self._check(self._lib.mimo_estep_cert_proven_waves(self._ctx, _ptr(out)))
+        return int(out[0])
+
     def profile(self, enable=True):
         self._check(self._lib.mimo_profile(self._ctx, 1 if enable else 0))
 
